@@ -60,6 +60,10 @@ def parse():
     ap.add_argument('--moco-k', type=int, default=65536)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--dump-launches', default='', help='write a per-launch timing table (calibration step) to this file')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps of the headline leg, write what its last step computed to DIR/<name>.npy: every '
+                         'tensor of the forward\'s output dict, the total loss, and a fixed seeded sample of the model state after '
+                         'the SGD update (state_sample, with its flat indices in state_index)')
     ap.add_argument('--cpu-batch', type=int, default=8)
     ap.add_argument('--cpu-steps', type=int, default=2)
     ap.add_argument('--launch-check', action='store_true',
@@ -145,6 +149,38 @@ def all_plans(model):
             for lst in m._plans.values():
                 for p in lst:
                     yield p
+
+
+DUMP_STATE_SAMPLE = 1 << 20          # elements of the model-state sample --dump-outputs writes
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, ret, loss, model):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy (float32; integer outputs as float64).  The inputs are
+    seeded (run_leg), so two builds run with the same arguments can be compared file by file."""
+    def host(t):
+        t = t.detach().cpu()
+        return t.double().numpy() if not t.is_floating_point() or t.dtype == torch.float64 else t.float().numpy()
+
+    arrays = {'loss': host(loss)}
+    for k, v in ret.items():
+        if torch.is_tensor(v):
+            arrays[k] = host(v)
+    # model state after the step's SGD update (parameters and BatchNorm running statistics, state_dict order): all of it, or
+    # a fixed seeded sample of it when it is larger than DUMP_STATE_SAMPLE elements
+    flat = torch.cat([t.detach().reshape(-1).float().cpu() for t in model.state_dict().values() if t.is_floating_point()])
+    idx = np.arange(flat.numel())
+    if flat.numel() > DUMP_STATE_SAMPLE:
+        idx = np.sort(np.random.RandomState(0).choice(flat.numel(), DUMP_STATE_SAMPLE, replace=False))
+    arrays['state_sample'] = flat[torch.from_numpy(idx)].numpy()
+    arrays['state_index'] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'[bench] --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), a)
+    print(f'[bench] --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MB -> {dirname}', file=sys.stderr, flush=True)
 
 
 def cpu_baseline(args, V):
@@ -332,7 +368,7 @@ def run_leg(args, dtype, rank, world, distributed, dev):
         opt.zero_grad()
         loss.backward()
         opt.step()
-        return loss
+        return loss, ret
 
     for _ in range(max(args.warmup - 1, 1)):
         step()
@@ -370,7 +406,7 @@ def run_leg(args, dtype, rank, world, distributed, dev):
     _rccl.STATS.reset()               # collectives issued inside the timed region (direct RCCL path; c10d calls are not counted)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, ret = step()
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
@@ -383,6 +419,8 @@ def run_leg(args, dtype, rank, world, distributed, dev):
     for p in all_plans(model):
         p.timer = None
     WD.phase(f'{dtype}: report', 120 if wd_on else 0)
+    if args.dump_outputs and rank == 0 and dtype == args.dtype:
+        dump_outputs(args.dump_outputs, ret, loss, model)
 
     print(f'[bench] {dtype}: timed region: {args.steps} steps in {dt:.3f} s', file=sys.stderr, flush=True)
     clips = world * B * V * args.steps

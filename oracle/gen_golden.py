@@ -181,6 +181,48 @@ def case_models_add_f64_step_losses(ref):
               'sens', {('loss_step%d' % it): '%.2e' % float(old['sens/loss_step%d' % it]) for it in range(steps)})
 
 
+def _first_step(ns, kind, net, distributed, block, dt):
+    """step 0 of run_model in dtype `dt`: {'first/out/*', 'first/total_loss', 'first/grad/*', 'first/gsample/*'}"""
+    torch.manual_seed(0)
+    m = build(ns, kind, net, distributed)
+    P.procedural_init(m)
+    m.train().to(dt)
+    np.random.seed(1234)
+    ret = m(block.to(dt))
+    loss = ret['clip_contrast_loss'] if 'clip_contrast_loss' in ret else 0
+    for key in ret:
+        if 'loss' in key and 'clip' not in key:
+            loss = loss + ret[key]
+    loss.backward()
+    rec = {'first/out/' + k: v.detach().numpy().copy() for k, v in ret.items()}
+    rec['first/total_loss'] = np.array(float(loss))
+    rec.update({'first/grad/' + k: v for k, v in grad_summary(m).items()})
+    rec.update({'first/gsample/' + k: v for k, v in P.grad_samples(m).items()})
+    return rec
+
+
+def case_models_add_f64_first(ref):
+    """tests/golden/model_<kind>_<net>_f64.npz next to the committed model fixtures (which stay as they are): the reference's
+    step 0 in float64, keys as `first/*` of the fp32 fixture.  A float32 recomputation on another host sums in another order
+    (other SIMD width, thread count) and can miss the fp32 `first/grad/*` checksums by more than the perturbation sensitivity
+    `sens/*`; in float64 that noise is ~1e-15, so the CPU oracle is pinned to these (tests/test_oracle_golden.py).  The fp32 leg must reproduce the stored step-0 loss bit for bit,
+    and the oracle in float64 must agree with the reference in float64, or this refuses."""
+    _init_pg()
+    for kind, net, B in (('simclr_naked', 'r3d', 2), ('simclr_timeseriesv4', 'r21d', 2),
+                         ('simclr_naked', 's3dg', 4), ('moco_timeseriesv4', 's3dg', 4)):
+        old = np.load(os.path.join(GOLD, f'model_{kind}_{net}.npz'))
+        V = 2 if kind.endswith('naked') else 3
+        block = P.procedural_clips(B, V, **CLIP)
+        r32 = _first_step(ref, kind, net, True, block, torch.float32)
+        assert float(r32['first/total_loss']) == float(old['first/total_loss']), (kind, net)
+        r64 = _first_step(ref, kind, net, True, block, torch.float64)
+        o64 = _first_step(O, kind, net, False, block, torch.float64)
+        err = compare(r64, o64, (kind, net, 'f64'), tol=1e-9)
+        np.savez_compressed(os.path.join(GOLD, f'model_{kind}_{net}_f64.npz'), **r64)
+        print('model', kind, net, 'f64 step 0: ref-vs-oracle %.1e, loss %.8f (fp32 %.8f)' % (
+            err, float(r64['first/total_loss']), float(old['first/total_loss'])))
+
+
 def compare(a, b, tag, tol=5e-4):
     a = {k: v for k, v in a.items() if not k.startswith(('sens/', 'f64/'))}
     b = {k: v for k, v in b.items() if not k.startswith(('sens/', 'f64/'))}
@@ -217,6 +259,29 @@ def case_backbones(ref):
         rec[net + '/fp32_vs_fp64'] = np.array(cond)
         print('backbone', net, tuple(outs[0].shape), 'ref-vs-oracle', err, 'reference fp32-vs-fp64', cond)
     np.savez_compressed(os.path.join(GOLD, 'backbones.npz'), **rec)
+
+
+def case_small_backbones(ref):
+    """tests/golden/backbones_small.npz: R3D / R(2+1)D on 2 x 8x64x64 clips -- the reference's state_dict key order and its
+    outputs in fp32 and fp64 (fp64: thread-count summation noise ~1e-15, so the oracle is pinned to it almost bit for bit)"""
+    rec = {}
+    for net in ('r3d', 'r21d'):
+        x = P.procedural_clips(2, 1, 8, 64, 64)[:, 0]
+        a, _ = ref.select_backbone(net)
+        b, _ = O.select_backbone(net)
+        assert list(a.state_dict().keys()) == list(b.state_dict().keys()), net
+        P.procedural_init(a).train()
+        P.procedural_init(b).train()
+        with torch.no_grad():
+            y, yo = a(x), b(x)
+            y64, yo64 = a.double()(x.double()), b.double()(x.double())
+        assert torch.equal(y, yo) and torch.equal(y64, yo64), net
+        rec[net + '/keys'] = np.array(list(a.state_dict().keys()))
+        rec[net + '/feat'] = y.numpy()
+        rec[net + '/feat64'] = y64.numpy()
+        rec[net + '/fp32_vs_fp64'] = np.array(float((y.double() - y64).abs().max() / y64.abs().max()))
+        print('small backbone', net, tuple(y.shape), 'reference fp32-vs-fp64', float(rec[net + '/fp32_vs_fp64']))
+    np.savez_compressed(os.path.join(GOLD, 'backbones_small.npz'), **rec)
 
 
 def case_eval(ref):
@@ -698,12 +763,14 @@ def case_shapes(ref):
 def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ['backbones', 'models', 'losses', 'eval', 'clf', 'extra', 'augment', 'shapes']
+    which = sys.argv[1:] or ['backbones', 'small', 'models', 'losses', 'eval', 'clf', 'extra', 'augment', 'shapes']
     if 'losses' in which:
         case_losses()
     ref = harness.load_reference()
     if 'backbones' in which:
         case_backbones(ref)
+    if 'small' in which:
+        case_small_backbones(ref)
     if 'eval' in which:
         case_eval(ref)
     if 'clf' in which:
@@ -718,6 +785,8 @@ def main():
         case_models(ref)
     if 'models_f64_losses' in which:
         case_models_add_f64_step_losses(ref)
+    if 'models_f64_first' in which:
+        case_models_add_f64_first(ref)
 
 
 if __name__ == '__main__':
