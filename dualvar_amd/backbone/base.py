@@ -43,8 +43,9 @@ class IngestOp(Op):
     def bind(self, x, perm, mean, istd):
         self.src, self.perm, self.mean, self.istd = x, perm, mean, istd
         if isinstance(x, FrameBatch):
-            if self.cmean is None:
-                self.cmean = torch.empty(self.N * self.T, dtype=torch.float32, device=x.device)
+            need = self.N * self.T * (x.n_block * x.n_block if x.patches is not None else 1)     # one contrast mean per frame (patch)
+            if self.cmean is None or self.cmean.numel() < need:
+                self.cmean = torch.empty(need, dtype=torch.float32, device=x.device)
             if x.blur is not None and getattr(self, 'blur_tmp', None) is None:      # quantised frames in front of the blur
                 self.blur_tmp = torch.empty(self.N * self.T * self.H * self.W * 3, dtype=torch.uint8, device=x.device)
             return
@@ -55,6 +56,19 @@ class IngestOp(Op):
         if isinstance(self.src, FrameBatch):
             # decoded uint8 frames + augmentation table -> the same NDHWC stem input (utils/transforms.py: FrameBatch)
             fb = self.src
+            if fb.patches is not None:           # block-wise colour jitter: one op list per (frame, patch)
+                L.check(p.lib.dv_augment_ingest_blocks(p.dtype, fb.frames.data_ptr(), fb.frames.shape[0], fb.frames.shape[1],
+                                                       fb.frames.shape[2], fb.table.data_ptr(), self.N, self.T, self.H, self.W,
+                                                       self.y.ptr, self.y.ld, self.pad,
+                                                       self.mean.data_ptr() if self.mean is not None else 0,
+                                                       self.istd.data_ptr() if self.istd is not None else 0,
+                                                       self.perm.data_ptr() if self.perm is not None else 0,
+                                                       self.n_seg if self.perm is not None else 0, self.cmean.data_ptr(),
+                                                       fb.blur.data_ptr() if fb.blur is not None else 0,
+                                                       self.blur_tmp.data_ptr() if fb.blur is not None else 0,
+                                                       fb.patches.data_ptr(), fb.n_block, stream),
+                        'dv_augment_ingest_blocks')
+                return
             L.check(p.lib.dv_augment_ingest(p.dtype, fb.frames.data_ptr(), fb.frames.shape[0], fb.frames.shape[1],
                                             fb.frames.shape[2], fb.table.data_ptr(), self.N, self.T, self.H, self.W,
                                             self.y.ptr, self.y.ld, self.pad,

@@ -2,6 +2,8 @@
 // NDHWC activations of the RGB stem, in two launches (three with blurred frames).  The arithmetic follows the reference's tensor-side
 // definitions, utils/transforms.py:13-31 (crop, hflip), :33-42 (bilinear resize, align_corners=False), :49-51 (/255),
 // :57-63 (normalize), :66-78 (luma), :90-163 (brightness / contrast / saturation blends with clamp to [0, 1]).
+// The block-wise entry (dv_augment_ingest_blocks) runs the same kernels with `Patched`: an nb x nb grid of patches per frame,
+// each with its own op list and its own contrast mean (the reference's ColorJitter(block=nb), utils/augmentation.py:587-652).
 #include "common.hpp"
 
 namespace {
@@ -17,7 +19,8 @@ struct AugArgs {
   float* cmean;                     // [F] mean luma in front of the contrast op
   const dv_aug_blur* blur;          // optional [F]: Gaussian blur of the finished frame (ww == 0: none)
   uint8_t* u8tmp;                   // [F][H][W][3] quantised frames in front of the blur
-  int n_src, Hs, Ws, F, T, n_seg, H, W, ldy, pad, Hp, Wp;
+  const dv_aug_patch* patches;      // Patched kernels: [F][nb * nb] op lists, row-major patch order, rows parallel to `tab`
+  int n_src, Hs, Ws, F, T, n_seg, H, W, ldy, pad, Hp, Wp, nb;
 };
 
 struct Rgb { float r, g, b; };
@@ -61,8 +64,9 @@ __device__ __forceinline__ Rgb sample(const AugArgs& a, const dv_aug_frame& q, i
   return o;
 }
 
-// colour ops op[from .. to) of a frame; `cm` = mean luma for the contrast op
-__device__ __forceinline__ Rgb colour_ops(Rgb p, const dv_aug_frame& q, int to, float cm) {
+// colour ops op[0 .. to) of a frame row or a patch row; `cm` = mean luma for the contrast op
+template <typename Ops>
+__device__ __forceinline__ Rgb colour_ops(Rgb p, const Ops& q, int to, float cm) {
   for (int k = 0; k < to; ++k) {
     const float f = q.factor[k], g = 1.f - f;
     switch (q.op[k]) {
@@ -110,24 +114,38 @@ __device__ __forceinline__ Rgb colour_ops(Rgb p, const dv_aug_frame& q, int to, 
   return p;
 }
 
-__device__ __forceinline__ int contrast_pos(const dv_aug_frame& q) {
+template <typename Ops>
+__device__ __forceinline__ int contrast_pos(const Ops& q) {
   for (int k = 0; k < DV_AUG_MAX_OPS; ++k)
     if (q.op[k] == DV_AUG_CONTRAST) return k;
   return -1;
 }
 
-// one workgroup per output frame: mean luma of the window as the contrast op sees it (fixed summation order)
-__global__ void __launch_bounds__(kThreads) aug_contrast_mean_kernel(AugArgs a) {
-  const int f = blockIdx.x;
-  const dv_aug_frame q = a.tab[table_row(a, f)];
-  const int kc = contrast_pos(q);
+// patch `pi` (row-major) of an nb x nb grid: rows [h0, h0 + ph), columns [w0, w0 + pw); the last row / column of patches takes
+// the remainder (utils/augmentation.py:600-610)
+__device__ __forceinline__ void patch_rect(const AugArgs& a, int pi, int& h0, int& ph, int& w0, int& pw) {
+  const int hu = a.H / a.nb, wu = a.W / a.nb, bi = pi / a.nb, bj = pi - bi * a.nb;
+  h0 = bi * hu; ph = bi < a.nb - 1 ? hu : a.H - h0;
+  w0 = bj * wu; pw = bj < a.nb - 1 ? wu : a.W - w0;
+}
+
+// patch of output pixel (hh, ww) (post-crop, post-resize, post-flip coordinates)
+__device__ __forceinline__ int patch_of(const AugArgs& a, int hh, int ww) {
+  return min(hh / (a.H / a.nb), a.nb - 1) * a.nb + min(ww / (a.W / a.nb), a.nb - 1);
+}
+
+// mean luma of a window of the frame as the op list `o` sees it in front of its contrast op (fixed summation order)
+template <typename Ops>
+__device__ __forceinline__ void window_mean(const AugArgs& a, const dv_aug_frame& q, const Ops& o, int h0, int ph, int w0, int pw,
+                                            float* out) {
+  const int kc = contrast_pos(o);
   if (kc < 0) return;
   __shared__ float sh[kThreads / 64];
   float s = 0.f;
-  const int px = a.H * a.W;
+  const int px = ph * pw;
   for (int i = threadIdx.x; i < px; i += kThreads) {
-    const int hh = i / a.W, ww = i - hh * a.W;
-    s += luma(colour_ops(sample(a, q, hh, ww), q, kc, 0.f));
+    const int hh = i / pw, ww = i - hh * pw;
+    s += luma(colour_ops(sample(a, q, h0 + hh, w0 + ww), o, kc, 0.f));
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
@@ -135,11 +153,29 @@ __global__ void __launch_bounds__(kThreads) aug_contrast_mean_kernel(AugArgs a) 
   if (threadIdx.x == 0) {
     float t = 0.f;
     for (int i = 0; i < kThreads / 64; ++i) t += sh[i];
-    a.cmean[f] = t / (float)px;
+    *out = t / (float)px;
   }
 }
 
-template <typename T>
+// one workgroup per output frame (Patched: per (frame, patch)): mean luma in front of the contrast op
+template <bool Patched>
+__global__ void __launch_bounds__(kThreads) aug_contrast_mean_kernel(AugArgs a) {
+  if (!Patched) {
+    const int f = blockIdx.x;
+    const dv_aug_frame q = a.tab[table_row(a, f)];
+    window_mean(a, q, q, 0, a.H, 0, a.W, a.cmean + f);
+    return;
+  }
+  const int nb2 = a.nb * a.nb, f = blockIdx.x / nb2, pi = blockIdx.x - f * nb2;
+  const int row = table_row(a, f);
+  const dv_aug_frame q = a.tab[row];
+  const dv_aug_patch o = a.patches[(int64_t)row * nb2 + pi];
+  int h0, ph, w0, pw;
+  patch_rect(a, pi, h0, ph, w0, pw);
+  window_mean(a, q, o, h0, ph, w0, pw, a.cmean + (int64_t)f * nb2 + pi);
+}
+
+template <typename T, bool Patched>
 __global__ void __launch_bounds__(kThreads) aug_apply_kernel(AugArgs a, T* __restrict__ y) {
   const int64_t px = (int64_t)a.H * a.W, total = px * a.F;
   for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kThreads) {
@@ -147,7 +183,14 @@ __global__ void __launch_bounds__(kThreads) aug_apply_kernel(AugArgs a, T* __res
     const int hw = (int)(i - (int64_t)f * px);
     const int hh = hw / a.W, ww = hw - hh * a.W;
     const dv_aug_frame q = a.tab[table_row(a, f)];
-    Rgb p = colour_ops(sample(a, q, hh, ww), q, DV_AUG_MAX_OPS, contrast_pos(q) >= 0 ? a.cmean[f] : 0.f);
+    Rgb p;
+    if (Patched) {
+      const int nb2 = a.nb * a.nb, pi = patch_of(a, hh, ww);
+      const dv_aug_patch o = a.patches[(int64_t)table_row(a, f) * nb2 + pi];
+      p = colour_ops(sample(a, q, hh, ww), o, DV_AUG_MAX_OPS, contrast_pos(o) >= 0 ? a.cmean[(int64_t)f * nb2 + pi] : 0.f);
+    } else {
+      p = colour_ops(sample(a, q, hh, ww), q, DV_AUG_MAX_OPS, contrast_pos(q) >= 0 ? a.cmean[f] : 0.f);
+    }
     if (a.blur && a.blur[table_row(a, f)].ww != 0) {
       // this frame goes through the blur: ToPILImage() of the float frame = mul(255).byte() (truncation), utils/augmentation.py:719
       uint8_t* u = a.u8tmp + ((int64_t)f * px + hw) * 3;
@@ -214,39 +257,22 @@ __global__ void __launch_bounds__(kThreads) aug_blur_kernel(AugArgs a, T* __rest
   }
 }
 
-}  // namespace
-
-extern "C" int dv_augment_ingest(int32_t dtype, const uint8_t* frames, int32_t n_src, int32_t Hs, int32_t Ws,
-                                 const dv_aug_frame* table, int32_t N, int32_t T_, int32_t H, int32_t W, void* y, int32_t ldy,
-                                 int32_t pad, const float* mean3, const float* istd3, const int32_t* perm, int32_t n_seg,
-                                 float* scratch, const dv_aug_blur* blur, uint8_t* blur_scratch, void* stream) {
-  if (blur && (!blur_scratch || (int64_t)H * W * 2 > 160 * 1024)) return DV_EINVAL;
-  if (!frames || !table || !y || !scratch || n_src <= 0 || Hs <= 0 || Ws <= 0 || N <= 0 || T_ <= 0 || H <= 0 || W <= 0 ||
-      ldy < 4 || ldy % 4 || pad < 0)
-    return DV_EINVAL;
-  if ((int64_t)N * T_ > 0x7fffffff / 4) return DV_EINVAL;
-  if (perm && (n_seg <= 0 || T_ % n_seg)) return DV_EINVAL;
-  if ((mean3 == nullptr) != (istd3 == nullptr)) return DV_EINVAL;
-  if (dtype != DV_F32 && dtype != DV_BF16) return DV_EUNSUPPORTED;
-  AugArgs a;
-  a.frames = frames; a.tab = table; a.perm = perm; a.mean3 = mean3; a.istd3 = istd3; a.cmean = scratch;
-  a.blur = blur; a.u8tmp = blur_scratch;
-  a.n_src = n_src; a.Hs = Hs; a.Ws = Ws; a.F = N * T_; a.T = T_; a.n_seg = perm ? n_seg : 1;
-  a.H = H; a.W = W; a.ldy = ldy; a.pad = pad; a.Hp = H + 2 * pad; a.Wp = W + 2 * pad;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(aug_contrast_mean_kernel, dim3(a.F), dim3(kThreads), 0, st, a);
+// the launches of both entries (arguments checked by the caller)
+template <bool Patched>
+int launch_ingest(const AugArgs& a, int32_t dtype, void* y, hipStream_t st) {
+  hipLaunchKernelGGL(aug_contrast_mean_kernel<Patched>, dim3(a.F * (Patched ? a.nb * a.nb : 1)), dim3(kThreads), 0, st, a);
   int rc = dv_launch_status();
   if (rc) return rc;
-  const int64_t total = (int64_t)a.F * H * W;
+  const int64_t total = (int64_t)a.F * a.H * a.W;
   const int blocks = (int)((total + kThreads - 1) / kThreads < 8192 ? (total + kThreads - 1) / kThreads : 8192);
   if (dtype == DV_F32)
-    hipLaunchKernelGGL((aug_apply_kernel<float>), dim3(blocks), dim3(kThreads), 0, st, a, (float*)y);
+    hipLaunchKernelGGL((aug_apply_kernel<float, Patched>), dim3(blocks), dim3(kThreads), 0, st, a, (float*)y);
   else
-    hipLaunchKernelGGL((aug_apply_kernel<bf16_t>), dim3(blocks), dim3(kThreads), 0, st, a, (bf16_t*)y);
-  if (blur) {
+    hipLaunchKernelGGL((aug_apply_kernel<bf16_t, Patched>), dim3(blocks), dim3(kThreads), 0, st, a, (bf16_t*)y);
+  if (a.blur) {
     rc = dv_launch_status();
     if (rc) return rc;
-    const size_t lds = (size_t)H * W * 2;
+    const size_t lds = (size_t)a.H * a.W * 2;
     if (dtype == DV_F32) {
       if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)aug_blur_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL((aug_blur_kernel<float>), dim3(a.F * 3), dim3(kThreads), lds, st, a, (float*)y);
@@ -256,4 +282,53 @@ extern "C" int dv_augment_ingest(int32_t dtype, const uint8_t* frames, int32_t n
     }
   }
   return dv_launch_status();
+}
+
+// argument checks and AugArgs of both entries
+int setup(AugArgs& a, int32_t dtype, const uint8_t* frames, int32_t n_src, int32_t Hs, int32_t Ws, const dv_aug_frame* table,
+          int32_t N, int32_t T_, int32_t H, int32_t W, void* y, int32_t ldy, int32_t pad, const float* mean3, const float* istd3,
+          const int32_t* perm, int32_t n_seg, float* scratch, const dv_aug_blur* blur, uint8_t* blur_scratch) {
+  if (blur && (!blur_scratch || (int64_t)H * W * 2 > 160 * 1024)) return DV_EINVAL;
+  if (!frames || !table || !y || !scratch || n_src <= 0 || Hs <= 0 || Ws <= 0 || N <= 0 || T_ <= 0 || H <= 0 || W <= 0 ||
+      ldy < 4 || ldy % 4 || pad < 0)
+    return DV_EINVAL;
+  if ((int64_t)N * T_ > 0x7fffffff / 4) return DV_EINVAL;
+  if (perm && (n_seg <= 0 || T_ % n_seg)) return DV_EINVAL;
+  if ((mean3 == nullptr) != (istd3 == nullptr)) return DV_EINVAL;
+  if (dtype != DV_F32 && dtype != DV_BF16) return DV_EUNSUPPORTED;
+  a.frames = frames; a.tab = table; a.perm = perm; a.mean3 = mean3; a.istd3 = istd3; a.cmean = scratch;
+  a.blur = blur; a.u8tmp = blur_scratch; a.patches = nullptr;
+  a.n_src = n_src; a.Hs = Hs; a.Ws = Ws; a.F = N * T_; a.T = T_; a.n_seg = perm ? n_seg : 1;
+  a.H = H; a.W = W; a.ldy = ldy; a.pad = pad; a.Hp = H + 2 * pad; a.Wp = W + 2 * pad; a.nb = 1;
+  return DV_OK;
+}
+
+}  // namespace
+
+extern "C" int dv_augment_ingest(int32_t dtype, const uint8_t* frames, int32_t n_src, int32_t Hs, int32_t Ws,
+                                 const dv_aug_frame* table, int32_t N, int32_t T_, int32_t H, int32_t W, void* y, int32_t ldy,
+                                 int32_t pad, const float* mean3, const float* istd3, const int32_t* perm, int32_t n_seg,
+                                 float* scratch, const dv_aug_blur* blur, uint8_t* blur_scratch, void* stream) {
+  AugArgs a;
+  const int rc = setup(a, dtype, frames, n_src, Hs, Ws, table, N, T_, H, W, y, ldy, pad, mean3, istd3, perm, n_seg, scratch, blur,
+                       blur_scratch);
+  if (rc) return rc;
+  return launch_ingest<false>(a, dtype, y, (hipStream_t)stream);
+}
+
+extern "C" int dv_augment_ingest_blocks(int32_t dtype, const uint8_t* frames, int32_t n_src, int32_t Hs, int32_t Ws,
+                                        const dv_aug_frame* table, int32_t N, int32_t T_, int32_t H, int32_t W, void* y,
+                                        int32_t ldy, int32_t pad, const float* mean3, const float* istd3, const int32_t* perm,
+                                        int32_t n_seg, float* scratch, const dv_aug_blur* blur, uint8_t* blur_scratch,
+                                        const dv_aug_patch* patches, int32_t n_block, void* stream) {
+  if (n_block < 1 || n_block > 8 || n_block > H || n_block > W || (!patches && n_block > 1)) return DV_EINVAL;
+  if ((int64_t)N * T_ * n_block * n_block > 0x7fffffff / 4) return DV_EINVAL;           // contrast grid and scratch index
+  AugArgs a;
+  const int rc = setup(a, dtype, frames, n_src, Hs, Ws, table, N, T_, H, W, y, ldy, pad, mean3, istd3, perm, n_seg, scratch, blur,
+                       blur_scratch);
+  if (rc) return rc;
+  if (!patches) return launch_ingest<false>(a, dtype, y, (hipStream_t)stream);      // n_block == 1: the frame rows' own ops
+  a.patches = patches;
+  a.nb = n_block;
+  return launch_ingest<true>(a, dtype, y, (hipStream_t)stream);
 }

@@ -37,6 +37,8 @@ AUG_MAX_OPS = 5
 AUG_ROW = np.dtype([('src', '<i4'), ('crop_i', '<i4'), ('crop_j', '<i4'), ('crop_h', '<i4'), ('crop_w', '<i4'), ('flip', '<i4'),
                     ('op', '<i4', (AUG_MAX_OPS,)), ('factor', '<f4', (AUG_MAX_OPS,))])                   # include/dualvar_hip.h
 AUG_BLUR = np.dtype([('radius', '<i4'), ('ww', '<u4'), ('fw', '<u4'), ('_pad', '<i4')])                  # dv_aug_blur
+AUG_PATCH = np.dtype([('op', '<i4', (AUG_MAX_OPS,)), ('factor', '<f4', (AUG_MAX_OPS,))])                 # dv_aug_patch
+AUG_MAX_BLOCK = 8                                                                                        # dv_augment_ingest_blocks
 
 
 def box_blur_params(sigma, passes=3):
@@ -69,6 +71,9 @@ class ClipState:
         self.flip = False
         self.ops = []                                          # [(code, factors[N])], in applied order
         self.sigma = None                                      # per-frame Gaussian blur sigma (0: none), set by GaussianBlur
+        # block-wise colour jitter (ColorJitter(block=b) / grad_consistent): b, the frame-wide ops in front of it, and per frame
+        # and per patch (row-major) its own [(code, factor)] list; self.ops then collects what comes after it
+        self.block, self.pre, self.patch_ops = None, None, None
 
     @property
     def N(self):
@@ -80,7 +85,7 @@ class ClipState:
     def _no_colour_yet(self, what):
         if self.sigma is not None:
             raise ValueError('%s after the Gaussian blur: the blur is the last op of a dv_augment_ingest pipeline' % what)
-        if self.ops:
+        if self.ops or self.block is not None:
             raise ValueError('%s after a colour op is not expressible in one dv_augment_ingest row' % what)
 
     def crop(self, i, j, h, w):
@@ -91,7 +96,20 @@ class ClipState:
             raise ValueError('crop after a flip: put the crop first')
         self.i, self.j, self.h, self.w = self.i + i, self.j + j, h, w
 
+    def set_patches(self, block, patch_ops):
+        """a block-wise colour jitter ran: patch_ops[n][p] = [(code, factor)] of frame n, patch p (row-major, block x block)"""
+        if self.block is not None:
+            raise ValueError('two block-wise colour jitters in one pipeline')
+        if self.sigma is not None:
+            raise ValueError('colour jitter after the Gaussian blur: the blur is the last op of a dv_augment_ingest pipeline')
+        self.block, self.pre, self.patch_ops, self.ops = block, self.ops, patch_ops, []
+
+    @staticmethod
+    def _frame_ops(ops, n):
+        return [(code, fac[n]) for code, fac in ops if not (code == AUG_GRAY and not fac[n])]
+
     def rows(self, H, W):
+        """one dv_aug_frame row per frame; after a block-wise jitter the rows carry the geometry only (ops: patch_rows)"""
         oh, ow = self.size()
         if (oh, ow) != (H, W):
             raise ValueError('pipeline produces %dx%d frames, the plan wants %dx%d' % (oh, ow, H, W))
@@ -100,6 +118,8 @@ class ClipState:
         t = np.zeros(self.N, dtype=AUG_ROW)
         t['src'], t['crop_i'], t['crop_j'], t['crop_h'], t['crop_w'] = self.src, self.i, self.j, self.h, self.w
         t['flip'] = int(self.flip)
+        if self.block is not None:
+            return t
         for n in range(self.N):
             k = 0
             for code, fac in self.ops:
@@ -107,6 +127,33 @@ class ClipState:
                     continue
                 t['op'][n, k], t['factor'][n, k] = code, fac[n]
                 k += 1
+        return t
+
+    def patch_rows(self, H, W, block=None):
+        """N * block^2 dv_aug_patch entries, frame-major, patches row-major: frame-wide ops in front of the block-wise jitter, the
+        patch's own ops, then the ops after it.  `block` = the batch's grid (default: this clip's); a clip without a block-wise
+        jitter (RandomApply skipped it) repeats its frame ops in every patch, which is exact unless one of them is a contrast"""
+        block = block if block is not None else (self.block or 1)
+        if self.block is not None and self.block != block:
+            raise ValueError('clip jittered on a %dx%d grid, the batch uses %dx%d' % (self.block, self.block, block, block))
+        if not 1 <= block <= min(H, W, AUG_MAX_BLOCK):
+            raise ValueError('a %dx%d patch grid does not fit %dx%d frames (at most %d)' % (block, block, H, W, AUG_MAX_BLOCK))
+        self.rows(H, W)                                        # size check and the limits of the frame-wide ops
+        nb2 = block * block
+        t = np.zeros(self.N * nb2, dtype=AUG_PATCH)
+        for n in range(self.N):
+            if self.block is None:
+                lists = [self._frame_ops(self.ops, n)] * nb2
+                if block > 1 and any(c == AUG_CONTRAST for c, _ in lists[0]):
+                    raise ValueError('a frame-wide contrast op cannot run on a %dx%d patch grid' % (block, block))
+            else:
+                pre, post = self._frame_ops(self.pre, n), self._frame_ops(self.ops, n)
+                lists = [pre + list(own) + post for own in self.patch_ops[n]]
+            for p, ops in enumerate(lists):
+                if len(ops) > AUG_MAX_OPS or sum(1 for c, _ in ops if c == AUG_CONTRAST) > 1:
+                    raise ValueError('at most %d colour ops and one contrast per patch' % AUG_MAX_OPS)
+                for k, (code, f) in enumerate(ops):
+                    t['op'][n * nb2 + p, k], t['factor'][n * nb2 + p, k] = code, f
         return t
 
     def blur_rows(self):
@@ -219,14 +266,37 @@ class RandomGray(object):                                   # transforms.py:80-8
 class ColorJitter(object):                                  # transforms.py:313-373
     """`hue` is an extension: the reference's tensor-side ColorJitter has none, its PIL one (utils/augmentation.py:429-508,
     the `ColorJitter(0.8, 0.8, 0.8, 0.2)` of pretrain.py:503) draws a shift in [-hue, hue] turns; here it joins the shuffled
-    list like the other three and runs as DV_AUG_HUE (`adjust_hue_np`'s arithmetic)."""
+    list like the other three and runs as DV_AUG_HUE (`adjust_hue_np`'s arithmetic).
 
-    def __init__(self, brightness=0, contrast=0, saturation=0, consistent=False, p=1.0, n_channel=1, gray_channel=0, hue=0):
+    `block`, `seq_len`, `grad_consistent`, `n_seqblock`: the block-wise and time-graded modes of the reference's
+    utils/augmentation.py:ColorJitter (:429-661, its `A.ColorJitter(..., block=args.n_block, grad_consistent=
+    args.aug_temp_grad_consist)` of pretrain.py:504-506).  With block > 1 or grad_consistent the class draws as that class's
+    __call__ draws (:587-652), call for call, and fills per-patch op lists (ClipState.patch_rows -> dv_augment_ingest_blocks):
+      * block-wise: every frame (under `consistent`: every n_seqblock-th frame) draws, for each of the block x block patches,
+        the gate np.random.uniform(0, 1) < p and, when it passes, get_params (:482-510): random.uniform factors in the order
+        brightness, contrast, saturation, hue, then random.shuffle of the list;
+      * time-graded: every seq_len-th frame draws, per patch, get_grad_consistent_factors (:512-525: a start and an end per op)
+        and a random.shuffle of [0, 1, 2, 3]; frame t runs all four ops with np.linspace(start, end, seq_len)[t], in that
+        order (get_params_fixed, :528-551).  The gate p is not used.
+    With block == 1 and grad_consistent False (the default) nothing of this applies: the tensor-side draws above."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, consistent=False, p=1.0, n_channel=1, gray_channel=0, hue=0,
+                 block=1, seq_len=16, grad_consistent=False, n_seqblock=0):
         self.brightness = self._check_input(brightness, 'brightness')
         self.contrast = self._check_input(contrast, 'contrast')
         self.saturation = self._check_input(saturation, 'saturation')
         self.hue = self._check_input(hue, 'hue', center=0, bound=(-0.5, 0.5))
         self.consistent, self.p = consistent, p
+        if not isinstance(block, int) or not 1 <= block <= AUG_MAX_BLOCK:
+            raise ValueError('block must be an integer in [1, %d], got %r' % (AUG_MAX_BLOCK, block))
+        if consistent and grad_consistent:                  # utils/augmentation.py:452
+            raise ValueError('consistent and grad_consistent are mutually exclusive')
+        if grad_consistent and None in (self.brightness, self.contrast, self.saturation, self.hue):
+            raise ValueError('grad_consistent draws all four factors: brightness, contrast, saturation and hue need a range')
+        self.n_seqblock = n_seqblock if n_seqblock != 0 else seq_len
+        if seq_len < 1 or seq_len % self.n_seqblock:        # :459
+            raise ValueError('seq_len (%d) must be a positive multiple of n_seqblock (%d)' % (seq_len, self.n_seqblock))
+        self.block, self.seq_len, self.grad_consistent = block, seq_len, grad_consistent
 
     @staticmethod
     def _check_input(value, name, center=1, bound=(0, float('inf'))):
@@ -248,7 +318,46 @@ class ColorJitter(object):                                  # transforms.py:313-
             return np.array([random.uniform(rng[0], rng[1])] * N)
         return np.random.uniform(rng[0], rng[1], size=(N,))
 
+    def _patch_params(self):                                # get_params (utils/augmentation.py:482-510): draws, then the shuffle
+        ops = []
+        for code, rng in ((AUG_BRIGHTNESS, self.brightness), (AUG_CONTRAST, self.contrast), (AUG_SATURATION, self.saturation),
+                          (AUG_HUE, self.hue)):
+            if rng is not None:
+                ops.append((code, np.float32(random.uniform(rng[0], rng[1]))))
+        random.shuffle(ops)
+        return ops
+
+    def _grad_factors(self):                                # get_grad_consistent_factors (:512-525) -> [seq_len, 4]
+        cols = []
+        for rng in (self.brightness, self.contrast, self.saturation, self.hue):
+            start, end = random.uniform(*rng), random.uniform(*rng)
+            cols.append(np.linspace(start, end, self.seq_len))
+        return np.stack(cols, axis=1)
+
+    def _patched(self, st):                                 # ColorJitter.__call__ (:587-652), the draws only
+        nb2, per_frame = self.block * self.block, []
+        codes = (AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE)
+        for idx in range(st.N):
+            if not self.grad_consistent:
+                if not self.consistent or idx % self.n_seqblock == 0:
+                    cur = [self._patch_params() if np.random.uniform(0., 1.) < self.p else [] for _ in range(nb2)]
+                per_frame.append(cur)
+            else:
+                if idx % self.seq_len == 0:
+                    graded = []
+                    for _ in range(nb2):
+                        fac = self._grad_factors().astype(np.float32)
+                        order = [0, 1, 2, 3]
+                        random.shuffle(order)
+                        graded.append((fac, order))
+                t = idx % self.seq_len
+                per_frame.append([[(codes[i], fac[t, i]) for i in order] for fac, order in graded])
+        st.set_patches(self.block, per_frame)
+        return st
+
     def __call__(self, st):
+        if self.block > 1 or self.grad_consistent:
+            return self._patched(st)
         if random.random() < self.p:
             todo = []                                       # get_params: the list is shuffled BEFORE any factor is drawn
             if self.brightness is not None:
@@ -314,18 +423,23 @@ class FrameBatch(object):
     """Decoded uint8 frames + one augmentation row per output frame: what the backbones' ingest consumes in place of a
     float clip tensor.  Quacks like the `[B, V, 3, T, H, W]` (or `[N, 3, T, H, W]`) tensor the models index."""
 
-    def __init__(self, frames, table, shape, blur=None):
+    def __init__(self, frames, table, shape, blur=None, patches=None, n_block=1):
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
             raise ValueError('frames must be uint8 [n_src, Hs, Ws, 3]')
         self.frames = frames.contiguous()
         self.table = table                                   # uint8 device tensor [rows * 64], rows in clip-major order
         self.blur = blur                                     # None, or uint8 device tensor [rows * 16] (dv_aug_blur), same order
+        # None, or uint8 device tensor [rows * n_block^2 * 40] (dv_aug_patch): the op lists of the block-wise colour jitter
+        self.patches, self.n_block = patches, n_block if patches is not None else 1
         self.shape = torch.Size(shape)
         rows = 1
         for d in self.shape[:-4]:
             rows *= d
         if table.numel() != rows * self.shape[-3] * AUG_ROW.itemsize:
             raise ValueError('table has %d bytes, shape %s needs %d rows' % (table.numel(), tuple(shape), rows * self.shape[-3]))
+        if patches is not None and patches.numel() != rows * self.shape[-3] * n_block * n_block * AUG_PATCH.itemsize:
+            raise ValueError('patches have %d bytes, %d rows of a %dx%d grid need %d' % (
+                patches.numel(), rows * self.shape[-3], n_block, n_block, rows * self.shape[-3] * n_block * n_block * AUG_PATCH.itemsize))
         self.is_cuda, self.device, self.dtype, self.requires_grad = frames.is_cuda, frames.device, torch.float32, False
 
     @classmethod
@@ -333,19 +447,27 @@ class FrameBatch(object):
         """frames: uint8 [n_src, Hs, Ws, 3]; clips: per sample the source-frame indices of its T frames; every one of
         the `views` views of a sample draws its own augmentation (pretrain's two clips of a video)."""
         Hs, Ws = frames.shape[1:3]
-        rows, blurs = [], []
+        rows, blurs, states = [], [], []
         for src in clips:
             for _ in range(views):
                 st = transform(ClipState(src, Hs, Ws))
                 rows.append(st.rows(*size))
                 blurs.append(st.blur_rows())
+                states.append(st)
         T = len(clips[0])
         tab, btab = np.concatenate(rows), np.concatenate(blurs)
         device = device if device is not None else frames.device
         t = torch.from_numpy(tab.view(np.uint8).copy()).to(device)
         b = torch.from_numpy(btab.view(np.uint8).copy()).to(device) if btab['ww'].any() else None
         shape = (len(clips), views, 3, T) + tuple(size) if views > 1 else (len(clips), 3, T) + tuple(size)
-        return cls(frames.to(device), t, shape, blur=b)
+        blocks = {st.block for st in states if st.block is not None}
+        if not blocks:
+            return cls(frames.to(device), t, shape, blur=b)
+        if len(blocks) > 1:
+            raise ValueError('clips of one batch jittered on different patch grids: %s' % sorted(blocks))
+        nb = blocks.pop()
+        ptab = np.concatenate([st.patch_rows(size[0], size[1], nb) for st in states])
+        return cls(frames.to(device), t, shape, blur=b, patches=torch.from_numpy(ptab.view(np.uint8).copy()).to(device), n_block=nb)
 
     def dim(self):
         return len(self.shape)
@@ -364,7 +486,7 @@ class FrameBatch(object):
         n = 1
         for d in s[:-4]:
             n *= d
-        return FrameBatch(self.frames, self.table, (n,) + tuple(s[-4:]), blur=self.blur)
+        return FrameBatch(self.frames, self.table, (n,) + tuple(s[-4:]), blur=self.blur, patches=self.patches, n_block=self.n_block)
 
     def reshape(self, *shape):
         shape = tuple(shape[0]) if len(shape) == 1 and not isinstance(shape[0], int) else tuple(shape)
@@ -393,7 +515,13 @@ class FrameBatch(object):
             blur = torch.cat([b.blur.view(-1) if b.blur is not None else
                               torch.zeros(b.table.numel() // AUG_ROW.itemsize * AUG_BLUR.itemsize, dtype=torch.uint8, device=b.table.device)
                               for b in batches])
-        return FrameBatch(first.frames, table, (sum(b.shape[0] for b in batches),) + tuple(first.shape[1:]), blur=blur)
+        patches = None
+        if any(b.patches is not None for b in batches):
+            if any(b.patches is None or b.n_block != first.n_block for b in batches):
+                raise ValueError('FrameBatch.cat: batches must all carry patch op lists of one grid, or none')
+            patches = torch.cat([b.patches.view(-1) for b in batches])
+        return FrameBatch(first.frames, table, (sum(b.shape[0] for b in batches),) + tuple(first.shape[1:]), blur=blur,
+                          patches=patches, n_block=first.n_block)
 
     def __getitem__(self, idx):
         # block[:, v]: one view of every sample
@@ -404,5 +532,8 @@ class FrameBatch(object):
             bl = None
             if self.blur is not None:
                 bl = self.blur.view(B, V, T * AUG_BLUR.itemsize)[:, idx[1]].contiguous().view(-1)
-            return FrameBatch(self.frames, t, (B,) + tuple(self.shape[2:]), blur=bl)
+            pt = None
+            if self.patches is not None:
+                pt = self.patches.view(B, V, -1)[:, idx[1]].contiguous().view(-1)
+            return FrameBatch(self.frames, t, (B,) + tuple(self.shape[2:]), blur=bl, patches=pt, n_block=self.n_block)
         raise NotImplementedError('FrameBatch supports block[:, v] only')

@@ -36,7 +36,8 @@ extern "C" {
    built with and a consumer must refuse a library whose value differs from the header it was compiled against.
    2: dv_conv3d_wgrad (workspace, workspace_bytes), dv_bn_bwd_reduce (ws), dv_infonce_fwd (workspace, bytes),
       dv_augment_ingest (blur, blur_scratch) gained arguments; dv_bn_item grew by red_ws (round 2 of this build).
-   (dv_conv3d_ksplit_cols, dv_conv3d_wgrad_bn, dv_conv3d_wgrad_bn_ok were ADDED under version 2: additions do not bump it.) */
+   (dv_conv3d_ksplit_cols, dv_conv3d_wgrad_bn, dv_conv3d_wgrad_bn_ok, dv_augment_ingest_blocks / dv_aug_patch were ADDED under
+   version 2: additions do not bump it.) */
 #define DV_ABI_VERSION 2
 
 enum { DV_F32 = 0, DV_BF16 = 1 };
@@ -307,6 +308,27 @@ int dv_augment_ingest(int32_t dtype, const uint8_t* frames, int32_t n_src, int32
                       const dv_aug_frame* table, int32_t N, int32_t T, int32_t H, int32_t W, void* y, int32_t ldy,
                       int32_t pad, const float* mean3, const float* istd3, const int32_t* perm, int32_t n_seg,
                       float* scratch, const dv_aug_blur* blur, uint8_t* blur_scratch, void* stream);
+/* Block-wise colour jitter (utils/augmentation.py:429-661, ColorJitter(block=nb, grad_consistent=...), __call__ :587-652): the
+ * H x W output frame (post-crop, post-resize, post-flip coordinates) is cut into an nb x nb grid of patches of H / nb x W / nb
+ * pixels, the last row / column of patches taking the remainder; pixel (h, w) belongs to patch
+ * (min(h / (H / nb), nb - 1), min(w / (W / nb), nb - 1)).  Every patch runs its own op list (`dv_aug_patch`: the op / factor
+ * fields of `dv_aug_frame`, same codes, same arithmetic), and its contrast op blends against the mean luma OF THE PATCH (the
+ * reference's F.adjust_contrast on the patch slice).  The time-graded mode (grad_consistent, :512-551) needs nothing more:
+ * its per-frame factors are np.linspace rows the host writes into each frame's patch lists. */
+typedef struct dv_aug_patch {
+  int32_t op[DV_AUG_MAX_OPS];      /* DV_AUG_*, applied in this order; unknown codes do nothing */
+  float factor[DV_AUG_MAX_OPS];    /* as dv_aug_frame.factor */
+} dv_aug_patch;                    /* 40 bytes per entry */
+/* dv_augment_ingest with patches: `table` rows give source and geometry only (their op lists are not read); `patches` holds
+ * n_block^2 entries per table row, row-major patch order, parallel to `table` (the segment shuffle `perm` moves a frame's patches
+ * with its row).  scratch: N*T*n_block^2 floats (one contrast mean per frame and patch).  DV_EINVAL for n_block < 1,
+ * n_block > 8, n_block > min(H, W), or patches == NULL with n_block > 1; patches == NULL with n_block == 1 is dv_augment_ingest.
+ * Launches as dv_augment_ingest, the contrast prepass with one workgroup per (frame, patch). */
+int dv_augment_ingest_blocks(int32_t dtype, const uint8_t* frames, int32_t n_src, int32_t Hs, int32_t Ws,
+                             const dv_aug_frame* table, int32_t N, int32_t T, int32_t H, int32_t W, void* y, int32_t ldy,
+                             int32_t pad, const float* mean3, const float* istd3, const int32_t* perm, int32_t n_seg,
+                             float* scratch, const dv_aug_blur* blur, uint8_t* blur_scratch, const dv_aug_patch* patches,
+                             int32_t n_block, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * BatchNorm3d, training mode (nn.BatchNorm3d at s3dg.py:16,46-47, r21d.py:56,99,106,111,228, ...;

@@ -115,7 +115,10 @@ def parse_args(argv=None):
     p.add_argument('--steps', default=0, type=int, help='stop every epoch after this many iterations (0 = whole epoch)')
     p.add_argument('--epoch_size', default=1024, type=int, help='synthetic samples per epoch (whole job)')
     p.add_argument('--warm_steps', default=20, type=int, help='steps excluded from the steady-state clips/s of an epoch')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.aug_temp_consist and args.aug_temp_grad_consist:       # utils/augmentation.py:452 asserts the same
+        p.error('--aug_temp_consist and --aug_temp_grad_consist are mutually exclusive')
+    return args
 
 
 class SyntheticClips(torch.utils.data.Dataset):
@@ -144,6 +147,8 @@ class SyntheticFrames(torch.utils.data.Dataset):
 
     def __init__(self, args, length, transform=None, views=1, pool=64):
         self.shape, self.length, self.seed = (args.seq_len, 128, 171, 3), length, args.seed
+        # block-wise / time-graded colour jitter (gpu_transform): every sample also ships `patch` rows on an n_block grid
+        self.n_block = args.n_block if block_jitter(args) else None
         rs = np.random.RandomState(args.seed)
         self.pool = torch.from_numpy(rs.randint(0, 256, (min(length, pool),) + self.shape, dtype=np.uint8))
         self.transform, self.views, self.size = transform, views, (args.img_dim, args.img_dim)
@@ -156,18 +161,23 @@ class SyntheticFrames(torch.utils.data.Dataset):
         if self.transform is not None:
             from dualvar_amd.utils.transforms import ClipState
             L, Hs, Ws = self.shape[:3]
-            rows, blurs = [], []
+            rows, blurs, patches = [], [], []
             for _ in range(self.views):
                 st = self.transform(ClipState(range(L), Hs, Ws))
                 rows.append(st.rows(*self.size))
                 blurs.append(st.blur_rows())
+                if self.n_block is not None:
+                    patches.append(st.patch_rows(*self.size, block=self.n_block))
             out['aug'] = torch.from_numpy(np.concatenate(rows).view(np.uint8).copy())
             out['blur'] = torch.from_numpy(np.concatenate(blurs).view(np.uint8).copy())
+            if patches:
+                out['patch'] = torch.from_numpy(np.concatenate(patches).view(np.uint8).copy())       # AUG_PATCH rows
         return out
 
 
 def collate_frames(samples):
-    """default collate + the source-frame indices of sample b's augmentation rows moved to its place in the batch (b * L)"""
+    """default collate + the source-frame indices of sample b's augmentation rows moved to its place in the batch (b * L); the
+    `patch` rows (block-wise colour jitter) hold op lists only, so the default collate's stacking is all they need"""
     batch = torch.utils.data.default_collate(samples)
     if 'aug' in batch:
         B, L = batch['frames'].shape[:2]
@@ -218,16 +228,27 @@ class DevicePrefetcher:
             yield batch
 
 
+def block_jitter(args):
+    """--n_block > 1 / --aug_temp_grad_consist: the block-wise or time-graded colour jitter (per-patch op lists)"""
+    return args.n_block > 1 or args.aug_temp_grad_consist
+
+
 def gpu_transform(args):
     """the base transform of pretrain.py:500-509 in its tensor-side form (utils/transforms.py): random crop, optional
     flip, colour jitter 0.8 / 0.8 / 0.8 / hue 0.2 with p = 0.8 (temporally consistent under --aug_temp_consist; hue by
     utils/augmentation.py:adjust_hue_np's arithmetic); then, with p = 0.5, the SimCLR Gaussian blur (sigma in [0.1, 2], one
-    per clip) exactly as PIL computes it (utils/augmentation.py:706-721)"""
+    per clip) exactly as PIL computes it (utils/augmentation.py:706-721).  Under --n_block > 1 or --aug_temp_grad_consist the
+    jitter is the reference's own structure, RandomApply([ColorJitter(..., p=0.8, block=n_block, grad_consistent=...)], p=0.8)
+    (pretrain.py:504-506): an n_block x n_block grid of patches, each with its own (gated, or time-graded) jitter."""
     from dualvar_amd.utils import transforms as T
     steps = [T.RandomCrop((args.img_dim, args.img_dim))]
     if args.rand_flip:
         steps.append(T.RandomHorizontalFlip())
-    steps.append(T.ColorJitter(0.8, 0.8, 0.8, consistent=args.aug_temp_consist, p=0.8 * 0.8, hue=0.2))
+    if block_jitter(args):
+        steps.append(T.RandomApply([T.ColorJitter(0.8, 0.8, 0.8, hue=0.2, p=0.8, consistent=args.aug_temp_consist, block=args.n_block,
+                                                  seq_len=args.seq_len, grad_consistent=args.aug_temp_grad_consist)], p=0.8))
+    else:
+        steps.append(T.ColorJitter(0.8, 0.8, 0.8, consistent=args.aug_temp_consist, p=0.8 * 0.8, hue=0.2))
     steps.append(T.RandomApply([T.GaussianBlur([.1, 2.], seq_len=args.seq_len)], p=0.5))
     return T.Compose(steps)
 
@@ -291,6 +312,8 @@ def main_worker(gpu, ngpus_per_node, args):
         args.gpu_transform = gpu_transform(args)
         dataset = SyntheticFrames(args, n_samples, transform=args.gpu_transform, views=args.num_seq * args.n_proto)
     else:
+        if block_jitter(args):
+            print('--n_block / --aug_temp_grad_consist take effect only on --dataset synthetic-frames: float clips are not augmented')
         dataset = SyntheticClips(args, n_samples)
     sampler = torch.utils.data.distributed.DistributedSampler(dataset, shuffle=True) if args.distributed else None
     nw = min(args.workers, 4)
@@ -413,7 +436,9 @@ def train_one_epoch(data_loader, model, optimizer, scheduler, transforms_cuda, e
                 shape = (fr.size(0), nv, 3, args.seq_len, args.img_dim, args.img_dim) if nv > 1 else \
                         (fr.size(0), 3, args.seq_len, args.img_dim, args.img_dim)
                 input_seq = FrameBatch(fr.view(-1, *fr.shape[2:]), batch['aug'].cuda(args.gpu).view(-1), shape,
-                                       blur=batch['blur'].cuda(args.gpu).view(-1) if batch.get('has_blur', True) else None)
+                                       blur=batch['blur'].cuda(args.gpu).view(-1) if batch.get('has_blur', True) else None,
+                                       patches=batch['patch'].cuda(args.gpu).view(-1) if 'patch' in batch else None,
+                                       n_block=args.n_block)
             else:
                 L_ = fr.size(1)
                 input_seq = FrameBatch.build(fr.view(-1, *fr.shape[2:]), [list(range(b * L_, b * L_ + args.seq_len)) for b in range(fr.size(0))],
