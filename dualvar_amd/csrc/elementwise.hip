@@ -579,7 +579,8 @@ __device__ __forceinline__ void bn_bwd_apply_body(const T* __restrict__ dy, int 
       const float act = fromx ? xx[e] * sc[e] + sh[e] : yy[e];     // the forward's expression: same mask bit for bit
       const float gg = (mask && !(act > 0.f)) ? 0.f : g[e];
       o[e] = k1[e] * gg + k2[e] * xx[e] + k3[e];
-      if (dres) ro[e] = (flags & DV_ACCUM) ? ro[e] + gg : gg;
+      // (pad lanes [C, CP) of dres are written as zeros, whatever dy / y / dres held there, as dx's are through k1..k3 = 0)
+      if (dres) ro[e] = c0 + e >= C ? 0.f : (flags & DV_ACCUM) ? ro[e] + gg : gg;
     }
     Pack16<T>::store(dx + (size_t)row * lddx + c0, o);
     if (dres) Pack16<T>::store(dres + (size_t)row * lddres + c0, ro);
@@ -1720,6 +1721,8 @@ extern "C" int dv_bn_bwd_reduce(int32_t dtype, const void* dy, int32_t lddy, con
                                 float* sums, int32_t n_rep, float* ws, void* stream) {
   const int CP = cp8(C);
   const bool mask = !(flags & DV_NO_RELU_MASK);
+  // DV_MASK_FROM_X needs the affine map (scale / shift) that only the multi-tensor item carries
+  if (mask && (flags & DV_MASK_FROM_X)) return DV_EINVAL;
   if (!dy || !x || (mask && !y) || !mean || !invstd || !sums || M <= 0 || C <= 0 || n_rep <= 0) return DV_EINVAL;
   if (ws && (reinterpret_cast<uintptr_t>(ws) & 3)) return DV_EALIGN;
   if (lddy < CP || ldx < CP || (mask && ldy < CP)) return DV_EINVAL;
@@ -1747,6 +1750,7 @@ extern "C" int dv_bn_bwd_apply(int32_t dtype, const void* dy, int32_t lddy, cons
                                int32_t lddres, int64_t M, int32_t C, int32_t flags, void* stream) {
   const int CP = cp8(C);
   const bool mask = !(flags & DV_NO_RELU_MASK);
+  if (mask && (flags & DV_MASK_FROM_X)) return DV_EINVAL;          // (as dv_bn_bwd_reduce: multi-tensor form only)
   if (!dy || !x || (mask && !y) || !mean || !invstd || !gamma || !sums_global || !dx || M <= 0 || C <= 0) return DV_EINVAL;
   if ((dgamma == nullptr) != (dbeta == nullptr) || rep_global <= 0) return DV_EINVAL;
   if (lddy < CP || ldx < CP || lddx < CP || (mask && ldy < CP) || (dres && lddres < CP)) return DV_EINVAL;

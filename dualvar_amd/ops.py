@@ -46,7 +46,7 @@ class Act:
         return self.buf.data_ptr() + self.off * ESIZE[self.dtype]
 
     def slice(self, off, C_):
-        assert off % 8 == 0 and off + cp8(C_) <= self.ld - self.off or off + C_ <= self.C
+        assert off % 8 == 0 and (off + cp8(C_) <= self.ld - self.off or off + C_ <= self.C)
         return Act(self.buf, self.N, self.T, self.H, self.W, C_, self.ld, self.off + off, self.dtype)
 
     def like(self, device=None):

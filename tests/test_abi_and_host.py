@@ -489,3 +489,94 @@ def test_kernel_choice_queries_on_the_host():
     r, c = C.c_int32(), C.c_int32()
     assert lib.dv_conv3d_tile_shape(C.byref(desc(128, 4, 28, 28, 64, 192, (1, 3, 3))), 0, C.byref(r), C.byref(c)) == 0
     assert (r.value, c.value) == (256, 64)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='a library without the check would launch: CPU-only hosts only')
+def test_single_tensor_bn_backward_refuses_mask_from_x():
+    """DV_MASK_FROM_X needs the item's scale / shift: only the multi-tensor entries carry them.  The single-tensor entries
+    must refuse the flag (their kernels would read scale / shift through null pointers, and the apply kernel's LDS table
+    has no room for them).  Every other argument is valid, so the flag is the only reason to refuse."""
+    from dualvar_amd import _lib as L
+    lib = L.load()
+    M, C_ = 64, 16
+    p = 1 << 20                                  # any non-null, 16-byte aligned value: nothing may be dereferenced
+    for fl in (L.DV_MASK_FROM_X, L.DV_MASK_FROM_X | L.DV_ACCUM):
+        assert lib.dv_bn_bwd_reduce(L.DV_F32, p, C_, p, C_, p, C_, p, p, M, C_, fl, p, 1, p, None) == -1
+        assert lib.dv_bn_bwd_apply(L.DV_BF16, p, C_, p, C_, p, C_, p, p, p, p, 1, 1.0 / M, 1.0, p, p, p, C_, p, C_,
+                                   M, C_, fl, None) == -1
+    # with DV_NO_RELU_MASK there is no mask to take from x: the flag is ignored, as in the multi-tensor kernels (not called
+    # here: it would launch)
+
+
+def _header_structs():
+    """{name: [field, ...]} of every `typedef struct` in include/dualvar_hip.h, in declaration order"""
+    src = open(os.path.join(ROOT, 'include', 'dualvar_hip.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    out = {}
+    for m in re.finditer(r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;', src, flags=re.S):
+        assert m.group(1) == m.group(3), m.group(0)
+        fields = []
+        for decl in m.group(2).split(';'):
+            decl = re.sub(r'\[[^\]]*\]', '', decl.replace('*', ' ')).strip()
+            if not decl:
+                continue
+            head, *rest = [d.strip() for d in decl.split(',')]
+            fields += [head.split()[-1]] + rest
+        out[m.group(1)] = fields
+    return out
+
+
+def test_ctypes_and_numpy_struct_mirrors_match_the_header(tmp_path):
+    """The host builds the structs of include/dualvar_hip.h by hand (ctypes in dualvar_amd/_lib.py, numpy row dtypes for the
+    ingest tables in dualvar_amd/utils/transforms.py).  A C probe compiled against the header prints sizeof and offsetof of
+    every field; the mirrors must agree field by field, and every struct of the header must have a mirror."""
+    import ctypes
+    import shutil
+    from dualvar_amd import _lib as L
+    from dualvar_amd.utils import transforms as TR
+    mirrors = {'dv_conv_desc': L.ConvDesc, 'dv_bn_reduce': L.BnReduce, 'dv_bn_bwd': L.BnBwd, 'dv_bn_in': L.BnIn,
+               'dv_w3_desc': L.W3Desc, 'dv_pack_desc': L.PackDesc, 'dv_aug_frame': TR.AUG_ROW, 'dv_aug_blur': TR.AUG_BLUR,
+               'dv_aug_patch': TR.AUG_PATCH, 'dv_bn_item': L.BnItem, 'dv_pool_desc': L.PoolDesc, 'dv_gemm_desc': L.GemmDesc}
+    structs = _header_structs()
+    assert set(structs) == set(mirrors)
+    cc = shutil.which('cc') or shutil.which('gcc') or shutil.which('clang')
+    assert cc, 'no host C compiler'
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "dualvar_hip.h"', 'int main(void) {']
+    for s, fields in structs.items():
+        lines.append(f'  printf("{s} %zu\\n", sizeof({s}));')
+        lines += [f'  printf("{s}.{f} %zu\\n", offsetof({s}, {f}));' for f in fields]
+    lines += ['  return 0;', '}']
+    (tmp_path / 'probe.c').write_text('\n'.join(lines) + '\n')
+    exe = str(tmp_path / 'probe')
+    subprocess.run([cc, '-std=c11', '-I', os.path.join(ROOT, 'include'), str(tmp_path / 'probe.c'), '-o', exe], check=True)
+    got = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = {k: int(v) for k, v in got.items()}
+    for s, fields in structs.items():
+        m = mirrors[s]
+        if isinstance(m, np.dtype):
+            names, size = list(m.names), m.itemsize
+            offs = {f: m.fields[f][1] for f in names}
+        else:
+            names, size = [f[0] for f in m._fields_], ctypes.sizeof(m)
+            offs = {f: getattr(m, f).offset for f in names}
+        assert names == fields, (s, names, fields)
+        assert size == got[s], (s, size, got[s])
+        for f in fields:
+            assert offs[f] == got[f'{s}.{f}'], (s, f, offs[f], got[f'{s}.{f}'])
+    assert got['dv_bn_item'] == 256 and got['dv_aug_frame'] == 64 and got['dv_aug_patch'] == 40
+
+
+def test_act_slice_refuses_misaligned_channel_offsets():
+    """the multi-tensor BatchNorm and conv kernels load 16 bytes at the view's first channel: a slice must start at a multiple
+    of 8 channels even when it fits inside the parent's C"""
+    from dualvar_amd import ops
+    a = ops.Act(torch.zeros(4, 48), 1, 1, 2, 2, 40, 48, 0, ops.DV_F32)
+    s = a.slice(8, 24)
+    assert (s.off, s.C, s.ld) == (8, 24, 48)
+    assert a.slice(16, 32).off == 16                  # up to the end of the pitch
+    with pytest.raises(AssertionError):
+        a.slice(4, 8)                                 # inside C, misaligned
+    with pytest.raises(AssertionError):
+        a.slice(12, 24)
+    with pytest.raises(AssertionError):
+        a.slice(24, 32)                               # aligned, but runs past the pitch and past C
