@@ -190,6 +190,22 @@ class RandomCrop(object):
         return st
 
 
+class PILRandomCrop(object):
+    """utils/augmentation.py:149-175, the PIL-pipeline RandomCrop(size) of pretrain.py:493-508: it reads `img.size`, which PIL gives
+    as (width, height), into (h, w), so it draws the LEFT edge first, random.randint(0, width - size[0]), then the top edge,
+    random.randint(0, height - size[1]) -- always two draws, even when the window already has the requested size"""
+
+    def __init__(self, size):
+        self.size = (size, size) if isinstance(size, int) else tuple(size)
+
+    def __call__(self, st):
+        h, w = st.size()
+        left = random.randint(0, w - self.size[0])
+        top = random.randint(0, h - self.size[1])
+        st.crop(top, left, self.size[1], self.size[0])
+        return st
+
+
 class RandomSizedCrop(object):
     """transforms.py:221-247: up to ten (area fraction in [0.5, 1], aspect in [3/4, 4/3]) proposals -- two uniform draws
     each, then the corner -- and a plain random crop of the output size when none fits; resized to `size`"""
@@ -278,10 +294,12 @@ class ColorJitter(object):                                  # transforms.py:313-
       * time-graded: every seq_len-th frame draws, per patch, get_grad_consistent_factors (:512-525: a start and an end per op)
         and a random.shuffle of [0, 1, 2, 3]; frame t runs all four ops with np.linspace(start, end, seq_len)[t], in that
         order (get_params_fixed, :528-551).  The gate p is not used.
-    With block == 1 and grad_consistent False (the default) nothing of this applies: the tensor-side draws above."""
+    With block == 1 and grad_consistent False (the default) nothing of this applies: the tensor-side draws above -- unless
+    `patched`: the reference's PIL-pipeline class draws per frame (and per patch) even at block == 1, and with patched=True this
+    class does too (one-patch op lists; the --dataset *-2clip-stage-prototype path, dualvar_amd/utils/frame_dataset.py)."""
 
     def __init__(self, brightness=0, contrast=0, saturation=0, consistent=False, p=1.0, n_channel=1, gray_channel=0, hue=0,
-                 block=1, seq_len=16, grad_consistent=False, n_seqblock=0):
+                 block=1, seq_len=16, grad_consistent=False, n_seqblock=0, patched=False):
         self.brightness = self._check_input(brightness, 'brightness')
         self.contrast = self._check_input(contrast, 'contrast')
         self.saturation = self._check_input(saturation, 'saturation')
@@ -296,7 +314,7 @@ class ColorJitter(object):                                  # transforms.py:313-
         self.n_seqblock = n_seqblock if n_seqblock != 0 else seq_len
         if seq_len < 1 or seq_len % self.n_seqblock:        # :459
             raise ValueError('seq_len (%d) must be a positive multiple of n_seqblock (%d)' % (seq_len, self.n_seqblock))
-        self.block, self.seq_len, self.grad_consistent = block, seq_len, grad_consistent
+        self.block, self.seq_len, self.grad_consistent, self.patched = block, seq_len, grad_consistent, patched
 
     @staticmethod
     def _check_input(value, name, center=1, bound=(0, float('inf'))):
@@ -356,7 +374,7 @@ class ColorJitter(object):                                  # transforms.py:313-
         return st
 
     def __call__(self, st):
-        if self.block > 1 or self.grad_consistent:
+        if self.block > 1 or self.grad_consistent or self.patched:
             return self._patched(st)
         if random.random() < self.p:
             todo = []                                       # get_params: the list is shuffled BEFORE any factor is drawn
@@ -407,6 +425,30 @@ class RandomApply(object):
         for t in self.transforms:
             st = t(st)
         return st
+
+
+class MultiRandomizedTransform(object):
+    """utils/augmentation.py:782-810: clip i of a sample draws np.random.uniform() and runs the first transform whose cumulative
+    weight (row i of `weights`) exceeds the draw; here each clip is a ClipState and the call maps a list of them"""
+
+    def __init__(self, transforms, weights):
+        self.transforms = list(transforms)
+        self.weights = [np.cumsum(w) for w in weights]
+        if any(w[-1] != 1. for w in self.weights):
+            raise ValueError('every row of weights must sum to 1')
+
+    def __call__(self, states):
+        if len(states) != len(self.weights):
+            raise ValueError('%d clips, but the transform is defined for %d (one row of weights per clip)' % (
+                len(states), len(self.weights)))
+        out = []
+        for st, w in zip(states, self.weights):
+            rand_p = np.random.uniform()
+            k = 0
+            while rand_p >= w[k]:
+                k += 1
+            out.append(self.transforms[k](st))
+        return out
 
 
 class Compose(object):

@@ -36,8 +36,8 @@ extern "C" {
    built with and a consumer must refuse a library whose value differs from the header it was compiled against.
    2: dv_conv3d_wgrad (workspace, workspace_bytes), dv_bn_bwd_reduce (ws), dv_infonce_fwd (workspace, bytes),
       dv_augment_ingest (blur, blur_scratch) gained arguments; dv_bn_item grew by red_ws (round 2 of this build).
-   (dv_conv3d_ksplit_cols, dv_conv3d_wgrad_bn, dv_conv3d_wgrad_bn_ok, dv_augment_ingest_blocks / dv_aug_patch were ADDED under
-   version 2: additions do not bump it.) */
+   (dv_conv3d_ksplit_cols, dv_conv3d_wgrad_bn, dv_conv3d_wgrad_bn_ok, dv_augment_ingest_blocks / dv_aug_patch,
+   dv_resample_u8 / dv_resample_desc were ADDED under version 2: additions do not bump it.) */
 #define DV_ABI_VERSION 2
 
 enum { DV_F32 = 0, DV_BF16 = 1 };
@@ -329,6 +329,35 @@ int dv_augment_ingest_blocks(int32_t dtype, const uint8_t* frames, int32_t n_src
                              int32_t pad, const float* mean3, const float* istd3, const int32_t* perm, int32_t n_seg,
                              float* scratch, const dv_aug_blur* blur, uint8_t* blur_scratch, const dv_aug_patch* patches,
                              int32_t n_block, void* stream);
+
+/* PIL-exact resample of decoded uint8 RGB frames: the reference's A.Scale((128, 171)) = PIL Image.resize((W, H), BICUBIC)
+ * (utils/augmentation.py:125-146), in Pillow's own integer arithmetic (src/libImaging/Resample.c): per output column (row) a
+ * table entry {xmin, n, w[ksize]} of 22-bit fixed-point weights computed on the host in float64 (dualvar_amd/utils/resample.py);
+ * out = clamp((2^21 + sum_k w[k] * in[xmin + k]) >> 22, 0, 255), the horizontal pass first (its result clamped to uint8), then the
+ * vertical one; a pass whose size does not change is skipped.  Integer only: bit-exact with PIL, whatever the filter the tables
+ * were built for.
+ * One batch of frames of different sizes (ragged) in ONE launch: `src` packs every source frame [Hs][Ws][3] at a 16-byte aligned
+ * offset; one descriptor per output frame; every output frame is Ho x Wo.
+ * `coef` holds coefficient tables, each at an int32 offset t: {in, out, ksize, 0}, then `out` entries of 2 + ksize words
+ * {xmin, n, w[0 .. ksize)}.  A descriptor's h_coef must name a table with in == Ws, out == Wo (v_coef: in == Hs, out == Ho), or be
+ * -1 when that size does not change (Pillow's skip rule). */
+#define DV_RESAMPLE_MAX_KSIZE 32   /* taps per table entry: bicubic downscales up to 7.75x, bilinear up to 15.5x */
+struct dv_resample_desc {
+  int64_t src_offset;              /* byte offset of the frame's [Hs][Ws][3] pixels in `src`; a multiple of 16 */
+  int32_t Hs, Ws;                  /* its size */
+  int32_t h_coef, v_coef;          /* int32 offsets of its horizontal / vertical tables in `coef`; -1: pass skipped */
+};                                 /* 24 bytes; numpy mirror dualvar_amd/utils/resample.py: DESC */
+/* src: src_bytes long (each frame's bytes rounded up to 16 must lie inside it); desc / coef: the device copies the kernel reads,
+ * host_desc / host_coef the SAME tables in host memory, which the entry validates before it launches; out:
+ * [N][Ho][Wo][3].  DV_EINVAL for sizes <= 0, a table whose in / out do not match the descriptor, a ksize outside
+ * [1, DV_RESAMPLE_MAX_KSIZE], an entry with n outside [1, ksize] or xmin + n outside [0, in], a frame outside `src`, or a band
+ * whose staged rows do not fit 64 KB of LDS; DV_EALIGN for a misaligned src or src_offset.  One workgroup per (frame, band of
+ * 32 output rows): the horizontal pass over the source rows the band's vertical taps reach, staged through LDS with 16-byte
+ * loads, then the vertical pass from LDS. */
+int dv_resample_u8(const uint8_t* src, int64_t src_bytes, const struct dv_resample_desc* desc,
+                   const struct dv_resample_desc* host_desc,
+                   int32_t N, const int32_t* coef, const int32_t* host_coef, int64_t coef_words, uint8_t* out, int32_t Ho,
+                   int32_t Wo, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * BatchNorm3d, training mode (nn.BatchNorm3d at s3dg.py:16,46-47, r21d.py:56,99,106,111,228, ...;

@@ -11,6 +11,8 @@ What differs, deliberately:
     PIL augmentations are the CPU data pipeline, out of scope -- SURVEY.md 2.1 rows 13-14); `--dataset
     synthetic-frames` feeds decoded uint8 128x171 frames and augments them ON THE GPU inside the ingest kernel
     (crop / flip / colour jitter / grayscale of utils/transforms.py, dualvar_amd.utils.transforms.FrameBatch);
+    `--dataset {ucf101,k400}-2clip-stage-prototype` reads the reference's extracted JPEG frames: decoded in the DataLoader
+    workers, scaled PIL-exactly (dv_resample_u8) and augmented on the GPU (dualvar_amd/utils/frame_dataset.py);
   * Normalize (utils/transforms.py) is fused into the ingest kernel instead of a separate GPU pass;
   * SyncBatchNorm / DDP are the engine's own collectives (dualvar_amd/parallel.py), not module wrappers;
   * accuracy meters read the positive's rank emitted by the loss kernels (no topk launch, no extra sync):
@@ -33,6 +35,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from dualvar_amd.model import MoCo_Naked, MoCo_TimeSeriesV4, SimCLR_Naked, SimCLR_TimeSeriesV4  # noqa: E402
+from dualvar_amd.utils.frame_dataset import DATASETS as FRAME_DATASETS  # noqa: E402
 from dualvar_amd.utils.utils import AverageMeter, ProgressMeter, neq_load_customized, save_checkpoint  # noqa: E402
 
 MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
@@ -80,6 +83,10 @@ def parse_args(argv=None):
     p.add_argument('--aug_temp_consist', action='store_true')
     p.add_argument('--aug_series', action='store_true')
     p.add_argument('--rand_flip', action='store_true')
+    p.add_argument('--split_root', default=None, type=str,
+                   help='*-2clip-stage-prototype: ClassInd.txt and {train,test}_split01.csv (default: the reference\'s path)')
+    p.add_argument('--frame_root', default=None, type=str,
+                   help='*-2clip-stage-prototype: <class>/<video>/image_%%05d.jpg (default: the reference\'s path)')
     # optimizer
     p.add_argument('--optim', default='sgd', type=str)
     p.add_argument('--batch_size', default=32, type=int)
@@ -118,6 +125,15 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.aug_temp_consist and args.aug_temp_grad_consist:       # utils/augmentation.py:452 asserts the same
         p.error('--aug_temp_consist and --aug_temp_grad_consist are mutually exclusive')
+    if args.dataset in FRAME_DATASETS:
+        # MultiRandomizedTransform (utils/augmentation.py:782-810) asserts one weight row per clip: 3 rows, 3 clips
+        if not args.aug_series or args.num_seq * args.n_proto != 3:
+            p.error('--dataset %s needs --aug_series and num_seq * n_proto == 3 (got --num_seq %d, --n_proto %d%s): its transform '
+                    'is defined for exactly three clips' % (args.dataset, args.num_seq, args.n_proto,
+                                                           '' if args.aug_series else ', no --aug_series'))
+        split_root, frame_root = FRAME_DATASETS[args.dataset]
+        args.split_root = args.split_root or os.path.join(ROOT, split_root)
+        args.frame_root = args.frame_root or os.path.join(ROOT, frame_root)
     return args
 
 
@@ -307,19 +323,33 @@ def main_worker(gpu, ngpus_per_node, args):
 
     per_rank = max(args.epoch_size // max(args.world_size, 1), args.batch_size)
     n_samples = per_rank * max(args.world_size, 1)
+    frame_clips = args.dataset in FRAME_DATASETS
     if args.dataset == 'synthetic-frames':
         # every view's augmentation is drawn in the DataLoader workers and applied on the GPU by the ingest kernel
         args.gpu_transform = gpu_transform(args)
         dataset = SyntheticFrames(args, n_samples, transform=args.gpu_transform, views=args.num_seq * args.n_proto)
+    elif frame_clips:
+        # extracted JPEG frames: decoded in the workers, scaled (PIL-exact) and augmented on the GPU
+        from dualvar_amd.utils import frame_dataset as FD
+        transform = FD.stage_prototype_transform(args.img_dim, args.seq_len, consistent=args.aug_temp_consist, n_block=args.n_block,
+                                                 grad_consistent=args.aug_temp_grad_consist)
+        dataset = FD.StagePrototypeFrames(args.split_root, args.frame_root, mode='train', num_frames=args.seq_len, ds=args.ds,
+                                          rand_flip=args.rand_flip, aug_series=args.aug_series, transform=transform,
+                                          img_dim=args.img_dim, n_block=args.n_block)
+        args.logger.info('"train" dataset %s: %d videos, %d classes' % (args.dataset, len(dataset), len(dataset.classes)))
     else:
         if block_jitter(args):
             print('--n_block / --aug_temp_grad_consist take effect only on --dataset synthetic-frames: float clips are not augmented')
         dataset = SyntheticClips(args, n_samples)
     sampler = torch.utils.data.distributed.DistributedSampler(dataset, shuffle=True) if args.distributed else None
-    nw = min(args.workers, 4)
+    nw = min(args.workers, 16 if frame_clips else 4)          # real frames are bound by JPEG decoding in the workers
+    if frame_clips:
+        from dualvar_amd.utils.frame_dataset import collate_frame_clips as collate
+    else:
+        collate = collate_frames if args.dataset == 'synthetic-frames' else None
     loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
                                          num_workers=nw, pin_memory=True, drop_last=True, worker_init_fn=seed_worker,
-                                         collate_fn=collate_frames if args.dataset == 'synthetic-frames' else None,
+                                         collate_fn=collate,
                                          persistent_workers=nw > 0, prefetch_factor=4 if nw > 0 else None)
     loader = DevicePrefetcher(loader, args.gpu)
 
@@ -427,15 +457,21 @@ def train_one_epoch(data_loader, model, optimizer, scheduler, transforms_cuda, e
 
     for idx, batch in enumerate(data_loader):
         data_time.update(time.time() - end)
-        if 'frames' in batch:        # decoded frames: every view is augmented inside the ingest kernel
+        if 'frames' in batch or 'src' in batch:        # decoded frames: every view is augmented inside the ingest kernel
             from dualvar_amd.utils.transforms import FrameBatch
-            fr = batch['frames']                                                         # [B, L, Hs, Ws, 3] uint8, on the GPU
-            if not fr.is_cuda:
-                fr = fr.cuda(args.gpu, non_blocking=True)
-            if 'aug' in batch:       # rows drawn by the DataLoader workers (SyntheticFrames with a transform)
-                shape = (fr.size(0), nv, 3, args.seq_len, args.img_dim, args.img_dim) if nv > 1 else \
-                        (fr.size(0), 3, args.seq_len, args.img_dim, args.img_dim)
-                input_seq = FrameBatch(fr.view(-1, *fr.shape[2:]), batch['aug'].cuda(args.gpu).view(-1), shape,
+            if 'src' in batch:       # frames of their stored sizes (StagePrototypeFrames): PIL's Scale on the GPU first
+                from dualvar_amd.utils.frame_dataset import scale_batch
+                fr = scale_batch(batch)                                                  # [n, 171, 128, 3] uint8
+                B_ = batch['aug'].size(0)
+            else:
+                fr = batch['frames']                                                     # [B, L, Hs, Ws, 3] uint8, on the GPU
+                if not fr.is_cuda:
+                    fr = fr.cuda(args.gpu, non_blocking=True)
+                B_ = fr.size(0)
+            if 'aug' in batch:       # rows drawn by the DataLoader workers (SyntheticFrames with a transform, StagePrototypeFrames)
+                shape = (B_, nv, 3, args.seq_len, args.img_dim, args.img_dim) if nv > 1 else \
+                        (B_, 3, args.seq_len, args.img_dim, args.img_dim)
+                input_seq = FrameBatch(fr.view(-1, *fr.shape[-3:]), batch['aug'].cuda(args.gpu).view(-1), shape,
                                        blur=batch['blur'].cuda(args.gpu).view(-1) if batch.get('has_blur', True) else None,
                                        patches=batch['patch'].cuda(args.gpu).view(-1) if 'patch' in batch else None,
                                        n_block=args.n_block)
