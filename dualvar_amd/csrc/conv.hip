@@ -15,13 +15,14 @@
 // both share the 32x32 C/D layout  col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 #include "conv_common.hpp"
 
-// the LDS-staged input-tile kernels for stride-1 "same" 1x3x3 / 3x1x1 convs (conv_tap.hip); the argument is a ConvArgs*
+// the LDS-staged input-tile kernels for stride-1 "same" 1x3x3 / 3x1x1 convs and their pixel-pair stem form (conv_tap.hip); the
+// argument is a ConvArgs*.  The three predicates answer route_conv's questions; the launches run what it decided.
 int dvt_conv_tap_kind(const void* conv_args, int mode);
-int dvt_conv_tap_rows(const void* conv_args, int mode);
-int dvt_conv_tap_launch(const void* conv_args, int mode, void* stream);
+int dvt_conv_tap_bm(const void* conv_args, int kind);
+int dvt_conv_pp_lines(const void* conv_args, int mode);
+void dvt_conv_tap_launch(const void* conv_args, int mode, int kind, int bm, void* stream);
+void dvt_conv_pp_launch(const void* conv_args, int G, void* stream);
 int64_t dvt_bn_ws_floats(int64_t rows, int np);
-int dvt_conv_pp_rows(const void* conv_args, int mode);
-int dvt_conv_pp_launch(const void* conv_args, int mode, void* stream);
 // dv_conv3d_dgrad_bn's reduce over what a data gradient has written (conv_experiments.hip); the argument is a ConvArgs*
 void dvx_dgrad_bn_tail_launch(const void* conv_args, int is_f32, void* stream);
 
@@ -1480,16 +1481,6 @@ extern "C" int dv_pack_w3(const float* base, void* out_base, const dv_w3_desc* d
   return dv_launch_status();
 }
 
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
-static bool f32_exact() {
-  static const bool v = getenv("DUALVAR_F32_EXACT") && atoi(getenv("DUALVAR_F32_EXACT")) != 0;
-  return v;
-}
-
 static int pick_bn(int np) {
   if (np <= 32) return 32;
   if (np <= 64) return 64;
@@ -1525,11 +1516,19 @@ static void pick_tile(int dtype, int M, int NP, int& bm, int& bn) {
   }
 }
 
+// One conv_gemm_kernel launch as the route decided it: the tile, the gather (gm: 1 uniform tap, 0 generic), the LDS stages, and
+// for fp32 the bf16 split (split), pre-split weights (wf) and BatchNorm on load (bnl).  launch_gemm maps it to a template.
+struct GemmForm {
+  int bm, bn, gvb, gm, ns;
+  bool split, wf, bnl;
+};
+
 template <typename T, int MODE, int GVB, int GM, int NS, bool SPLIT = false, bool WF = false>
-static void launch_gemm_ns(int bm, int bn, const ConvArgs& a, int grid, hipStream_t s) {
+static void launch_gemm_ns(const GemmForm& f, const ConvArgs& a, int grid, hipStream_t s) {
+  const int bm = f.bm, bn = f.bn;
   if constexpr (WF) {       // pre-split weights: the instantiations the fp32 split mode uses
     if constexpr (MODE == MODE_FWD && GM == 1 && NS == 2 && sizeof(T) == 4) {
-      if (a.in_scale != nullptr) {             // BatchNorm on load (fwd_impl has checked: 256 x 64 tile, channel pitch <= 256)
+      if (f.bnl) {             // BatchNorm on load (route_conv has checked: 256 x 64 tile, channel pitch <= 256)
         hipLaunchKernelGGL((conv_gemm_kernel<T, MODE, GVB, 256, 64, 4, 1, GM, NS, true, true, true>), dim3(grid), dim3(256), 0, s, a);
         return;
       }
@@ -1560,65 +1559,76 @@ static void launch_gemm_ns(int bm, int bn, const ConvArgs& a, int grid, hipStrea
   else hipLaunchKernelGGL((conv_gemm_kernel<T, MODE, GVB, 128, 128, 2, 2, GM, NS, SPLIT>), dim3(grid), dim3(256), 0, s, a);
 }
 
-
-
-// Two LDS stages where the grid fills the chip several times over: there three to six stages measured equal or slower
-// (they cost resident workgroups, and the K loop is issue bound).  Launches of at most ~2 workgroups per CU (64-row tiles
-// of the 12 544- and 1 152-row layers) are latency bound instead -- one workgroup per CU waits out every DMA round trip --
-// and get four stages: those layers 252 -> 200 us (1 152 rows) and 581 -> 541 us (12 544 rows) per pass, step 10.53 ->
-// 10.35 ms.  Three stages, and six on the smallest grids, were measured equal or slower.
-template <typename T, int MODE, int GVB, int GM>
-static void launch_gemm_gm(int bm, int bn, const ConvArgs& a, int grid, hipStream_t s) {
-  if constexpr (GVB == 16 && sizeof(T) == 2) {
-    if (bm == 64 && grid <= 512) {
-      launch_gemm_ns<T, MODE, GVB, GM, 4>(bm, bn, a, grid, s);
-      return;
-    }
-  }
+// the form -> the template (sizeof(T) == 1: the fp8 pointwise GEMMs)
+template <typename T, int MODE, int GVB>
+static void launch_gemm(const GemmForm& f, ConvArgs& a, hipStream_t s) {
+  a.ntn = (a.NP + f.bn - 1) / f.bn;
+  const int grid = a.ntn * ((a.M + f.bm - 1) / f.bm);
   if constexpr (sizeof(T) == 4) {
-    if constexpr (GM == 1) {                     // (only the pre-split-weight kernels are built with uniform-tap gathers)
-      // (four or six stages for the small grids, as for bf16, were measured SLOWER here: Mixed_5c 1x3x3 forward 57 -> 68 -> 71 us;
-      // with one workgroup per CU the K step is bound by its own ds_read -> split -> MFMA chain, not by the DMA round trip)
-      launch_gemm_ns<T, MODE, GVB, 1, 2, true, true>(bm, bn, a, grid, s);
-      return;
-    } else {
-      if (!f32_exact()) {
-        if (a.flags & DV_W3) launch_gemm_ns<T, MODE, GVB, 0, 2, true, true>(bm, bn, a, grid, s);
-        else launch_gemm_ns<T, MODE, GVB, 0, 2, true>(bm, bn, a, grid, s);
-        return;
-      }
-    }
+    if (f.wf && f.gm) launch_gemm_ns<T, MODE, GVB, 1, 2, true, true>(f, a, grid, s);
+    else if (f.wf) launch_gemm_ns<T, MODE, GVB, 0, 2, true, true>(f, a, grid, s);
+    else if (f.split) launch_gemm_ns<T, MODE, GVB, 0, 2, true>(f, a, grid, s);
+    else launch_gemm_ns<T, MODE, GVB, 0, 2>(f, a, grid, s);
+  } else if constexpr (GVB == 8) {
+    launch_gemm_ns<T, MODE, GVB, 0, 2>(f, a, grid, s);
+  } else if constexpr (sizeof(T) == 1) {
+    if (f.gm) launch_gemm_ns<T, MODE, GVB, 1, 2>(f, a, grid, s);
+    else launch_gemm_ns<T, MODE, GVB, 0, 2>(f, a, grid, s);
+  } else {
+    if (f.gm && f.ns == 4) launch_gemm_ns<T, MODE, GVB, 1, 4>(f, a, grid, s);
+    else if (f.gm) launch_gemm_ns<T, MODE, GVB, 1, 2>(f, a, grid, s);
+    else if (f.ns == 4) launch_gemm_ns<T, MODE, GVB, 0, 4>(f, a, grid, s);
+    else launch_gemm_ns<T, MODE, GVB, 0, 2>(f, a, grid, s);
   }
-  if constexpr (sizeof(T) != 4 || GM == 0) launch_gemm_ns<T, MODE, GVB, GM, 2>(bm, bn, a, grid, s);
 }
 
-template <typename T, int MODE, int GVB>
-static void launch_gemm(int bm, int bn, const ConvArgs& a, int grid, hipStream_t s) {
-  if constexpr (GVB == 16 && (sizeof(T) == 2 || sizeof(T) == 4)) {
-    // uniform-tap gathers: every K-step (64 bytes: 32 bf16 / 16 f32) inside one tap, tap bit mask in one register.
-    // f32: for the pre-split-weight kernels (the fp32 split mode's hot path; its K loop is bound by vector instructions)
-    constexpr int BKE_ = 64 / (int)sizeof(T);
-    if (a.g.CP % BKE_ == 0 && a.g.kt * a.g.kh * a.g.kw <= 32 && (sizeof(T) == 2 || ((a.flags & DV_W3) && !f32_exact()))) {
-      launch_gemm_gm<T, MODE, GVB, 1>(bm, bn, a, grid, s);
-      return;
-    }
-  }
-  launch_gemm_gm<T, MODE, GVB, 0>(bm, bn, a, grid, s);
+template <int MODE>
+static void launch_gemm_dt(int dtype, const GemmForm& f, ConvArgs& a, hipStream_t s) {
+  if (dtype == DV_F32) launch_gemm<float, MODE, 16>(f, a, s);
+  else if (f.gvb == 16) launch_gemm<bf16_t, MODE, 16>(f, a, s);
+  else if constexpr (MODE == MODE_FWD) launch_gemm<bf16_t, MODE, 8>(f, a, s);       // (8-byte gathers: the padded RGB input)
 }
 
 }  // namespace
+
+// the conv_gemm form for a launch over `a` with tile bm x bn
+static GemmForm gemm_form(int dtype, const ConvArgs& a, int bm, int bn) {
+  GemmForm f{};
+  f.bm = bm; f.bn = bn; f.ns = 2;
+  f.gvb = gather_bytes(dtype, a.g.CP);
+  // uniform-tap gathers: every K-step (64 bytes: 32 bf16 / 16 f32) inside one tap, tap bit mask in one register.
+  // f32: for the pre-split-weight kernels (the fp32 split mode's hot path; its K loop is bound by vector instructions)
+  const int bke = dtype == DV_F32 ? 16 : 32;
+  f.gm = f.gvb == 16 && a.g.CP % bke == 0 && a.g.kt * a.g.kh * a.g.kw <= 32;
+  if (dtype == DV_F32) {
+    f.split = !f32_exact();
+    f.wf = f.split && (a.flags & DV_W3);
+    f.gm = f.gm && f.wf;          // (only the pre-split-weight kernels are built with uniform-tap gathers)
+    f.bnl = f.wf && f.gm && a.in_scale != nullptr;
+    // (four or six stages for the small grids, as for bf16 below, were measured SLOWER here: Mixed_5c 1x3x3 forward 57 -> 68 -> 71
+    // us; with one workgroup per CU the K step is bound by its own ds_read -> split -> MFMA chain, not by the DMA round trip)
+    return f;
+  }
+  // Two LDS stages where the grid fills the chip several times over: there three to six stages measured equal or slower
+  // (they cost resident workgroups, and the K loop is issue bound).  Launches of at most ~2 workgroups per CU (64-row tiles
+  // of the 12 544- and 1 152-row layers) are latency bound instead -- one workgroup per CU waits out every DMA round trip --
+  // and get four stages: those layers 252 -> 200 us (1 152 rows) and 581 -> 541 us (12 544 rows) per pass, step 10.53 ->
+  // 10.35 ms.  Three stages, and six on the smallest grids, were measured equal or slower.
+  const int64_t grid = (int64_t)((a.NP + bn - 1) / bn) * ((a.M + bm - 1) / bm);
+  if (f.gvb == 16 && bm == 64 && grid <= 512) f.ns = 4;
+  return f;
+}
 
 // Taps that fall into the padding for EVERY row of the launch contribute nothing: run the window of the live taps instead
 // (per axis a contiguous range [lo, hi]).  Mixed_5b / 5c of S3D-G at 8-frame clips have ONE frame left: their 3x1x1 convs
 // (padding 1) keep one tap of three -- a third of the K loop.  Weights stay where they are: the kernel addresses a live tap
 // at its original index (ConvArgs::cls_on == 2).  Stride-1 data gradients and forward convs; not for the generic-gather
 // pre-split-weight path (its K tiles straddle taps).
-static void trim_dead_taps(ConvArgs& a, int mode, int dtype) {
+static void trim_dead_taps(ConvArgs& a, int mode) {
   ConvGeom& g = a.g;
   if (a.cls_on || g.kt * g.kh * g.kw <= 1) return;
   if (mode == MODE_DGRAD && (g.st > 1 || g.sh > 1 || g.sw > 1)) return;
   if ((a.flags & DV_W3) && (g.CP % 16 != 0 || g.kt * g.kh * g.kw > 32)) return;
-  (void)dtype;
   auto live = [&](int k, int rdim, int sdim, int stride, int pad, int& lo, int& hi) {
     lo = k; hi = -1;
     for (int d = 0; d < k; ++d) {
@@ -1648,9 +1658,8 @@ static void trim_dead_taps(ConvArgs& a, int mode, int dtype) {
 // conv_gemm_ks_kernel (K split over the waves) takes a fwd / dgrad launch when the ordinary tiling leaves a small grid with a
 // long K loop.  Returns the column tile (32 / 64) or 0.  DUALVAR_CONV_KS=0 switches it off (A/B runs).
 static int ks_tile(int dtype, const ConvArgs& a, int bm) {
-  static const int on = env_int("DUALVAR_CONV_KS", 1);
   constexpr int max_grid = 400, min_nk = 16;       // (a larger grid limit was measured slower: 19.54 -> 20.44 ms at 1024)
-  if (!on || dtype != DV_F32 || !(a.flags & DV_W3) || f32_exact() || a.cls_on == 1 || a.bn_x != nullptr || bm != 64) return 0;
+  if (!conv_ks() || dtype != DV_F32 || !(a.flags & DV_W3) || f32_exact() || a.cls_on == 1 || a.bn_x != nullptr || bm != 64) return 0;
   if (a.g.CP % 16 != 0 || a.g.kt * a.g.kh * a.g.kw > 32 || a.g.Ktot / 16 < min_nk) return 0;
   if (a.g.st > 1 || a.g.sh > 1 || a.g.sw > 1) return 0;       // (few-row layers are stride 1; keeps one gather form)
   const int64_t mt = (a.M + 63) / 64;
@@ -1671,7 +1680,6 @@ static void launch_ks(int bn, ConvArgs& a, hipStream_t s) {
 
 // the parity classes of a strided data gradient (ConvArgs::cls_on == 1): `a` holds the launch-wide fields; -> number of classes
 static int dgrad_classes(const dv_conv_desc* d, const ConvArgs& a, ConvArgs (&out)[8]) {
-  const int taps_orig = d->kt * d->kh * d->kw;
   int n = 0;
   for (int rt = 0; rt < d->st; ++rt)
     for (int rh = 0; rh < d->sh; ++rh)
@@ -1680,7 +1688,7 @@ static int dgrad_classes(const dv_conv_desc* d, const ConvArgs& a, ConvArgs (&ou
         const int ot = first(rt, d->pt, d->st), oh = first(rh, d->ph, d->sh), ow = first(rw, d->pw, d->sw);
         if (ot >= d->Ti || oh >= d->Hi || ow >= d->Wi) continue;
         ConvArgs& c = out[n++];
-        c = a;
+        c = a;                                                  // (ldw stays that of the whole window)
         ConvGeom& g = c.g;
         g.rT = (d->Ti - ot + d->st - 1) / d->st; g.rH = (d->Hi - oh + d->sh - 1) / d->sh; g.rW = (d->Wi - ow + d->sw - 1) / d->sw;
         g.kt = (d->kt - rt + d->st - 1) / d->st; g.kh = (d->kh - rh + d->sh - 1) / d->sh; g.kw = (d->kw - rw + d->sw - 1) / d->sw;
@@ -1689,149 +1697,204 @@ static int dgrad_classes(const dv_conv_desc* d, const ConvArgs& a, ConvArgs (&ou
         g.Ktot = g.kt * g.kh * g.kw * g.CP;
         g.dW = make_fastdiv((uint32_t)g.rW); g.dH = make_fastdiv((uint32_t)g.rH); g.dT = make_fastdiv((uint32_t)g.rT);
         c.M = d->N * g.rT * g.rH * g.rW;
-        if (!(a.flags & DV_W3)) c.ldw = taps_orig * g.CP;       // (pre-split weights: ldw stays their padded row count)
         c.cls_on = 1; c.cst = d->st; c.csh = d->sh; c.csw = d->sw; c.cot = ot; c.coh = oh; c.cow = ow;
         c.crt = rt; c.crh = rh; c.crw = rw; c.oKH = d->kh; c.oKW = d->kw; c.oT = d->Ti; c.oH = d->Hi; c.oW = d->Wi;
       }
   return n;
 }
 
-// the ConvArgs fields the kernel-choice queries look at (no pointers: nothing is launched)
-static void query_args(const dv_conv_desc* d, int dgrad, ConvArgs& a) {
-  fill_geom(d, dgrad ? MODE_DGRAD : MODE_FWD, a.g);
-  a.M = dgrad ? d->N * d->Ti * d->Hi * d->Wi : d->N * d->To * d->Ho * d->Wo;
-  a.N = dgrad ? d->Cin : d->Cout;
-  a.NP = dgrad ? d->cin_pitch : d->cout_pitch;
-  a.ldo = dgrad ? d->ldx : d->ldy;
-  a.flags = d->flags & (dgrad ? (DV_W3 | DV_ACCUM) : (DV_W3 | DV_BIAS | DV_RELU | DV_SIGMOID | DV_STATS));
-  a.cls_on = 0;
-  a.bn_x = nullptr; a.bn_ws = nullptr; a.bn_bytes = 0;
-  const int64_t ob = (((int64_t)a.M - 1) * a.ldo + a.NP) * 4;
+// The ConvArgs of a forward (MODE_FWD) / data gradient (MODE_DGRAD) of `d`, all but the pointers and the fused extras (bias,
+// stats, bn_*, in_*, the fp8 scales), which the entry points set.  fp8: the pointwise fp8 GEMMs (one-byte operands; DV_STATS /
+// DV_ACCUM are their only flags).  DV_EUNSUPPORTED when no kernel takes the problem's extents or its DV_W3; `a` is complete
+// either way (the kernel-choice queries read it too).
+static int conv_args(const dv_conv_desc* d, int mode, ConvArgs& a, bool fp8 = false) {
+  const bool fwd = mode == MODE_FWD;
+  a = ConvArgs();
+  fill_geom(d, mode, a.g);
+  a.M = fwd ? d->N * d->To * d->Ho * d->Wo : d->N * d->Ti * d->Hi * d->Wi;
+  a.N = fwd ? d->Cout : d->Cin;
+  a.NP = fwd ? d->cout_pitch : d->cin_pitch;
+  a.lds_ = fwd ? d->ldx : d->ldy;
+  a.ldo = fwd ? d->ldy : d->ldx;
+  a.flags = d->flags & (fp8 ? (fwd ? DV_STATS : DV_ACCUM) : fwd ? (DV_W3 | DV_BIAS | DV_RELU | DV_SIGMOID | DV_STATS) : (DV_W3 | DV_ACCUM));
+  const bool w3 = (a.flags & DV_W3) != 0;
+  a.ldw = w3 ? w3_rows(a.N) : a.g.Ktot;
+  a.fCP = make_fastdiv((uint32_t)a.g.CP);
+  const int64_t es = fp8 ? 1 : d->dtype == DV_F32 ? 4 : 2;
+  const int64_t src_rows = fwd ? (int64_t)d->N * d->Ti * d->Hi * d->Wi : (int64_t)d->N * d->To * d->Ho * d->Wo;
+  const int64_t sb = (src_rows - 1) * a.lds_ * es + (int64_t)a.g.CP * es;
+  const int64_t wb = w3 ? w3_bytes(a.N, a.g.Ktot) : (int64_t)a.N * a.g.Ktot * es;
+  const int64_t ob = (((int64_t)a.M - 1) * a.ldo + a.NP) * 4;          // fp32 outputs: direct-store epilogue
   a.out_bytes = (d->dtype == DV_F32 && ob < (1ll << 31)) ? (int)ob : 0;
+  const bool fits = sb < (1ll << 31) && wb < (1ll << 31) && d->kt <= 32 && d->kh <= 32 && d->kw <= 32 && d->kt * d->kh * d->kw <= 256;
+  a.src_bytes = fits ? (int)sb : 0;
+  a.w_bytes = fits ? (int)wb : 0;
+  return fits && !(w3 && (d->dtype != DV_F32 || f32_exact())) ? DV_OK : DV_EUNSUPPORTED;
 }
 
-// rows per tile when dv_conv3d_fwd runs this problem on the pixel-pair stem form (conv_tap.hip: conv_pp_fwd_kernel), else 0
-static int pp_rows_choice(const dv_conv_desc* d) {
-  if (d->dtype != DV_F32 || f32_exact() || !(d->flags & DV_W3)) return 0;
-  ConvArgs a;
-  query_args(d, 0, a);
-  a.lds_ = d->ldx;
-  return dvt_conv_pp_rows(&a, MODE_FWD);
-}
+// Which kernel runs a forward / data gradient, with which tile: decided once per call by route_conv and read by the launch
+// (launch_route) and by every kernel-choice query (dv_conv3d_tap_kind ... dv_conv3d_dgrad_bn_workspace), as WgradPlan is for
+// the weight gradient.  In particular `rows` fixes the layout of the BatchNorm partials dv_bn_reduce_stats reads.
+enum {
+  ROUTE_NONE,           // no kernel takes this call: DV_EUNSUPPORTED
+  ROUTE_PP,             // the pixel-pair stem form (conv_tap.hip: conv_pp_fwd_kernel), forward only
+  ROUTE_TAP,            // the LDS-staged input-tile kernel (conv_tap.hip), kind 1 spatial / 2 temporal
+  ROUTE_TAP_CLASSES,    // strided data gradient, pre-split weights: every parity class on the temporal form
+  ROUTE_KS,             // conv_gemm_ks_kernel: K split over the waves
+  ROUTE_GEMM_CLASSES,   // strided data gradient without pre-split weights: conv_gemm per parity class
+  ROUTE_GEMM,           // conv_gemm_kernel
+};
+struct ConvRoute {
+  int path;             // ROUTE_*
+  int kind;             // what dv_conv3d_tap_kind reports: 1 / 2 the LDS-staged kernel's form, 3 the pixel-pair form, else 0
+  int rows;             // rows per tile = rows per BatchNorm partial (ROUTE_PP: lines per tile * Wo)
+  int bm, bn;           // pick_tile over the whole problem (dv_conv3d_tile_shape)
+  int ks_cols;          // ROUTE_KS: the column tile
+  int ncls;             // ROUTE_*_CLASSES: parity classes (dgrad_classes)
+  GemmForm gemm[8];     // ROUTE_GEMM: [0]; ROUTE_GEMM_CLASSES: one per class
+};
 
-// 0: conv_gemm / conv_gemm_ks; 1 / 2: the LDS-staged input-tile kernel (conv_tap.hip), spatial / temporal form; 3: its pixel-pair
-// stem form (forward only)
-static int tap_choice(const dv_conv_desc* d, int dgrad) {
-  if (d->dtype != DV_F32 || f32_exact() || !(d->flags & DV_W3)) return 0;
-  if (!dgrad && pp_rows_choice(d)) return 3;
-  ConvArgs a;
-  query_args(d, dgrad, a);
-  if (d->st > 1 || d->sh > 1 || d->sw > 1) {
-    // a strided data gradient whose parity classes all run on the temporal form (the 7x1x1 / stride-2 stem conv); forward: never
-    if (!dgrad || d->st > 2 || d->sh > 2 || d->sw > 2 || !(d->kt >= d->st && d->kh >= d->sh && d->kw >= d->sw)) return 0;
-    a.ldw = w3_rows(d->Cin);
+// `a`: conv_args plus the call's extras (bn_x / bn_ws of the ordered fused BatchNorm reduce, in_scale of BatchNorm on load).
+// Trims dead taps in `a` where the launch runs the trimmed window.
+static ConvRoute route_conv(const dv_conv_desc* d, int mode, ConvArgs& a) {
+  ConvRoute r{};
+  pick_tile(d->dtype, a.M, a.NP, r.bm, r.bn);
+  r.rows = r.bm;
+  const bool w3 = (a.flags & DV_W3) != 0;
+  if (w3 && (d->dtype != DV_F32 || f32_exact())) return r;
+  const bool strided = d->st > 1 || d->sh > 1 || d->sw > 1;
+  if (mode == MODE_DGRAD && strided && d->st <= 2 && d->sh <= 2 && d->sw <= 2 && d->kt >= d->st && d->kh >= d->sh && d->kw >= d->sw) {
+    // one dense stride-1 launch per parity class of the input positions (see ConvArgs): every class has >= 1 tap
     ConvArgs cls[8];
-    const int ncls = dgrad_classes(d, a, cls);
-    for (int i = 0; i < ncls; ++i)
-      if (!dvt_conv_tap_kind(&cls[i], MODE_DGRAD)) return 0;
-    return ncls > 0 ? 2 : 0;
+    r.ncls = dgrad_classes(d, a, cls);
+    if (w3) {
+      // pre-split weights: every class on the LDS-staged input-tile kernel (conv_tap.hip, temporal form), or not at all
+      for (int i = 0; i < r.ncls; ++i)
+        if (!dvt_conv_tap_kind(&cls[i], MODE_DGRAD)) return r;
+      r.path = ROUTE_TAP_CLASSES; r.kind = 2; r.rows = dvt_conv_tap_bm(&cls[0], 2);
+      return r;
+    }
+    if (a.bn_ws) return r;
+    for (int i = 0; i < r.ncls; ++i) {
+      int bm, bn;
+      pick_tile(d->dtype, cls[i].M, cls[i].NP, bm, bn);
+      r.gemm[i] = gemm_form(d->dtype, cls[i], bm, bn);
+    }
+    r.path = ROUTE_GEMM_CLASSES;
+    return r;
   }
-  trim_dead_taps(a, dgrad ? MODE_DGRAD : MODE_FWD, d->dtype);
-  return dvt_conv_tap_kind(&a, dgrad ? MODE_DGRAD : MODE_FWD);
+  if (!a.in_scale) {
+    trim_dead_taps(a, mode);
+  } else if (!strided) {                                // BatchNorm on load: never on a trimmed window
+    ConvArgs t = a;
+    trim_dead_taps(t, mode);
+    if (t.cls_on) return r;
+  }
+  if (d->dtype == DV_F32 && w3) {
+    if (const int G = dvt_conv_pp_lines(&a, mode)) {
+      r.path = ROUTE_PP; r.kind = 3; r.rows = G * a.g.rW;
+      return r;
+    }
+    if (const int k = dvt_conv_tap_kind(&a, mode)) {
+      r.path = ROUTE_TAP; r.kind = k; r.rows = dvt_conv_tap_bm(&a, k);
+      return r;
+    }
+    if (a.in_scale) {                                   // (the plain call would take the spatial LDS-staged form: keep it)
+      ConvArgs p = a;
+      p.in_scale = nullptr;
+      if (dvt_conv_tap_kind(&p, mode)) return r;
+    }
+  }
+  if (a.bn_ws) return r;                                // (the ordered fused reduce exists on the LDS-staged kernel only)
+  if ((r.ks_cols = ks_tile(d->dtype, a, r.bm))) {
+    r.path = a.in_scale ? ROUTE_NONE : ROUTE_KS;        // (the K-split kernel applies no BatchNorm on load)
+    return r;
+  }
+  r.gemm[0] = gemm_form(d->dtype, a, r.bm, r.bn);
+  // BatchNorm on load on conv_gemm: its 256 x 64 uniform-tap pre-split-weight form only, no bias / activation
+  if (a.in_scale && !(r.gemm[0].bnl && r.bm == 256 && r.bn == 64 && a.g.CP <= 256 && !(a.flags & (DV_BIAS | DV_RELU | DV_SIGMOID))))
+    return r;
+  r.path = ROUTE_GEMM;
+  return r;
+}
+
+// the launches of one forward / data gradient along its route
+static int launch_route(const dv_conv_desc* d, int mode, const ConvRoute& r, ConvArgs& a, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const bool fwd = mode == MODE_FWD;
+  switch (r.path) {
+    case ROUTE_PP: dvt_conv_pp_launch(&a, r.rows / a.g.rW, stream); break;
+    case ROUTE_TAP: dvt_conv_tap_launch(&a, mode, r.kind, r.rows, stream); break;
+    case ROUTE_KS:
+      if (fwd) launch_ks<MODE_FWD>(r.ks_cols, a, s);
+      else launch_ks<MODE_DGRAD>(r.ks_cols, a, s);
+      break;
+    case ROUTE_GEMM:
+      if (fwd) launch_gemm_dt<MODE_FWD>(d->dtype, r.gemm[0], a, s);
+      else launch_gemm_dt<MODE_DGRAD>(d->dtype, r.gemm[0], a, s);
+      break;
+    case ROUTE_TAP_CLASSES:
+    case ROUTE_GEMM_CLASSES: {
+      ConvArgs cls[8];
+      dgrad_classes(d, a, cls);
+      for (int i = 0; i < r.ncls; ++i) {
+        if (r.path == ROUTE_TAP_CLASSES) dvt_conv_tap_launch(&cls[i], MODE_DGRAD, r.kind, r.rows, stream);
+        else launch_gemm_dt<MODE_DGRAD>(d->dtype, r.gemm[i], cls[i], s);
+      }
+      break;
+    }
+    default: return DV_EUNSUPPORTED;
+  }
+  return dv_launch_status();
+}
+
+// the route of dv_conv3d_fwd (dgrad = 0) / dv_conv3d_dgrad (1) on this problem, as the kernel-choice queries report it
+static ConvRoute query_route(const dv_conv_desc* d, int dgrad) {
+  const int mode = dgrad ? MODE_DGRAD : MODE_FWD;
+  if (check_desc(d)) {                  // (no route; the GEMM tile, as dv_conv3d_tile_shape / tile_rows have always reported it)
+    ConvRoute r{};
+    const int64_t m = dgrad ? (int64_t)d->N * d->Ti * d->Hi * d->Wi : (int64_t)d->N * d->To * d->Ho * d->Wo;
+    pick_tile(d->dtype, (int)m, dgrad ? d->cin_pitch : d->cout_pitch, r.bm, r.bn);
+    r.rows = r.bm;
+    return r;
+  }
+  ConvArgs a;
+  conv_args(d, mode, a);
+  return route_conv(d, mode, a);
 }
 
 extern "C" int dv_conv3d_tap_kind(const dv_conv_desc* d, int32_t dgrad) {
-  if (!d || check_desc(d)) return 0;
-  return tap_choice(d, dgrad);
+  return d ? query_route(d, dgrad).kind : 0;
 }
 
 extern "C" int dv_conv3d_tap_rows(const dv_conv_desc* d, int32_t dgrad) {
-  if (!d || check_desc(d)) return 0;
-  const int kind = tap_choice(d, dgrad);
-  if (!kind) return 0;
-  if (kind == 3) return pp_rows_choice(d);
-  if (d->st > 1 || d->sh > 1 || d->sw > 1) return 256;           // (the parity classes of a strided data gradient)
-  ConvArgs a;
-  query_args(d, dgrad, a);
-  trim_dead_taps(a, dgrad ? MODE_DGRAD : MODE_FWD, d->dtype);
-  return dvt_conv_tap_rows(&a, dgrad ? MODE_DGRAD : MODE_FWD);
+  if (!d) return 0;
+  const ConvRoute r = query_route(d, dgrad);
+  return r.kind ? r.rows : 0;
 }
 
 extern "C" int dv_conv3d_tile_rows(const dv_conv_desc* d) {
-  if (!d) return DV_EINVAL;
-  if (!check_desc(d)) {
-    if (const int r = pp_rows_choice(d)) return r;
-    if (tap_choice(d, 0)) {              // (stride 1 here: the strided forward never runs on the LDS-staged kernel)
-      ConvArgs a;
-      query_args(d, 0, a);
-      trim_dead_taps(a, MODE_FWD, d->dtype);
-      return dvt_conv_tap_rows(&a, MODE_FWD);
-    }
-  }
-  const int64_t m = (int64_t)d->N * d->To * d->Ho * d->Wo;
-  int bm, bn;
-  pick_tile(d->dtype, (int)m, d->cout_pitch, bm, bn);
-  return bm;
-}
-
-extern "C" int dv_conv3d_tile_shape(const dv_conv_desc* d, int32_t dgrad, int32_t* rows, int32_t* cols) {
-  if (!d || !rows || !cols) return DV_EINVAL;
-  int bm, bn;
-  if (dgrad) {
-    const int64_t m = (int64_t)d->N * d->Ti * d->Hi * d->Wi;
-    pick_tile(d->dtype, (int)m, d->cin_pitch, bm, bn);
-  } else {
-    const int64_t m = (int64_t)d->N * d->To * d->Ho * d->Wo;
-    pick_tile(d->dtype, (int)m, d->cout_pitch, bm, bn);
-  }
-  *rows = bm; *cols = bn;
-  return DV_OK;
-}
-
-extern "C" int dv_conv3d_ksplit_cols(const dv_conv_desc* d, int32_t dgrad) {
-  if (!d || check_desc(d)) return 0;
-  if (dgrad && (d->st > 1 || d->sh > 1 || d->sw > 1)) return 0;
-  ConvArgs a;
-  fill_geom(d, dgrad ? MODE_DGRAD : MODE_FWD, a.g);
-  a.M = dgrad ? d->N * d->Ti * d->Hi * d->Wi : d->N * d->To * d->Ho * d->Wo;
-  a.N = dgrad ? d->Cin : d->Cout;
-  a.NP = dgrad ? d->cin_pitch : d->cout_pitch;
-  a.flags = d->flags & DV_W3;
-  a.cls_on = 0;
-  a.bn_x = nullptr; a.bn_ws = nullptr; a.bn_bytes = 0;
-  trim_dead_taps(a, dgrad ? MODE_DGRAD : MODE_FWD, d->dtype);
-  int bm, bn;
-  pick_tile(d->dtype, a.M, a.NP, bm, bn);
-  return ks_tile(d->dtype, a, bm);
+  return d ? query_route(d, 0).rows : DV_EINVAL;
 }
 
 extern "C" int dv_conv3d_stat_tiles(const dv_conv_desc* d) {
   if (!d) return DV_EINVAL;
   const int64_t m = (int64_t)d->N * d->To * d->Ho * d->Wo;
-  const int bm = dv_conv3d_tile_rows(d);
+  const int bm = query_route(d, 0).rows;
   return (int)((m + bm - 1) / bm);
 }
 
-// which forward kernel can apply a BatchNorm to its INPUT (dv_conv3d_fwd_bn_in): 1 the LDS-staged temporal form, 2 conv_gemm's
-// 256 x 64 uniform-tap form; 0 none
-static int fwd_bn_in_path(const dv_conv_desc* d) {
-  if (d->dtype != DV_F32 || f32_exact() || !(d->flags & DV_W3) || (d->flags & (DV_BIAS | DV_RELU | DV_SIGMOID))) return 0;
-  if (d->cin_pitch % 16 != 0) return 0;
-  static const float dummy = 0.f;
-  ConvArgs a;
-  query_args(d, 0, a);
-  a.in_scale = &dummy;
-  if (d->st == 1 && d->sh == 1 && d->sw == 1) {
-    trim_dead_taps(a, MODE_FWD, d->dtype);
-    if (a.cls_on) return 0;
-    if (dvt_conv_tap_kind(&a, MODE_FWD)) return 1;
-    if (tap_choice(d, 0)) return 0;          // (the plain launch would take the spatial LDS-staged form: keep it)
-  }
-  if (d->cin_pitch > 256 || d->kt * d->kh * d->kw > 32) return 0;
-  int bm, bn;
-  pick_tile(d->dtype, a.M, a.NP, bm, bn);
-  if (bm != 256 || bn != 64 || ks_tile(d->dtype, a, bm)) return 0;
-  return 2;
+extern "C" int dv_conv3d_tile_shape(const dv_conv_desc* d, int32_t dgrad, int32_t* rows, int32_t* cols) {
+  if (!d || !rows || !cols) return DV_EINVAL;
+  const ConvRoute r = query_route(d, dgrad);
+  *rows = r.bm; *cols = r.bn;
+  return DV_OK;
+}
+
+extern "C" int dv_conv3d_ksplit_cols(const dv_conv_desc* d, int32_t dgrad) {
+  if (!d) return 0;
+  const ConvRoute r = query_route(d, dgrad);
+  return r.path == ROUTE_KS ? r.ks_cols : 0;
 }
 
 static int fwd_impl(const dv_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
@@ -1842,58 +1905,18 @@ static int fwd_impl(const dv_conv_desc* d, const void* x, const void* w, const f
   if ((d->flags & DV_BIAS) && !bias) return DV_EINVAL;
   if ((d->flags & DV_STATS) && !stats) return DV_EINVAL;
   if (!aligned16(w) || !aligned16(y) || (reinterpret_cast<uintptr_t>(x) & 7)) return DV_EALIGN;
+  if (bn_in && (!bn_in->scale || !bn_in->shift)) return DV_EINVAL;
   ConvArgs a;
-  fill_geom(d, MODE_FWD, a.g);
-  a.src = x; a.w = w; a.out = y; a.bias = bias; a.stats = stats; a.sc_a = a.sc_b = nullptr; a.bn_x = nullptr; a.bn_ws = nullptr; a.bn_bytes = 0;
-  a.M = d->N * d->To * d->Ho * d->Wo;
-  a.N = d->Cout; a.NP = d->cout_pitch;
-  a.lds_ = d->ldx; a.ldo = d->ldy; a.ldw = a.g.Ktot;
-  a.flags = d->flags & (DV_BIAS | DV_RELU | DV_SIGMOID | DV_STATS);
-  const bool w3 = (d->flags & DV_W3) != 0;
-  if (w3 && (d->dtype != DV_F32 || f32_exact())) return DV_EUNSUPPORTED;
-  if (w3) { a.flags |= DV_W3; a.ldw = w3_rows(d->Cout); }
-  a.cls_on = 0;
-  int bn_path = 0;
-  if (bn_in) {
-    if (!bn_in->scale || !bn_in->shift) return DV_EINVAL;
-    bn_path = fwd_bn_in_path(d);
-    if (!bn_path) return DV_EUNSUPPORTED;
-    a.in_scale = bn_in->scale; a.in_shift = bn_in->shift; a.in_C = d->Cin; a.in_relu = (bn_in->flags & DV_RELU) ? 1 : 0;
-  }
-  {
-    const int64_t es = d->dtype == DV_F32 ? 4 : 2;
-    const int64_t sb = ((int64_t)d->N * d->Ti * d->Hi * d->Wi - 1) * d->ldx * es + (int64_t)d->cin_pitch * es;
-    const int64_t wb = w3 ? w3_bytes(d->Cout, a.g.Ktot) : (int64_t)d->Cout * a.g.Ktot * es;
-    if (sb >= (1ll << 31) || wb >= (1ll << 31) || d->kt > 32 || d->kh > 32 || d->kw > 32 || d->kt * d->kh * d->kw > 256)
-      return DV_EUNSUPPORTED;
-    a.src_bytes = (int)sb; a.w_bytes = (int)wb;
-    {
-      const int64_t ob = (((int64_t)a.M - 1) * a.ldo + a.NP) * 4;       // fp32 outputs: direct-store epilogue
-      a.out_bytes = (d->dtype == DV_F32 && ob < (1ll << 31)) ? (int)ob : 0;
-    }
-    a.fCP = make_fastdiv((uint32_t)a.g.CP);
-  }
+  if ((rc = conv_args(d, MODE_FWD, a))) return rc;
+  a.src = x; a.w = w; a.out = y; a.bias = bias; a.stats = stats;
+  if (bn_in) { a.in_scale = bn_in->scale; a.in_shift = bn_in->shift; a.in_C = d->Cin; a.in_relu = (bn_in->flags & DV_RELU) ? 1 : 0; }
+  const ConvRoute r = route_conv(d, MODE_FWD, a);
+  if (r.path == ROUTE_NONE) return DV_EUNSUPPORTED;
   const int gvb = gather_bytes(d->dtype, d->cin_pitch);
   if (gvb == 16 && !aligned16(x)) return DV_EALIGN;
   const int esz = d->dtype == DV_F32 ? 4 : 2;
   if ((d->ldx * esz) % gvb || (a.ldw * esz) % gvb) return DV_EALIGN;
-  if (bn_path != 2) trim_dead_taps(a, MODE_FWD, d->dtype);
-  if (d->dtype == DV_F32 && w3 && !bn_path && dvt_conv_pp_launch(&a, MODE_FWD, stream)) return dv_launch_status();
-  if (d->dtype == DV_F32 && w3 && bn_path != 2 && dvt_conv_tap_launch(&a, MODE_FWD, stream)) return dv_launch_status();
-  if (bn_path == 1) return DV_EUNSUPPORTED;          // (cannot happen: fwd_bn_in_path asked the same question)
-  int bm, bn;
-  pick_tile(d->dtype, a.M, a.NP, bm, bn);
-  a.ntn = (a.NP + bn - 1) / bn;
-  const int grid = a.ntn * ((a.M + bm - 1) / bm);
-  hipStream_t s = (hipStream_t)stream;
-  if (const int kbn = bn_path ? 0 : ks_tile(d->dtype, a, bm)) {
-    launch_ks<MODE_FWD>(kbn, a, s);
-    return dv_launch_status();
-  }
-  if (d->dtype == DV_F32) launch_gemm<float, MODE_FWD, 16>(bm, bn, a, grid, s);
-  else if (gvb == 16) launch_gemm<bf16_t, MODE_FWD, 16>(bm, bn, a, grid, s);
-  else launch_gemm<bf16_t, MODE_FWD, 8>(bm, bn, a, grid, s);
-  return dv_launch_status();
+  return launch_route(d, MODE_FWD, r, a, stream);
 }
 
 extern "C" int dv_conv3d_fwd(const dv_conv_desc* d, const void* x, const void* w, const float* bias, void* y,
@@ -1908,13 +1931,6 @@ extern "C" int dv_conv3d_fwd_bn_in(const dv_conv_desc* d, const void* x_bn, cons
 }
 
 // ---- fp8 pointwise GEMMs (BASELINE configs[4]: the 1x1x1 convs of resnet_2d3d.py's bottleneck blocks) --------------------
-template <typename T, int MODE>
-static void launch_gemm_fp8(int bm, int bn, const ConvArgs& a, int grid, hipStream_t s) {
-  // one tap, channel pitch a multiple of the 64-element K tile: the uniform-tap gather (tap state in SGPRs)
-  if (a.g.CP % 64 == 0) launch_gemm_ns<T, MODE, 16, 1, 2>(bm, bn, a, grid, s);
-  else launch_gemm_ns<T, MODE, 16, 0, 2>(bm, bn, a, grid, s);
-}
-
 static int check_fp8_desc(const dv_conv_desc* d) {
   int rc = check_desc(d);
   if (rc) return rc;
@@ -1925,101 +1941,36 @@ static int check_fp8_desc(const dv_conv_desc* d) {
   return DV_OK;
 }
 
-extern "C" int dv_conv3d_fwd_fp8(const dv_conv_desc* d, const void* x8, const void* w8, const float* scale_x,
-                                 const float* scale_w, void* y, float* stats, void* stream) {
+// forward: src = x (e4m3), scales (x, w); data gradient: src = dy (e5m2), scales (dy, w)
+static int fp8_impl(const dv_conv_desc* d, int mode, const void* src, const void* w, const float* sc_a, const float* sc_b, void* out,
+                    float* stats, void* stream) {
   int rc = check_fp8_desc(d);
   if (rc) return rc;
-  if (!x8 || !w8 || !y || !scale_x || !scale_w) return DV_EINVAL;
-  if ((d->flags & DV_STATS) && !stats) return DV_EINVAL;
-  if (!aligned16(x8) || !aligned16(w8) || !aligned16(y) || d->ldx % 16 || (d->ldy * 2) % 16) return DV_EALIGN;
+  const bool fwd = mode == MODE_FWD;
+  if (!src || !w || !out || !sc_a || !sc_b) return DV_EINVAL;
+  if ((d->flags & DV_STATS) && fwd && !stats) return DV_EINVAL;
+  if (!aligned16(src) || !aligned16(w) || !aligned16(out) || (fwd ? d->ldx : d->ldy) % 16 || ((fwd ? d->ldy : d->ldx) * 2) % 16)
+    return DV_EALIGN;
   ConvArgs a;
-  fill_geom(d, MODE_FWD, a.g);
-  a.src = x8; a.w = w8; a.out = y; a.bias = nullptr; a.stats = stats; a.sc_a = scale_x; a.sc_b = scale_w; a.bn_x = nullptr; a.bn_ws = nullptr; a.bn_bytes = 0;
-  a.M = d->N * d->To * d->Ho * d->Wo;
-  a.N = d->Cout; a.NP = d->cout_pitch;
-  a.lds_ = d->ldx; a.ldo = d->ldy; a.ldw = a.g.Ktot;
-  a.flags = d->flags & DV_STATS;
-  a.cls_on = 0;
-  const int64_t sb = ((int64_t)a.M - 1) * d->ldx + d->cin_pitch, wb = (int64_t)d->Cout * a.g.Ktot;
-  if (sb >= (1ll << 31) || wb >= (1ll << 31)) return DV_EUNSUPPORTED;
-  a.src_bytes = (int)sb; a.w_bytes = (int)wb;
-  a.out_bytes = 0;
-  a.fCP = make_fastdiv((uint32_t)a.g.CP);
-  int bm, bn;
-  pick_tile(DV_BF16, a.M, a.NP, bm, bn);
-  a.ntn = (a.NP + bn - 1) / bn;
-  launch_gemm_fp8<fp8e4_t, MODE_FWD>(bm, bn, a, a.ntn * ((a.M + bm - 1) / bm), (hipStream_t)stream);
+  if ((rc = conv_args(d, mode, a, true))) return rc;
+  a.src = src; a.w = w; a.out = out; a.stats = stats; a.sc_a = sc_a; a.sc_b = sc_b;
+  GemmForm f{};
+  pick_tile(DV_BF16, a.M, a.NP, f.bm, f.bn);
+  f.gvb = 16; f.ns = 2;
+  f.gm = a.g.CP % 64 == 0;      // one tap, channel pitch a multiple of the 64-element K tile: the uniform-tap gather (tap state in SGPRs)
+  if (fwd) launch_gemm<fp8e4_t, MODE_FWD, 16>(f, a, (hipStream_t)stream);
+  else launch_gemm<fp8e5_t, MODE_DGRAD, 16>(f, a, (hipStream_t)stream);
   return dv_launch_status();
+}
+
+extern "C" int dv_conv3d_fwd_fp8(const dv_conv_desc* d, const void* x8, const void* w8, const float* scale_x,
+                                 const float* scale_w, void* y, float* stats, void* stream) {
+  return fp8_impl(d, MODE_FWD, x8, w8, scale_x, scale_w, y, stats, stream);
 }
 
 extern "C" int dv_conv3d_dgrad_fp8(const dv_conv_desc* d, const void* dy8, const void* wd8, const float* scale_dy,
                                    const float* scale_w, void* dx, void* stream) {
-  int rc = check_fp8_desc(d);
-  if (rc) return rc;
-  if (!dy8 || !wd8 || !dx || !scale_dy || !scale_w) return DV_EINVAL;
-  if (!aligned16(dy8) || !aligned16(wd8) || !aligned16(dx) || d->ldy % 16 || (d->ldx * 2) % 16) return DV_EALIGN;
-  ConvArgs a;
-  fill_geom(d, MODE_DGRAD, a.g);
-  a.src = dy8; a.w = wd8; a.out = dx; a.bias = nullptr; a.stats = nullptr; a.sc_a = scale_dy; a.sc_b = scale_w; a.bn_x = nullptr; a.bn_ws = nullptr; a.bn_bytes = 0;
-  a.M = d->N * d->Ti * d->Hi * d->Wi;
-  a.N = d->Cin; a.NP = d->cin_pitch;
-  a.lds_ = d->ldy; a.ldo = d->ldx; a.ldw = a.g.Ktot;
-  a.flags = d->flags & DV_ACCUM;
-  a.cls_on = 0;
-  const int64_t sb = ((int64_t)a.M - 1) * d->ldy + d->cout_pitch, wb = (int64_t)d->Cin * a.g.Ktot;
-  if (sb >= (1ll << 31) || wb >= (1ll << 31)) return DV_EUNSUPPORTED;
-  a.src_bytes = (int)sb; a.w_bytes = (int)wb;
-  a.out_bytes = 0;
-  a.fCP = make_fastdiv((uint32_t)a.g.CP);
-  int bm, bn;
-  pick_tile(DV_BF16, a.M, a.NP, bm, bn);
-  a.ntn = (a.NP + bn - 1) / bn;
-  launch_gemm_fp8<fp8e5_t, MODE_DGRAD>(bm, bn, a, a.ntn * ((a.M + bm - 1) / bm), (hipStream_t)stream);
-  return dv_launch_status();
-}
-
-// the launches of one data gradient (`a` complete): parity classes / LDS-staged kernel / K split over the waves / conv_gemm
-static int dgrad_launch(const dv_conv_desc* d, ConvArgs& a, bool w3, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  a.cls_on = 0;
-  const bool strided = d->st > 1 || d->sh > 1 || d->sw > 1;
-  if (strided && d->kt >= d->st && d->kh >= d->sh && d->kw >= d->sw) {
-    // one dense stride-1 launch per parity class of the input positions (see ConvArgs): every class has >= 1 tap
-    ConvArgs cls[8];
-    const int ncls = dgrad_classes(d, a, cls);
-    if (w3) {
-      // pre-split weights: every class on the LDS-staged input-tile kernel (conv_tap.hip, temporal form), or not at all
-      for (int i = 0; i < ncls; ++i)
-        if (!dvt_conv_tap_kind(&cls[i], MODE_DGRAD)) return DV_EUNSUPPORTED;
-      for (int i = 0; i < ncls; ++i) dvt_conv_tap_launch(&cls[i], MODE_DGRAD, stream);
-      return dv_launch_status();
-    }
-    if (a.bn_ws) return DV_EUNSUPPORTED;
-    for (int i = 0; i < ncls; ++i) {
-      ConvArgs& c = cls[i];
-      int bm, bn;
-      pick_tile(d->dtype, c.M, c.NP, bm, bn);
-      c.ntn = (c.NP + bn - 1) / bn;
-      const int grid = c.ntn * ((c.M + bm - 1) / bm);
-      if (d->dtype == DV_F32) launch_gemm<float, MODE_DGRAD, 16>(bm, bn, c, grid, s);
-      else launch_gemm<bf16_t, MODE_DGRAD, 16>(bm, bn, c, grid, s);
-    }
-    return dv_launch_status();
-  }
-  trim_dead_taps(a, MODE_DGRAD, d->dtype);
-  if (d->dtype == DV_F32 && w3 && dvt_conv_tap_launch(&a, MODE_DGRAD, stream)) return dv_launch_status();
-  if (a.bn_ws) return DV_EUNSUPPORTED;           // (the ordered fused reduce exists on the LDS-staged kernel only)
-  int bm, bn;
-  pick_tile(d->dtype, a.M, a.NP, bm, bn);
-  a.ntn = (a.NP + bn - 1) / bn;
-  const int grid = a.ntn * ((a.M + bm - 1) / bm);
-  if (const int kbn = ks_tile(d->dtype, a, bm)) {
-    launch_ks<MODE_DGRAD>(kbn, a, s);
-    return dv_launch_status();
-  }
-  if (d->dtype == DV_F32) launch_gemm<float, MODE_DGRAD, 16>(bm, bn, a, grid, s);
-  else launch_gemm<bf16_t, MODE_DGRAD, 16>(bm, bn, a, grid, s);
-  return dv_launch_status();
+  return fp8_impl(d, MODE_DGRAD, dy8, wd8, scale_dy, scale_w, dx, nullptr, stream);
 }
 
 static int dgrad_impl(const dv_conv_desc* d, const void* dy, const void* wd, void* dx, const dv_bn_reduce* bnr, void* stream,
@@ -2038,13 +1989,8 @@ static int dgrad_impl(const dv_conv_desc* d, const void* dy, const void* wd, voi
   const int esz = d->dtype == DV_F32 ? 4 : 2;
   if ((d->ldx * esz) % 16) return DV_EALIGN;
   ConvArgs a;
-  fill_geom(d, MODE_DGRAD, a.g);
-  a.src = dy; a.w = wd; a.out = dx; a.bias = nullptr; a.stats = nullptr; a.sc_a = a.sc_b = nullptr;
-  a.M = d->N * d->Ti * d->Hi * d->Wi;
-  a.N = d->Cin; a.NP = d->cin_pitch;
-  a.lds_ = d->ldy; a.ldo = d->ldx; a.ldw = a.g.Ktot;
-  a.flags = d->flags & DV_ACCUM;
-  a.bn_x = nullptr; a.bn_ws = nullptr; a.bn_bytes = 0;
+  if ((rc = conv_args(d, MODE_DGRAD, a))) return rc;
+  a.src = dy; a.w = wd; a.out = dx;
   if (bnr) {
     a.bn_x = bnr->x; a.bn_ldx = bnr->ldx; a.bn_mean = bnr->mean; a.bn_invstd = bnr->invstd; a.bn_scale = bnr->scale;
     a.bn_shift = bnr->shift; a.bn_sums = bnr->sums; a.bn_rep = bnr->n_rep; a.bn_mask = (bnr->flags & DV_NO_RELU_MASK) ? 0 : 1;
@@ -2057,34 +2003,15 @@ static int dgrad_impl(const dv_conv_desc* d, const void* dy, const void* wd, voi
       a.bn_bytes = (int)xb;
     }
   }
-  const bool w3 = (d->flags & DV_W3) != 0;
-  if (w3 && (d->dtype != DV_F32 || f32_exact())) return DV_EUNSUPPORTED;      // (strided: only where every parity class runs on the
-                                                                              //  LDS-staged kernel, checked at the class launches)
-  if (w3) { a.flags |= DV_W3; a.ldw = w3_rows(d->Cin); }
-  {
-    const int64_t es = d->dtype == DV_F32 ? 4 : 2;
-    const int64_t sb = ((int64_t)d->N * d->To * d->Ho * d->Wo - 1) * d->ldy * es + (int64_t)d->cout_pitch * es;
-    const int64_t wb = w3 ? w3_bytes(d->Cin, a.g.Ktot) : (int64_t)d->Cin * a.g.Ktot * es;
-    if (sb >= (1ll << 31) || wb >= (1ll << 31) || d->kt > 32 || d->kh > 32 || d->kw > 32 || d->kt * d->kh * d->kw > 256)
-      return DV_EUNSUPPORTED;
-    a.src_bytes = (int)sb; a.w_bytes = (int)wb;
-    {
-      const int64_t ob = (((int64_t)a.M - 1) * a.ldo + a.NP) * 4;       // fp32 outputs: direct-store epilogue
-      a.out_bytes = (d->dtype == DV_F32 && ob < (1ll << 31)) ? (int)ob : 0;
-    }
-    a.fCP = make_fastdiv((uint32_t)a.g.CP);
-  }
   if (bnr && !bn_ws) {
     // dv_conv3d_dgrad_bn, the atomic form: the plain data gradient on whatever kernel takes it, then the reduce over what it wrote
-    ConvArgs tail = a;
+    const ConvArgs tail = a;
     a.bn_x = nullptr;
-    const int rc2 = dgrad_launch(d, a, w3, stream);
-    if (rc2) return rc2;
-    tail.out_bytes = a.out_bytes;
+    if ((rc = launch_route(d, MODE_DGRAD, route_conv(d, MODE_DGRAD, a), a, stream))) return rc;
     dvx_dgrad_bn_tail_launch(&tail, d->dtype == DV_F32 ? 1 : 0, stream);
     return dv_launch_status();
   }
-  return dgrad_launch(d, a, w3, stream);
+  return launch_route(d, MODE_DGRAD, route_conv(d, MODE_DGRAD, a), a, stream);
 }
 
 extern "C" int dv_conv3d_dgrad(const dv_conv_desc* d, const void* dy, const void* wd, void* dx, void* stream) {
@@ -2098,7 +2025,9 @@ extern "C" int dv_conv3d_dgrad_bn(const dv_conv_desc* d, const void* dy, const v
 }
 
 extern "C" int64_t dv_conv3d_dgrad_bn_workspace(const dv_conv_desc* d) {
-  if (!d || check_desc(d) || (d->flags & DV_ACCUM) || !tap_choice(d, 1)) return 0;
+  if (!d || check_desc(d) || (d->flags & DV_ACCUM)) return 0;
+  const int path = query_route(d, 1).path;
+  if (path != ROUTE_TAP && path != ROUTE_TAP_CLASSES) return 0;
   const int64_t rows = (int64_t)d->N * d->Ti * d->Hi * d->Wi;
   return dvt_bn_ws_floats(rows, d->cin_pitch) * 4;
 }
@@ -2143,8 +2072,8 @@ static int wgrad_tm_kind(const dv_conv_desc* d) {
   if (on != 2 && d->kt == 1 && d->kh == 7 && d->kw == 4 && d->st == 1 && d->sh == 2 && d->sw == 1 && !d->pt && !d->ph && !d->pw &&
       d->cin_pitch == 8 && d->ldx == 8 && d->Wo <= 64 && d->Wi <= 68) {
     const int64_t Mx = (int64_t)d->N * d->Ti * d->Hi * d->Wi, M = (int64_t)d->N * d->To * d->Ho * d->Wo;
-    static const int min_rows4 = env_int("DUALVAR_CONV_TAP_GRID", 128) <= 1 ? 1 : 8192;
-    if (Mx * 32 < (1ll << 31) && (M - 1) * d->ldy * 4 + (int64_t)d->cout_pitch * 4 < (1ll << 31) && M >= min_rows4) return 4;
+    if (Mx * 32 < (1ll << 31) && (M - 1) * d->ldy * 4 + (int64_t)d->cout_pitch * 4 < (1ll << 31) && M >= (conv_tap_any_size() ? 1 : 8192))
+      return 4;
     return 0;
   }
   if (d->sh != 1 || d->sw != 1) return 0;
@@ -2158,16 +2087,14 @@ static int wgrad_tm_kind(const dv_conv_desc* d) {
     // (128 channels) 310 -> 240; Mixed_3b (96 channels: a half-empty second tile) 148 -> 156 and the 12 544-row levels 89 -> 87
     // stay on conv_wgrad_dma_kernel (isolated, one box)
     const int64_t rows = (int64_t)d->N * d->Ti * d->Hi * d->Wi;
-    static const int any_size = env_int("DUALVAR_CONV_TAP_GRID", 128) <= 1;
-    if ((any_size && d->cin_pitch >= 16) || (rows >= 50000 && (d->cin_pitch + 63) / 64 * 64 * 10 <= d->cin_pitch * 11)) kind = 3;
+    if ((conv_tap_any_size() && d->cin_pitch >= 16) || (rows >= 50000 && (d->cin_pitch + 63) / 64 * 64 * 10 <= d->cin_pitch * 11)) kind = 3;
   }
   if (!kind) return 0;
   const int64_t Mx = (int64_t)d->N * d->Ti * d->Hi * d->Wi, M = (int64_t)d->N * d->To * d->Ho * d->Wo;
   const int64_t xb = (Mx - 1) * d->ldx * 4 + (int64_t)d->cin_pitch * 4, yb = (M - 1) * d->ldy * 4 + (int64_t)d->cout_pitch * 4;
   if (xb >= (1ll << 31) || yb >= (1ll << 31)) return 0;
   // (DUALVAR_CONV_TAP_GRID <= 1, the test knob of the LDS-staged kernels, also lets tiny problems through: tools/tap_check.py)
-  static const int min_rows = env_int("DUALVAR_CONV_TAP_GRID", 128) <= 1 ? 1 : 8192;
-  return M >= min_rows ? kind : 0;
+  return M >= (conv_tap_any_size() ? 1 : 8192) ? kind : 0;
 }
 
 
@@ -2445,5 +2372,10 @@ extern "C" int dv_conv3d_bn_in_ok(const dv_conv_desc* d) {
   if (!d || check_desc(d)) return 0;
   const int k = wgrad_tm_kind(d);
   if (k != 1 && k != 2) return 0;
-  return fwd_bn_in_path(d);
+  static const float dummy = 0.f;
+  ConvArgs a;
+  conv_args(d, MODE_FWD, a);
+  a.in_scale = &dummy;
+  const int path = route_conv(d, MODE_FWD, a).path;
+  return path == ROUTE_TAP ? 1 : path == ROUTE_GEMM ? 2 : 0;
 }

@@ -15,6 +15,27 @@ namespace {
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1 };
 
+// ---- routing switches (A/B runs, test knobs): each is read from the environment once per process ----------------------------
+static int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+// DUALVAR_F32_EXACT=1: fp32 convs on the exact-f32 MFMA kernels instead of the bf16 split (split3 below)
+static bool f32_exact() { static const bool v = env_int("DUALVAR_F32_EXACT", 0) != 0; return v; }
+// DUALVAR_CONV_TAP=0: forward / data gradient never on the LDS-staged input-tile kernel (conv_tap.hip)
+static int conv_tap_on() { static const int v = env_int("DUALVAR_CONV_TAP", 1); return v; }
+// DUALVAR_CONV_TAP_GRID: smallest grid that kernel takes, in 256-row x 64-column tiles (conv_tap.hip: tap_kind).  <= 1, the test
+// knob of the LDS-staged kernels, also lets tiny problems onto the pixel-pair stem form and the LDS-staged weight gradients
+static int conv_tap_grid() { static const int v = env_int("DUALVAR_CONV_TAP_GRID", 49); return v; }
+static bool conv_tap_any_size() { return conv_tap_grid() <= 1; }
+// DUALVAR_CONV_TAP_BM128=0: that kernel always on 256-row tiles; DUALVAR_CONV_TAP_BM128_GRID: largest 256-row grid that gets 128
+static int conv_tap_bm128() { static const int v = env_int("DUALVAR_CONV_TAP_BM128", 1); return v; }
+static int conv_tap_bm128_grid() { static const int v = env_int("DUALVAR_CONV_TAP_BM128_GRID", 768); return v; }
+// DUALVAR_CONV_PP_FWD=0: no pixel-pair stem form (conv_tap.hip: conv_pp_fwd_kernel)
+static int conv_pp_fwd() { static const int v = env_int("DUALVAR_CONV_PP_FWD", 1); return v; }
+// DUALVAR_CONV_KS=0: no K split over the waves (conv.hip: conv_gemm_ks_kernel)
+static int conv_ks() { static const int v = env_int("DUALVAR_CONV_KS", 1); return v; }
+
 struct ConvGeom {
   // "row space" (what m enumerates) and "source space" (the tensor the gather reads)
   int rT, rH, rW;        // row-space dims

@@ -751,10 +751,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
 // lines per tile of the pixel-pair stem form for this problem, or 0 (not that form / does not fit)
 static int pp_lines(const ConvArgs& a, int mode) {
-  static const int on = getenv("DUALVAR_CONV_PP_FWD") ? atoi(getenv("DUALVAR_CONV_PP_FWD")) : 1;
-  static const int any_size = (getenv("DUALVAR_CONV_TAP_GRID") ? atoi(getenv("DUALVAR_CONV_TAP_GRID")) : 128) <= 1;
   const ConvGeom& g = a.g;
-  if (!on || mode != MODE_FWD || !(a.flags & DV_W3) || (a.flags & (DV_BIAS | DV_RELU | DV_SIGMOID | DV_ACCUM)) || a.out_bytes <= 0) return 0;
+  if (!conv_pp_fwd() || mode != MODE_FWD || !(a.flags & DV_W3) || (a.flags & (DV_BIAS | DV_RELU | DV_SIGMOID | DV_ACCUM)) || a.out_bytes <= 0) return 0;
   if (a.cls_on || a.bn_x != nullptr || a.in_scale != nullptr) return 0;
   if (g.kt != 1 || g.kh != 7 || g.kw != 4 || g.st != 1 || g.sh != 2 || g.sw != 1 || g.pt || g.ph || g.pw || g.CP != 8 || a.lds_ != 8) return 0;
   if (g.rW < 1 || g.rW > 64 || g.sW < g.rW + 3 || g.sH < 2 * g.rH + 5) return 0;
@@ -762,7 +760,7 @@ static int pp_lines(const ConvArgs& a, int mode) {
     if (g.rH % G) continue;
     if ((2 * G + 5) * g.sW > 768) continue;                      // three staging units per thread
     if (2 * 64 * 96 + (size_t)(2 * G + 5) * g.sW * 48 > 54000) continue;       // three workgroups per CU
-    if (!any_size && (G * g.rW < 128 || (int64_t)(a.M / (G * g.rW)) * ((a.NP + 63) / 64) < 512)) return 0;
+    if (!conv_tap_any_size() && (G * g.rW < 128 || (int64_t)(a.M / (G * g.rW)) * ((a.NP + 63) / 64) < 512)) return 0;
     return G;
   }
   return 0;
@@ -771,14 +769,13 @@ static int pp_lines(const ConvArgs& a, int mode) {
 // ------------------------------------------------------------------------------------------ host side
 // 0: not applicable; 1: spatial; 2: temporal
 static int tap_kind(const ConvArgs& a, int mode) {
-  static const int on = getenv("DUALVAR_CONV_TAP") ? atoi(getenv("DUALVAR_CONV_TAP")) : 1;
   // smallest grid (counted in 256-row x 64-column tiles) the kernel takes.  With the 128-row tiles (tap_bm) the 64-channel
   // branches of the 12 544-row levels (49 tiles) belong here too: their data gradients leave conv_gemm_ks (nine launches, 498 -> 177
   // us) for +287 us of this kernel, forwards likewise, five more BatchNorms are applied on load -- step 16.35 - 16.49 -> 16.10 -
   // 16.22 ms (thresholds 128 / 49 / 25 / 10: 16.35, 16.16, 16.18, 16.36 ms).  Below that (the 1 152-row levels) conv_gemm_ks's K split
   // over the waves fills the chip better.  DUALVAR_CONV_TAP_GRID overrides (tests: 1).
-  static const int min_grid = getenv("DUALVAR_CONV_TAP_GRID") ? atoi(getenv("DUALVAR_CONV_TAP_GRID")) : 49;
-  if (!on) return 0;
+  const int min_grid = conv_tap_grid();
+  if (!conv_tap_on()) return 0;
   const ConvGeom& g = a.g;
   if (!(a.flags & DV_W3) || (a.flags & (DV_BIAS | DV_RELU | DV_SIGMOID)) || a.out_bytes <= 0) return 0;
   // the fused BatchNorm-backward reduce: only in its ordered form (workspace given), on a data gradient that is not accumulated
@@ -818,14 +815,12 @@ static void launch_tap(const TapArgs& t, int grid, size_t lds, hipStream_t s) {
 // workgroups, one wave per SIMD, latency bound): twice the workgroups, two or three resident per CU.  Not for the parity
 // classes of the strided stem data gradient (large) nor for eight-frame temporal tiles (128 / 8 pixels < one row block).
 static int tap_bm(const ConvArgs& a, int kind) {
-  static const int on = getenv("DUALVAR_CONV_TAP_BM128") ? atoi(getenv("DUALVAR_CONV_TAP_BM128")) : 1;
+  if (!conv_tap_bm128() || a.cls_on == 1) return 256;
+  if (kind == 2 && a.g.sT != 2 && a.g.sT != 4) return 256;
   // below ONE full round of three workgroups per CU (sweep on the headline step, kernel time summed over the step: 384 -> 17.60 -
   // 17.65 ms, 800 -> 17.38 - 17.41, 1 600 -> 17.33 - 17.43; step time equal within noise)
-  static const int max_grid = getenv("DUALVAR_CONV_TAP_BM128_GRID") ? atoi(getenv("DUALVAR_CONV_TAP_BM128_GRID")) : 768;
-  if (!on || a.cls_on == 1) return 256;
-  if (kind == 2 && a.g.sT != 2 && a.g.sT != 4) return 256;
   const int64_t grid = (int64_t)((a.M + 255) / 256) * ((a.NP + 63) / 64);
-  return grid < max_grid ? 128 : 256;
+  return grid < conv_tap_bm128_grid() ? 128 : 256;
 }
 
 }  // namespace
@@ -837,16 +832,15 @@ int64_t dvt_bn_ws_floats(int64_t rows, int np) {
   return kBnTickWords + (int64_t)ntn * bn_ws_floats_per_coltile(n_mt);
 }
 
-// rows per tile (= rows per BatchNorm partial) when dv_conv3d_fwd runs this problem on the pixel-pair stem form, else 0
-int dvt_conv_pp_rows(const void* conv_args, int mode) {
-  const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);
-  return pp_lines(a, mode) * a.g.rW;
-}
+// entry points for conv.hip (the argument block is conv_common.hpp's ConvArgs, passed by address).  The route (conv.hip:
+// route_conv) asks the three predicates and launches what they answered; the launches decide nothing themselves.
+int dvt_conv_pp_lines(const void* conv_args, int mode) { return pp_lines(*static_cast<const ConvArgs*>(conv_args), mode); }
+int dvt_conv_tap_kind(const void* conv_args, int mode) { return tap_kind(*static_cast<const ConvArgs*>(conv_args), mode); }
+int dvt_conv_tap_bm(const void* conv_args, int kind) { return tap_bm(*static_cast<const ConvArgs*>(conv_args), kind); }
 
-int dvt_conv_pp_launch(const void* conv_args, int mode, void* stream) {
+// the pixel-pair stem form with tiles of G output lines (G = dvt_conv_pp_lines)
+void dvt_conv_pp_launch(const void* conv_args, int G, void* stream) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);
-  const int G = pp_lines(a, mode);
-  if (!G) return 0;
   const ConvGeom& g = a.g;
   PpArgs t;
   t.src = a.src; t.w = a.w; t.out = a.out; t.stats = a.stats;
@@ -859,23 +853,11 @@ int dvt_conv_pp_launch(const void* conv_args, int mode, void* stream) {
   const int grid = t.ntn * (a.M / t.rows);
   const size_t lds = 2 * 64 * 96 + (size_t)t.npos * 48;
   hipLaunchKernelGGL((conv_pp_fwd_kernel<2>), dim3(grid), dim3(256), lds, (hipStream_t)stream, t);
-  return 1;
 }
 
-// entry points for conv.hip (the argument block is conv_common.hpp's ConvArgs, passed by address)
-int dvt_conv_tap_kind(const void* conv_args, int mode) { return tap_kind(*static_cast<const ConvArgs*>(conv_args), mode); }
-// rows per tile (= rows per BatchNorm partial) of that launch, 0 when the problem does not run on the kernel
-int dvt_conv_tap_rows(const void* conv_args, int mode) {
+// the LDS-staged kernel in form `kind` (dvt_conv_tap_kind) with tiles of bm rows (dvt_conv_tap_bm)
+void dvt_conv_tap_launch(const void* conv_args, int mode, int kind, int bm, void* stream) {
   const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);
-  const int kind = tap_kind(a, mode);
-  return kind ? tap_bm(a, kind) : 0;
-}
-
-// launches the LDS-staged kernel for this problem if it is one of its forms; returns 1 when it did
-int dvt_conv_tap_launch(const void* conv_args, int mode, void* stream) {
-  const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);
-  const int kind = tap_kind(a, mode);
-  if (!kind) return 0;
   const ConvGeom& g = a.g;
   TapArgs t;
   t.src = a.src; t.w = a.w; t.out = a.out; t.stats = a.stats;
@@ -886,7 +868,6 @@ int dvt_conv_tap_launch(const void* conv_args, int mode, void* stream) {
   t.CP = g.CP;
   t.H = g.sH; t.W = g.sW; t.T = g.sT; t.S = g.sH * g.sW;
   t.fW = make_fastdiv((uint32_t)g.sW); t.fH = make_fastdiv((uint32_t)g.sH); t.fS = make_fastdiv((uint32_t)t.S);
-  const int bm = tap_bm(a, kind);
   t.P = bm / g.sT; t.lgP = 0;
   while ((1 << t.lgP) < t.P) ++t.lgP;
   t.NQ = a.M / g.sT;
@@ -922,5 +903,4 @@ int dvt_conv_tap_launch(const void* conv_args, int mode, void* stream) {
     else if (g.kt == 4) launch_tap<1, 4, 2>(t, grid, lds, s);
     else launch_tap<1, 3, 2>(t, grid, lds, s);
   }
-  return 1;
 }

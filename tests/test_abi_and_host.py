@@ -490,6 +490,38 @@ def test_kernel_choice_queries_on_the_host():
     assert lib.dv_conv3d_tile_shape(C.byref(desc(128, 4, 28, 28, 64, 192, (1, 3, 3))), 0, C.byref(r), C.byref(c)) == 0
     assert (r.value, c.value) == (256, 64)
 
+    # Every query reads the one route the launch takes.  Mixed_4's 64 -> 64 1x3x3 runs on the LDS-staged kernel, so it reports no
+    # K-split column tile; over a sweep of the backbones' windows, map sizes and ragged channel counts the queries agree with
+    # each other: one kernel per problem, the forward's BatchNorm partials are that kernel's tiles, and they cover M.
+    tk = lambda d, dg=0: lib.dv_conv3d_tap_kind(C.byref(d), dg)       # noqa: E731
+    m4s = desc(128, 2, 7, 7, 64, 64, (1, 3, 3))
+    assert tk(m4s) == 1 and ks(m4s) == 0
+    wins = [((1, 1, 1), (1, 1, 1)), ((1, 3, 3), (1, 1, 1)), ((3, 1, 1), (1, 1, 1)), ((3, 3, 3), (1, 1, 1)),
+            ((1, 7, 7), (1, 2, 2)), ((7, 1, 1), (2, 1, 1)), ((3, 3, 3), (2, 2, 2))]
+    maps = [(4, 56, 56), (4, 28, 28), (2, 14, 14), (2, 7, 7), (1, 3, 3), (8, 6, 6)]
+    chans = [(64, 64), (64, 192), (192, 96), (20, 48), (832, 256), (512, 64), (384, 384), (160, 320)]
+    descs = [desc(N, T, H, W, ci, co, k, s, dtype=dt, flags=fl)
+             for dt, fl in [(L.DV_F32, 0), (L.DV_F32, L.DV_W3), (L.DV_F32, L.DV_W3 | L.DV_STATS), (L.DV_F32, L.DV_W3 | L.DV_ACCUM),
+                            (L.DV_BF16, 0)]
+             for N in (128, 2) for T, H, W in maps for ci, co in chans for k, s in wins]
+    for N, Ho, Wo in [(128, 56, 56), (128, 28, 28), (2, 56, 56), (2, 7, 64)]:    # the pixel-pair stem form: 1x7x4, stride (1, 2, 1)
+        d = desc(N, 8, 2 * Ho + 5, Wo + 3, 6, 64, (1, 7, 4), (1, 2, 1), (0, 0, 0), flags=L.DV_W3 | L.DV_STATS)
+        d.cin_pitch = d.ldx = 8
+        assert (d.Ho, d.Wo) == (Ho, Wo)
+        descs.append(d)
+    vals = lambda d: [getattr(d, f) for f, _ in d._fields_]           # noqa: E731
+    seen = set()
+    for d in descs:
+        for dg in (0, 1):
+            assert not (tk(d, dg) and ks(d, dg)), (vals(d), dg)
+            seen.add((dg, tk(d, dg) != 0, ks(d, dg) != 0))
+        rows, tiles = lib.dv_conv3d_tile_rows(C.byref(d)), lib.dv_conv3d_stat_tiles(C.byref(d))
+        if tk(d):
+            assert rows == lib.dv_conv3d_tap_rows(C.byref(d), 0), vals(d)
+        M = d.N * d.To * d.Ho * d.Wo
+        assert rows > 0 and 0 <= tiles * rows - M < rows, (vals(d), rows, tiles)
+    assert {(0, True, False), (0, False, True), (1, True, False), (1, False, True)} <= seen      # (the sweep reaches both kernels)
+
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason='a library without the check would launch: CPU-only hosts only')
 def test_single_tensor_bn_backward_refuses_mask_from_x():
