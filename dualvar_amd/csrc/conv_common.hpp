@@ -302,6 +302,14 @@ template <> struct OutOf<fp8e5_t> { typedef bf16_t type; };
 // is exact in fp32 and the MFMA accumulates in fp32, small terms first.  Six bf16 MFMAs (32 cycles each) replace eight
 // 32x32x2 f32 MFMAs (64 cycles each) per 32x32x16 block: 2.67x less matrix-pipe time at fp32-level accuracy
 // (DUALVAR_F32_EXACT=1 selects the exact-f32 MFMA kernels instead; tests/test_ops_gpu.py compares both with torch fp32).
+// Range of the "EXACTLY": the lowest bit of lo is 2^-23 |v| and must be a bf16 number.  bf16's smallest denormal is 2^-133, so
+// every normal fp32 |v| >= 2^-110 (and 0) splits exactly when the conversions keep bf16 denormals; they do on gfx950, and the matrix
+// cores multiply them: an identity convolution returns its input bit for bit down to [2^-110, 2^-109), 6 % of the elements at
+// 2^-114, none at 2^-120 (tests/test_conv_float64_gpu.py::test_split_exactness_range_on_the_matrix_cores, the fractions a host
+// emulation that keeps bf16 denormals predicts).  Hardware that flushed bf16 denormals would be exact for |v| >= 2^-103 only.  Below the edge the
+// value loses its low bits (it is not flushed).  The partial products of that measurement (lo * 1.0 = 2^-127 .. 2^-133) are fp32
+// denormals and the accumulator keeps them.  split3w below forms the same planes wherever mid needs no rounding; its edge was not
+// measured separately.
 struct Split3 { bf16x8 hi, mid, lo; };
 __device__ __forceinline__ Split3 split3(const float (&v)[8]) {
   Split3 s;

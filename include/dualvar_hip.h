@@ -224,7 +224,9 @@ int dv_conv3d_dgrad_fp8(const dv_conv_desc* d, const void* dy8, const void* wd8,
 /* ---- fp32 products on the bf16 matrix cores.  gfx950 has no TF32 path and its f32-input MFMA runs at 1/16 of the bf16 rate,
  * so DV_F32 convolutions split every fp32 operand EXACTLY into three bf16 (hi + mid + lo, 8 significant bits each) and
  * accumulate the six partial products of weight >= 2^-16 in fp32 (error at fp32 rounding level; DUALVAR_F32_EXACT=1 in the
- * environment selects exact-f32 MFMA kernels instead).  Activations are split inside the kernels; the WEIGHTS can be handed
+ * environment selects exact-f32 MFMA kernels instead).  "EXACTLY" holds for 0 and every normal |v| >= 2^-110 (the lowest bit of lo,
+ * 2^-23 |v|, must be a bf16 number; gfx950 keeps bf16 denormals in the conversion and on the matrix cores: measured); smaller
+ * values lose low bits.  Activations are split inside the kernels; the WEIGHTS can be handed
  * over already split and in fragment order (flag DV_W3 on dv_conv3d_fwd / stride-1 dv_conv3d_dgrad), made by dv_pack_w3 for
  * many tensors in one launch: [K tile of 16][k half][rows padded to 128][hi|mid|lo][8] bf16 = dv_w3_bytes(rows, Ktot) bytes
  * per tensor (rows = Cout of the forward layout [Cout][Ktot], Cin of the dgrad layout [Cin][Ktot]). */

@@ -612,3 +612,57 @@ def test_act_slice_refuses_misaligned_channel_offsets():
         a.slice(12, 24)
     with pytest.raises(AssertionError):
         a.slice(24, 32)                               # aligned, but runs past the pitch and past C
+
+
+CONV_TABLE_ROWS = [
+    'pw_c64_m294', 'pw_c24_m16384', 'sp3_c40_m16384', 'sp3_c128_c40_m16384', 'pw_c24_m131072', 'pw_c256_m65536', 'pw_c64_m131072',
+    'rgb_stem_sp7', 'w5x7x7_c8', 'tap_sp_m12544', 'tap_tm_m12544', 'tap_sp_m50176', 'tap_sp_c192_m100352', 'tap_tm_t2', 'tap_tm_t8', 'ks32_m72', 'ks64_m6080',
+    'ks_trim_t', 'ks_trim_hw', 'gemm_trim_t', 'gemm_trim_hw', 'stem_tm7_m12544', 'stem_tm7_m131072', 'pair_stem_pp',
+    'pair_stem_small', 'c83_tm3', 'c144_c230_sp3', 'c1_c1_sp3', 'c40_c3_sp3', 'w1x9x9_c16', 'now3_stem_tm7', 'now3_full3_s2',
+    'now3_sp3_s2_c83', 'now3_full3_s2_t1', 'now3_pw_s2', 'now3_sp3_c24', 'bf_rgb_stem', 'bf_sp3_c24', 'bf_sp3_c64',
+    'bf_pw_c64_m131072', 'bf_sp3_c192_m100352', 'bf_sp3_c320_m3136', 'bf_pw_c512_m1568', 'bf_sp3_c64_m25088', 'bf_w1x9x9_c16']
+
+CONV_TILES = ('64x32', '64x64', '64x128', '128x32', '128x64', '128x128', '256x64')
+# every member the table must reach (members are derived per row by conv_cases.members from the row's literals)
+CONV_REQUIRED = (
+    ['%s:path:%s' % (m, p) for m in ('fwd', 'dgrad') for p in ('GEMM', 'KS', 'TAP')] +
+    ['fwd:path:PP', 'dgrad:path:GEMM_CLASSES', 'dgrad:path:TAP_CLASSES'] +
+    ['%s:tile:%s' % (m, t) for m in ('fwd', 'dgrad') for t in CONV_TILES] +
+    ['f32:w3:generic:cp4', 'f32:w3:generic:cp8', 'f32:w3:generic:cp24', 'f32:w3:generic:cp40', 'f32:w3:generic:taps>32',
+     'f32:w3:uniform-tap', 'f32:plain-split',
+     'bf16:gather8', 'bf16:gather16', 'bf16:cp%32==0', 'bf16:cp%32!=0', 'bf16:stages2', 'bf16:stages4',
+     'trim:t:GEMM', 'trim:hw:GEMM', 'trim:t:KS', 'trim:hw:KS',
+     'fwd:ks32', 'fwd:ks64', 'dgrad:ks32', 'dgrad:ks64',
+     'dgrad:classes:2', 'dgrad:classes:4', 'dgrad:classes:8', 'dgrad:classes:empty-class', 'dgrad:classes:w3',
+     'dgrad:classes:no-w3', 'dgrad:strided-generic(k<s)',
+     'tap:kind1', 'tap:kind2', 'tap:rows128', 'tap:rows256',
+     'bn-on-load:1', 'bn-on-load:2', 'dgrad-bn:ordered', 'wgrad:bn-ok',
+     'wgrad:bf16:conv_wgrad_kernel:no-16-byte-gather', 'wgrad:bf16:conv_wgrad_kernel:window>8',
+     'wgrad:f32:conv_wgrad_kernel:window>8',
+     'wgrad:bf16:dma:128x128', 'wgrad:bf16:dma:64x256', 'wgrad:bf16:dma:128x256', 'wgrad:bf16:dma:192x256',
+     'wgrad:f32:dma:128x128', 'wgrad:f32:dma:64x128',
+     'wgrad:tm1', 'wgrad:tm2', 'wgrad:tm3', 'wgrad:tm4', 'wgrad:splits=1', 'wgrad:splits>1'] +
+    ['channels:%d' % ch for ch in (1, 3, 24, 40, 83, 144, 230)])
+
+
+def test_conv_case_table_routes_and_coverage():
+    """tests/conv_cases.py, the table tests/test_conv_float64_gpu.py runs: every row still takes the route it was written for
+    (the host-side kernel-choice queries against the literals of the row), and the table as a whole reaches every member of
+    CONV_REQUIRED above -- the route_conv paths, the conv_gemm tiles in both modes, the gather / weight forms of gemm_form,
+    trimmed windows, the K-split column tiles, the parity-class counts of the strided data gradients, the LDS-staged tile
+    heights, every weight-gradient kernel and table row -- and every row listed above.  A routing threshold that moves a
+    case, or a row taken out, is named here."""
+    from tests import conv_cases as T
+    moved, seen = [], set()
+    for c in T.CASES:
+        got = T.query(c)
+        want = (c.fwd, c.dgrad, c.wgrad, c.bn_in, c.dgrad_bn_ws)
+        for what, g, w in zip(('fwd', 'dgrad', 'wgrad', 'bn_in_ok', 'dgrad_bn_workspace'), got, want):
+            if g != w:
+                moved.append('%s %s: expected %r, the library reports %r' % (c.name, what, w, g))
+        seen |= set(T.members(c))
+    assert not moved, '\n'.join(moved)
+    assert len({c.name for c in T.CASES}) == len(T.CASES)
+    need = list(CONV_REQUIRED) + ['row:' + n for n in CONV_TABLE_ROWS]
+    missing = [m for m in need if m not in seen]
+    assert not missing, 'not covered by the table: %s' % ', '.join(missing)

@@ -1,8 +1,8 @@
 """GPU parity of every HIP kernel against the fp32 PyTorch-CPU op the oracle is made of.
 
 Tolerances: DV_F32 path -> 2e-5 relative to the tensor's max (fp32 storage, statistics and accumulation; products as six
-exact bf16 partial products on the matrix cores -- error at fp32 rounding level -- or, under DUALVAR_F32_EXACT=1, the
-f32-input MFMA); DV_BF16 path -> inputs are rounded to bf16 first, outputs compared at 1.5e-2 of the tensor's max
+exact bf16 partial products on the matrix cores -- error at fp32 rounding level: measured against float64 per route in
+tests/test_conv_float64_gpu.py, within 3 x torch's fp32 CPU conv on the same data (figures: DESIGN.md section 2) -- or, under DUALVAR_F32_EXACT=1, the f32-input MFMA); DV_BF16 path -> inputs are rounded to bf16 first, outputs compared at 1.5e-2 of the tensor's max
 (bf16 storage rounding, fp32 accumulation)."""
 import numpy as np
 import pytest
