@@ -163,6 +163,7 @@ SIGNATURES = {
     'dv_group_mean_bwd_f32': [P, I32, I32, I32, P, P],
     'dv_sgd_momentum': [P, P, P, I64, F, F, F, F, I32, P, P],
     'dv_ema': [P, P, I64, F, I32, P, P],
+    'dv_adam': [P, P, P, P, I64, F, F, F, F, F, F, F, F, F, I32, P, P],
 }
 
 _lib = None

@@ -122,3 +122,171 @@ class SGD(torch.optim.Optimizer):
             warnings.warn('optimizer state: %d of %d momentum buffers restored, the rest start at zero'
                           % (restored, len(views)))
         return restored
+
+
+def _step_value(s):
+    """state[i]['step'] of torch.optim.Adam: an int (torch 1.8, the reference's) or a 0-dim tensor (torch >= 1.12)"""
+    v = float(s.item()) if torch.is_tensor(s) else float(s)
+    if v < 0 or v != int(v):
+        raise ValueError('Adam step %r is not a non-negative whole number' % (s,))
+    return int(v)
+
+
+class Adam(torch.optim.Optimizer):
+    """Fused Adam over the parameter arenas (classifier.py:261-262 `--optim adam`: optim.Adam(params, lr, weight_decay) --
+    L2 weight decay coupled into the gradient, no amsgrad).  One dv_adam launch per run of trainable tensors updates the
+    master weights, both moments and the compute copy.  ONE step counter serves every tensor: all of them are stepped
+    together, and tensors that do not require gradients are never touched (torch's Adam skips them, weight decay included).
+    state_dict() / load_state_dict() speak torch.optim.Adam's format.
+    One lr, betas, eps and weight decay for all groups, as SGD here (the reference builds one group per tensor with the same
+    values, classifier.py:242-262): step() reads group 0, and load_state_dict refuses a state whose groups disagree.
+    The two moment arenas span the whole store, also when only the head trains: a slot is addressed by its arena offset."""
+
+    UNIFORM = ('lr', 'betas', 'eps', 'weight_decay')
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, stores=None, grad_sync=None):
+        if stores is None:
+            raise ValueError('dualvar_amd.optim.Adam updates ParamStore arenas: pass stores=model.stores()')
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError('Adam betas must lie in [0, 1): %r' % (betas,))
+        if not eps > 0.0:
+            raise ValueError('Adam eps must be > 0 (the zero padding between arena slots divides by it): %r' % (eps,))
+        # the remaining keys of torch.optim.Adam's groups at their defaults, so that torch's Adam can step on our state_dict
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                                      foreach=None, capturable=False, differentiable=False, fused=None,
+                                      decoupled_weight_decay=False))
+        self.stores = list(stores)
+        self.grad_sync = grad_sync
+        self._buf = {}
+        self._step = 0
+
+    def _moments(self, st):
+        """(exp_avg, exp_avg_sq) of one arena, [total] fp32 each (two allocations: ParamStore._view addresses a slot from
+        the start of the tensor's storage)"""
+        b = self._buf.get(id(st))
+        if b is None or b[0].numel() != st.total or b[0].device != st.master.device:
+            b = tuple(torch.zeros(st.total, dtype=torch.float32, device=st.master.device) for _ in range(2))
+            self._buf[id(st)] = b
+        return b
+
+    def zero_grad(self, set_to_none=False):
+        for st in self.stores:
+            st.zero_grad()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        g = self.param_groups[0]
+        lr, (b1, b2), eps, wd = float(g['lr']), g['betas'], float(g['eps']), float(g['weight_decay'])
+        self._step += 1
+        bc1, bc2 = 1.0 - float(b1) ** self._step, 1.0 - float(b2) ** self._step       # in double, as torch forms them
+        for st in self.stores:
+            if st.master is None:
+                continue
+            scale = 1.0
+            if self.grad_sync is not None:
+                scale = self.grad_sync(st)
+            copy = st.cc if st.dtype != ops.DV_F32 else None
+            mom = self._moments(st)
+            es = ops.ESIZE[st.dtype]
+            for a, n in st.trainable_ranges():
+                ops.call('dv_adam', st.master.data_ptr() + 4 * a, st.grad.data_ptr() + 4 * a, mom[0].data_ptr() + 4 * a,
+                         mom[1].data_ptr() + 4 * a, n, lr, 1.0 - float(b1), float(b2), 1.0 - float(b2), eps, wd, bc1, bc2, scale,
+                         st.dtype,
+                         (copy.data_ptr() + es * a) if copy is not None else None)
+            st.mark_dirty(cast_done=True)
+            st.pending_backward = 0
+
+    def _moment_views(self):
+        """[(index in torch's flat parameter order, exp_avg view, exp_avg_sq view)] for every parameter of an arena"""
+        where = {}
+        for st in self.stores:
+            if st.master is None:
+                continue
+            mom = self._moments(st)
+            for s in st.slots:
+                where[id(s.tensor)] = (st._view(mom[0], s), st._view(mom[1], s))
+        out, i = [], 0
+        for g in self.param_groups:
+            for p in g['params']:
+                if id(p) in where:
+                    out.append((i,) + where[id(p)])
+                i += 1
+        return out
+
+    def moment_summary(self):
+        """(step count, L2 norm of all exp_avg, L2 norm of all exp_avg_sq) over the optimizer's parameters: what a driver logs
+        after a resume"""
+        views = self._moment_views()
+        norms = [float(torch.sqrt(sum((x.double().pow(2).sum() for x in col), torch.zeros((), dtype=torch.float64,
+                                                                                          device=col[0].device))))
+                 for col in zip(*[(m, v) for _, m, v in views])] if views else [0.0, 0.0]
+        return self._step, norms[0], norms[1]
+
+    def state_dict(self):
+        """torch.optim.Adam's format: param_groups with flat parameter indices; state[i] = {'step', 'exp_avg', 'exp_avg_sq'}
+        (empty before the first step, as torch's is)"""
+        groups, i = [], 0
+        for g in self.param_groups:
+            d = {k: v for k, v in g.items() if k != 'params'}
+            d['params'] = list(range(i, i + len(g['params'])))
+            i += len(g['params'])
+            groups.append(d)
+        state = {}
+        if self._step > 0:
+            state = {i: {'step': torch.tensor(float(self._step)), 'exp_avg': m.detach().cpu().clone(),
+                         'exp_avg_sq': v.detach().cpu().clone()} for i, m, v in self._moment_views()}
+        return {'state': state, 'param_groups': groups}
+
+    def load_state_dict(self, sd):
+        """Accepts torch.optim.Adam state ('step' an int or a tensor) and this class's own; returns the number of parameters
+        whose moments were restored and warns when some are missing.  Everything is validated before anything changes."""
+        import warnings
+        if any(st.master is None for st in self.stores):
+            raise ValueError('the parameter arenas are not materialised yet (backbone.prepare(device), or one forward pass): '
+                             'there is nowhere to load the moments into')
+        views = self._moment_views()
+        if len(sd['param_groups']) != len(self.param_groups):
+            raise ValueError('optimizer state has %d param_groups, this optimizer %d' % (len(sd['param_groups']), len(self.param_groups)))
+        for s in sd['param_groups']:
+            for k in ('amsgrad', 'maximize', 'decoupled_weight_decay'):
+                if s.get(k):
+                    raise ValueError('optimizer state was saved with %s=True, which this Adam does not implement' % k)
+        for k in self.UNIFORM:
+            vals = {(tuple(s[k]) if k == 'betas' else s[k]) for s in sd['param_groups'] if k in s}
+            if len(vals) > 1:
+                raise ValueError('optimizer state has groups with different %s %s: this Adam steps every tensor with one value'
+                                 % (k, sorted(vals)))
+        state = sd.get('state', {})
+        staged, steps = [], set()
+        for i, m, v in views:
+            e = state.get(i, state.get(str(i)))
+            if e is None:
+                staged.append((m, v, None, None))
+                continue
+            missing = [k for k in ('step', 'exp_avg', 'exp_avg_sq') if k not in e]
+            if missing:
+                raise ValueError('optimizer state %d lacks %s: not an Adam state' % (i, ', '.join(missing)))
+            for k in ('exp_avg', 'exp_avg_sq'):
+                if tuple(e[k].shape) != tuple(m.shape):
+                    raise ValueError('%s %d has shape %s, parameter has %s' % (k, i, tuple(e[k].shape), tuple(m.shape)))
+            steps.add(_step_value(e['step']))
+            staged.append((m, v, e['exp_avg'], e['exp_avg_sq']))
+        if len(steps) > 1:
+            raise ValueError('optimizer state holds different step counts %s: this Adam keeps one counter' % sorted(steps))
+        # ... then mutate
+        for g, s in zip(self.param_groups, sd['param_groups']):
+            g.update({k: (tuple(v) if k == 'betas' else v) for k, v in s.items() if k != 'params'})
+        restored = 0
+        with torch.no_grad():
+            for m, v, em, ev in staged:
+                if em is None:
+                    m.zero_()
+                    v.zero_()
+                else:
+                    m.copy_(em.to(device=m.device, dtype=m.dtype))
+                    v.copy_(ev.to(device=v.device, dtype=v.dtype))
+                    restored += 1
+        self._step = steps.pop() if steps else 0
+        if restored != len(views):
+            warnings.warn('optimizer state: %d of %d Adam moments restored, the rest start at zero' % (restored, len(views)))
+        return restored

@@ -92,7 +92,7 @@ class ClipState:
         self._no_colour_yet('crop')
         if self.out is not None:
             raise ValueError('crop after a resize is not expressible in one dv_augment_ingest row')
-        if self.flip:
+        if np.any(self.flip):
             raise ValueError('crop after a flip: put the crop first')
         self.i, self.j, self.h, self.w = self.i + i, self.j + j, h, w
 
@@ -117,7 +117,7 @@ class ClipState:
             raise ValueError('at most %d colour ops and one contrast per frame' % AUG_MAX_OPS)
         t = np.zeros(self.N, dtype=AUG_ROW)
         t['src'], t['crop_i'], t['crop_j'], t['crop_h'], t['crop_w'] = self.src, self.i, self.j, self.h, self.w
-        t['flip'] = int(self.flip)
+        t['flip'] = np.asarray(self.flip, dtype=np.int32)       # one flag for the clip, or one per frame (per-block flips)
         if self.block is not None:
             return t
         for n in range(self.N):

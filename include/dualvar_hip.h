@@ -37,7 +37,7 @@ extern "C" {
    2: dv_conv3d_wgrad (workspace, workspace_bytes), dv_bn_bwd_reduce (ws), dv_infonce_fwd (workspace, bytes),
       dv_augment_ingest (blur, blur_scratch) gained arguments; dv_bn_item grew by red_ws (round 2 of this build).
    (dv_conv3d_ksplit_cols, dv_conv3d_wgrad_bn, dv_conv3d_wgrad_bn_ok, dv_augment_ingest_blocks / dv_aug_patch,
-   dv_resample_u8 / dv_resample_desc were ADDED under version 2: additions do not bump it.) */
+   dv_resample_u8 / dv_resample_desc, dv_adam were ADDED under version 2: additions do not bump it.) */
 #define DV_ABI_VERSION 2
 
 enum { DV_F32 = 0, DV_BF16 = 1 };
@@ -594,6 +594,17 @@ int dv_mean_f32(const float* x, int32_t n, float* out, void* stream);
 int dv_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, float mu, float wd,
                     float grad_scale, int32_t copy_dtype, void* p_copy, void* stream);
 int dv_ema(float* k, const float* q, int64_t n, float m, int32_t copy_dtype, void* k_copy, void* stream);
+/* Adam over one contiguous arena range (classifier.py:261-262 `--optim adam`: torch.optim.Adam(params, lr, weight_decay),
+ * single-tensor form, L2 weight decay coupled into the gradient), one pass, every line one fp32 rounding per operation:
+ *   d = g*grad_scale + wd*p;   m = m + omb1*(d - m);   v = b2*v + (omb2*d)*d;
+ *   p = p - (lr / bc1) * (m / (sqrtf(v) / sqrtf(bc2) + eps));   optional compute-dtype copy of p (as dv_sgd_momentum).
+ * omb1 = 1 - b1, omb2 = 1 - b2, bc1 = 1 - b1^t, bc2 = 1 - b2^t are formed by the caller in double (torch forms them so) and
+ * arrive rounded to float.  sqrtf and `/` are the CORRECTLY ROUNDED IEEE pair (hipcc's default; no fast-math reciprocal or
+ * rsqrt), and nothing is contracted into an FMA: one rounding per operation written above.  eps must be > 0 (the zero padding
+ * between arena slots has g = v = 0 and stays 0), 0 < omb1, omb2 <= 1, 0 <= b2 < 1, bc1, bc2 > 0: DV_EINVAL otherwise.
+ * p, g, m, v 16-byte aligned. */
+int dv_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float omb1, float b2, float omb2, float eps,
+            float wd, float bc1, float bc2, float grad_scale, int32_t copy_dtype, void* p_copy, void* stream);
 
 #ifdef __cplusplus
 }

@@ -88,7 +88,7 @@ def parse_args(argv=None):
     p.add_argument('--frame_root', default=None, type=str,
                    help='*-2clip-stage-prototype: <class>/<video>/image_%%05d.jpg (default: the reference\'s path)')
     # optimizer
-    p.add_argument('--optim', default='sgd', type=str)
+    p.add_argument('--optim', default='sgd', type=str, help="'adam' selects dualvar_amd.optim.Adam; anything else SGD")
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--lr', default=0.03, type=float)
     p.add_argument('--wd', default=5e-4, type=float)
@@ -319,7 +319,11 @@ def main_worker(gpu, ngpus_per_node, args):
     gsync = GradSync() if args.distributed else None
     if gsync is not None:
         gsync.attach(model)         # single-pass objectives: bucket-wise all-reduce from inside the backward pass
-    optimizer = SGD(params, lr=args.lr, weight_decay=args.wd, momentum=0.9, stores=model.stores(), grad_sync=gsync)
+    if args.optim == 'adam':
+        from dualvar_amd.optim import Adam
+        optimizer = Adam(params, lr=args.lr, weight_decay=args.wd, stores=model.stores(), grad_sync=gsync)
+    else:
+        optimizer = SGD(params, lr=args.lr, weight_decay=args.wd, momentum=0.9, stores=model.stores(), grad_sync=gsync)
 
     per_rank = max(args.epoch_size // max(args.world_size, 1), args.batch_size)
     n_samples = per_rank * max(args.world_size, 1)
@@ -363,8 +367,13 @@ def main_worker(gpu, ngpus_per_node, args):
             neq_load_customized(model, ck['state_dict'], verbose=True, args=args)
         if 'optimizer' in ck:
             try:
+                # the optimizer state lives in arenas shaped like the parameter arenas: they must exist before it is loaded
+                # (they otherwise appear with the first forward pass, and the state would be dropped without a word)
+                for m_ in model.modules():
+                    if hasattr(m_, 'prepare') and hasattr(m_, 'store'):
+                        m_.prepare(torch.device('cuda', args.gpu))
                 n = optimizer.load_state_dict(ck['optimizer'])
-                args.logger.info('optimizer state restored (%d momentum buffers)' % n)
+                args.logger.info('optimizer state restored (%d %s)' % (n, 'Adam moment pairs' if args.optim == 'adam' else 'momentum buffers'))
             except Exception as e:
                 args.logger.info('optimizer state not restored: %s' % e)
     elif args.pretrain and os.path.isfile(args.pretrain):
