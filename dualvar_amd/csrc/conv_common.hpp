@@ -1,6 +1,7 @@
-// Device-side pieces shared by the convolution translation units (conv.hip: the hot path; conv_tap.hip: the LDS-staged
-// input-tile kernels for the separable convs; conv_experiments.hip: measured-and-not-selected kernels kept under test).
-// Everything sits in an anonymous namespace: each translation unit gets its own copy, nothing is exported.
+// Device-side pieces and argument blocks shared by the convolution translation units: conv.hip (the GEMM and DMA kernels and
+// all host code: one plan per call, route_conv for a forward / data gradient, plan_wgrad for a weight gradient), conv_tap.hip /
+// conv_tap_wgrad.hip (the LDS-staged kernels those plans can pick), conv_experiments.hip (the opt-in, not-selected form).
+// Everything sits in an anonymous namespace: each translation unit gets its own copy (argument blocks cross by address).
 #pragma once
 #include "common.hpp"
 #include <algorithm>
@@ -9,9 +10,7 @@
 #include <type_traits>
 #include <utility>
 
-
 namespace {
-
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1 };
 
@@ -421,16 +420,20 @@ __device__ __forceinline__ void wgrad_store_block(const WgradArgs& a, int split,
   }
 }
 
+// dv_conv3d_wgrad_bn: the dY operand is dv_bn_bwd_apply's output formed on the fly from g = dy and the BatchNorm's input x (same
+// rows / pitch as dy), the fields of dv_bn_bwd.  x == nullptr: plain weight gradient (nothing else is read).
+struct BnBwdFuse {
+  const void* x;
+  const float *mean, *invstd, *gamma, *scale, *shift, *sums;
+  float *dgamma, *dbeta;
+  float inv_count, dscale;
+  int rep, mask;          // replicas of sums; 1: g is masked by relu(x * scale + shift) > 0 first
+};
 
 struct WgradDmaArgs {
   WgradArgs w;
   int x_bytes, dy_bytes;
-  // BNA (dv_conv3d_wgrad_bn): the dY operand is formed from g = w.dy and the BatchNorm's input bn_x (same rows / pitch)
-  const void* bn_x;
-  const float *bn_mean, *bn_invstd, *bn_gamma, *bn_scale, *bn_shift, *bn_sums;
-  float *bn_dgamma, *bn_dbeta;
-  float bn_inv_count, bn_dscale;
-  int bn_rep, bn_mask;
+  BnBwdFuse bn;           // BNA
 };
 
 // rows of RB bytes: four consecutive rows must fall on four different 64-byte bank groups of the 256-byte LDS line
@@ -471,13 +474,9 @@ struct TmWgradArgs {
   FastDiv fW, fH;
   // kind 4: the pixel-pair RGB stem conv (window 1 x 7 x 4 over 8-channel pixel pairs, stride (1, 2, 1), no padding): one output
   // line per step.  Wo / Ho output pixels per line / lines per frame, Wp / Hp pairs per input line / input lines per frame,
-  // nchunks = N * T * Ho lines.  bn_x != nullptr: the dY operand is dv_bn_bwd_apply's output formed on the fly (dv_conv3d_wgrad_bn)
+  // nchunks = N * T * Ho lines.  bn.x != nullptr: dv_conv3d_wgrad_bn
   int Wo, Ho, Wp, Hp;
-  const void* bn_x;
-  const float *bn_mean, *bn_invstd, *bn_gamma, *bn_scale, *bn_shift, *bn_sums;
-  float *bn_dgamma, *bn_dbeta;
-  float bn_inv_count, bn_dscale;
-  int bn_rep, bn_mask;
+  BnBwdFuse bn;
   // kinds 1, 2: the x operand is y = [relu](x * in_scale + in_shift) formed on the fly (dv_conv3d_wgrad_bn_in; see ConvArgs)
   const float* in_scale = nullptr;
   const float* in_shift = nullptr;

@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int bi = wave >> 1, par = wave & 1;
   const int ln_begin = split * a.chunks_per_split, ln_end = min(a.nchunks, ln_begin + a.chunks_per_split);
   const dma_rsrc_t x_rs = dma_make_rsrc(a.x, (unsigned)a.x_bytes), dy_rs = dma_make_rsrc(a.dy, (unsigned)a.dy_bytes);
-  const dma_rsrc_t bx_rs = dma_make_rsrc(BNA ? a.bn_x : a.dy, (unsigned)a.dy_bytes);
+  const dma_rsrc_t bx_rs = dma_make_rsrc(BNA ? a.bn.x : a.dy, (unsigned)a.dy_bytes);
   const unsigned ldyb = (unsigned)a.ldy * 4u;
   const int Wo = a.Wo, Wp = a.Wp;
 
@@ -459,14 +459,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       float k1 = 0.f, k2 = 0.f, k3 = 0.f, sc = 0.f, sh = 0.f;
       if (c < a.Cout) {
         float sg = 0.f, sgx = 0.f;
-        for (int r = 0; r < a.bn_rep; ++r) { sg += a.bn_sums[(size_t)r * 2 * cpb + c]; sgx += a.bn_sums[(size_t)r * 2 * cpb + cpb + c]; }
-        k1 = a.bn_gamma[c] * a.bn_invstd[c];
-        k2 = -k1 * a.bn_invstd[c] * sgx * a.bn_inv_count;
-        k3 = -k1 * sg * a.bn_inv_count - k2 * a.bn_mean[c];
-        if (a.bn_mask) { sc = a.bn_scale[c]; sh = a.bn_shift[c]; }
-        if (split == 0 && a.bn_dgamma) {                         // one workgroup per channel tile: dgamma, dbeta
-          a.bn_dbeta[c] += a.bn_dscale * sg;
-          a.bn_dgamma[c] += a.bn_dscale * sgx;
+        for (int r = 0; r < a.bn.rep; ++r) { sg += a.bn.sums[(size_t)r * 2 * cpb + c]; sgx += a.bn.sums[(size_t)r * 2 * cpb + cpb + c]; }
+        k1 = a.bn.gamma[c] * a.bn.invstd[c];
+        k2 = -k1 * a.bn.invstd[c] * sgx * a.bn.inv_count;
+        k3 = -k1 * sg * a.bn.inv_count - k2 * a.bn.mean[c];
+        if (a.bn.mask) { sc = a.bn.scale[c]; sh = a.bn.shift[c]; }
+        if (split == 0 && a.bn.dgamma) {                         // one workgroup per channel tile: dgamma, dbeta
+          a.bn.dbeta[c] += a.bn.dscale * sg;
+          a.bn.dgamma[c] += a.bn.dscale * sgx;
         }
       }
       float* cf = reinterpret_cast<float*>(smem + COFF);
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float act = xv[e] * cf[192 + e] + cf[256 + e];   // the forward's expression (dv_bn_apply), same rounding
-          const float gg = (a.bn_mask && !(act > 0.f)) ? 0.f : v[e];
+          const float gg = (a.bn.mask && !(act > 0.f)) ? 0.f : v[e];
           v[e] = cf[e] * gg + cf[64 + e] * xv[e] + cf[128 + e];  // dv_bn_bwd_apply's expression
         }
       }
@@ -613,7 +613,7 @@ void dvw_wgrad_tm_launch(const void* args, int grid, void* stream) {
   const TmWgradArgs& a = *static_cast<const TmWgradArgs*>(args);
   hipStream_t s = (hipStream_t)stream;
   if (a.kind == 4) {
-    if (a.bn_x) hipLaunchKernelGGL((conv_wgrad_pp_kernel<true>), dim3(grid), dim3(256), 0, s, a);
+    if (a.bn.x) hipLaunchKernelGGL((conv_wgrad_pp_kernel<true>), dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_wgrad_pp_kernel<false>), dim3(grid), dim3(256), 0, s, a);
   } else if (a.kind == 3) hipLaunchKernelGGL((conv_wgrad_sp_kernel<0>), dim3(grid), dim3(256), 0, s, a);
   else if (a.in_scale != nullptr) {

@@ -2,8 +2,8 @@
 
 Every row is one convolution problem with the kernels it is EXPECTED to run on, written out as literals: the forward's and
 the data gradient's route (`route_conv` of csrc/conv.hip: path, GEMM tile, LDS-staged kind and rows, K-split columns, rows
-and number of the BatchNorm partial tiles) and the weight gradient's plan (`plan_wgrad`: tile, row splits, workspace, and
-whether the fused BatchNorm forms take it).  The expectations are read back through the host-side queries of
+and number of the BatchNorm partial tiles) and the weight gradient's plan (`plan_wgrad`, the one decision its launch and
+its queries read: tile, row splits, workspace, and whether the fused BatchNorm forms take it).  The expectations are read back through the host-side queries of
 include/dualvar_hip.h (no device needed), so
 
 * the CPU test proves on any machine that every row still runs where it was written for (a routing threshold that moves a

@@ -498,7 +498,7 @@ def test_kernel_choice_queries_on_the_host():
     assert tk(m4s) == 1 and ks(m4s) == 0
     wins = [((1, 1, 1), (1, 1, 1)), ((1, 3, 3), (1, 1, 1)), ((3, 1, 1), (1, 1, 1)), ((3, 3, 3), (1, 1, 1)),
             ((1, 7, 7), (1, 2, 2)), ((7, 1, 1), (2, 1, 1)), ((3, 3, 3), (2, 2, 2))]
-    maps = [(4, 56, 56), (4, 28, 28), (2, 14, 14), (2, 7, 7), (1, 3, 3), (8, 6, 6)]
+    maps = [(4, 56, 56), (4, 28, 28), (2, 14, 14), (2, 7, 7), (1, 3, 3), (8, 6, 6), (8, 56, 56)]     # (the last: the 7x1x1 stem)
     chans = [(64, 64), (64, 192), (192, 96), (20, 48), (832, 256), (512, 64), (384, 384), (160, 320)]
     descs = [desc(N, T, H, W, ci, co, k, s, dtype=dt, flags=fl)
              for dt, fl in [(L.DV_F32, 0), (L.DV_F32, L.DV_W3), (L.DV_F32, L.DV_W3 | L.DV_STATS), (L.DV_F32, L.DV_W3 | L.DV_ACCUM),
@@ -521,6 +521,38 @@ def test_kernel_choice_queries_on_the_host():
         M = d.N * d.To * d.Ho * d.Wo
         assert rows > 0 and 0 <= tiles * rows - M < rows, (vals(d), rows, tiles)
     assert {(0, True, False), (0, False, True), (1, True, False), (1, False, True)} <= seen      # (the sweep reaches both kernels)
+
+    # The weight gradient has one plan as well (plan_wgrad): the tile, the row splits, the workspace and the two fused-form
+    # answers are reads of it and agree with each other on every problem of the sweep (its own descriptor has no flags;
+    # dv_conv3d_bn_in_ok also asks the forward, which needs the pre-split weights).
+    r, c, sp = C.c_int32(), C.c_int32(), C.c_int32()
+    wseen, wdone = set(), set()
+    for d in descs:
+        key = tuple(vals(d)[:-1])                         # (all but the flags, the descriptor's last field)
+        if key in wdone:
+            continue
+        wdone.add(key)
+        flags, d.flags = d.flags, 0
+        assert lib.dv_conv3d_wgrad_tile(C.byref(d), C.byref(r), C.byref(c), C.byref(sp)) == 0, vals(d)
+        tile, splits = (r.value, c.value), sp.value
+        ws, bn_ok = lib.dv_conv3d_wgrad_workspace(C.byref(d)), lib.dv_conv3d_wgrad_bn_ok(C.byref(d))
+        d.flags = L.DV_W3
+        bn_in = lib.dv_conv3d_bn_in_ok(C.byref(d))
+        d.flags = flags
+        S = (d.Cout * d.kt * d.kh * d.kw * d.cin_pitch + 63) // 64 * 64
+        assert splits >= 1 and ws == (splits * S * 4 if splits > 1 else 0), (vals(d), tile, splits, ws)
+        if bn_ok:
+            assert d.dtype == L.DV_F32 and tile in ((64, 128), (64, 224)), (vals(d), tile)
+        if bn_in:
+            assert tile in ((64, 192), (64, 224)), (vals(d), tile, bn_in)
+        wseen.add((d.dtype, tile, bn_in, bn_ok))
+    assert len(wdone) == 1572
+    tiles_of = lambda dt: {t for dd, t, _, _ in wseen if dd == dt}      # noqa: E731
+    assert {(128, 128), (64, 256), (128, 256), (192, 256)} <= tiles_of(L.DV_BF16)       # the bf16 DMA list ...
+    assert {(128, 128), (64, 128)} <= tiles_of(L.DV_F32)                                # ... the fp32 one ...
+    assert {(64, 128), (128, 64)} <= tiles_of(L.DV_BF16)      # ... conv_wgrad_kernel's two (no bf16 DMA tile is 64 x 128)
+    assert {(L.DV_F32, (64, 192), 0, 0), (L.DV_F32, (64, 192), 1, 0), (L.DV_F32, (64, 224), 2, 0),
+            (L.DV_F32, (64, 224), 0, 1)} <= wseen             # the LDS-staged forms, with and without their fused variants
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason='a library without the check would launch: CPU-only hosts only')
