@@ -147,6 +147,10 @@ SIGNATURES = {
     'dv_gate_scale': [I32, P, I32, P, I32, I32, I32, P, I32, P],
     'dv_gate_bwd_reduce': [I32, P, I32, P, I32, P, I32, I32, I32, P, I32, P],
     'dv_gate_bwd_apply': [I32, P, I32, P, P, I32, I32, I32, P, I32, I32, P],
+    'dv_gate_mean_bn': [I32, P, I32, P, I32, I32, I32, P, P],
+    'dv_gate_scale_bn': [I32, P, I32, P, P, I32, I32, I32, P],
+    'dv_bn_bwd_reduce_multi_gated': [I32, P, I32, I32, P, P, I32, I32, P, P],
+    'dv_bn_bwd_apply_multi_gated': [I32, P, I32, I32, I32, P, P, I32, I32, P, P],
     'dv_colsum_f32': [P, I32, I32, I32, P, P],
     'dv_l2norm_fwd': [P, I32, I32, F, P, P, P],
     'dv_l2norm_bwd': [P, P, P, I32, I32, P, P],

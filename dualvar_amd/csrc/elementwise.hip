@@ -218,6 +218,25 @@ __device__ __forceinline__ void load_params(const float* __restrict__ p, int c0,
   }
 }
 
+// The BatchNorm's affine map, ONE expression for bn_apply, the DV_MASK_FROM_X sites and the gate-on-load kernels: whoever
+// rebuilds an activation (or its sign) from x gets the bits the forward stored.  (The library is built with -ffp-contract=off:
+// a product and a sum, two roundings, wherever this is inlined.)
+__device__ __forceinline__ float bn_affine(float x, float sc, float sh) { return x * sc + sh; }
+// a value as it comes back from a tensor of type T it was stored to (bf16: rounded; fp32: itself)
+template <typename T>
+__device__ __forceinline__ float as_stored(float v) { return DT<T>::to_f(DT<T>::from_f(v)); }
+// relu(bn(x)) as bn_apply (DV_RELU, no residual) leaves it in memory
+template <typename T>
+__device__ __forceinline__ float bn_relu_stored(float x, float sc, float sh) { return as_stored<T>(fmaxf(bn_affine(x, sc, sh), 0.f)); }
+// the gradient behind a self-gating scale, dy*g + dmean/S, as rowscale_kernel<T, 1> forms it (and, as_stored, leaves it)
+__device__ __forceinline__ float gate_grad(float dy, float g, float dm, float invS) { return dy * g + dm * invS; }
+
+// Self gating folded into the BatchNorm backward of the gated members: g / dm point at the item's first column of the level's
+// [N][ldg] gate tables (nullptr: this item is not gated -- block-uniform, a launch may mix both kinds), fS divides a row by S.
+struct GateOnLoad {
+  const float* g; const float* dm; FastDiv fS; int ldg; float invS;
+};
+
 template <typename T>
 __device__ __forceinline__ void bn_apply_body(const T* __restrict__ x, int ldx, const float* __restrict__ scale,
                                               const float* __restrict__ shift, const T* __restrict__ res, int ldr,
@@ -235,7 +254,7 @@ __device__ __forceinline__ void bn_apply_body(const T* __restrict__ x, int ldx, 
     load_params<V>(shift, c0, sh);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      float o = v[e] * sc[e] + sh[e];
+      float o = bn_affine(v[e], sc[e], sh[e]);
       if (res) o += r[e];
       if (flags & DV_RELU) o = fmaxf(o, 0.f);
       v[e] = (c0 + e < C) ? o : 0.f;
@@ -278,7 +297,7 @@ __global__ void bn_apply_multi_kernel(const dv_bn_item* __restrict__ items, int 
 // (row, c0) -> V values for NS sums.  Result: out[s][c] for this block (written by the caller's lambda).
 struct NoPre { __device__ __forceinline__ void operator()(int) const {} };
 
-template <int V, int NS, typename F, typename W, typename Pre = NoPre>
+template <int V, int NS, int UNROLL = 0, typename F, typename W, typename Pre = NoPre>
 __device__ __forceinline__ void column_reduce(int64_t r_begin, int64_t r_end, int CP, F f, W write, Pre pre = Pre()) {
   __shared__ float lds[kThreads * V * NS > 4096 ? 4096 : kThreads * V * NS];
   const int CV = CP / V;
@@ -300,7 +319,7 @@ __device__ __forceinline__ void column_reduce(int64_t r_begin, int64_t r_end, in
       // (unroll 4 for bf16 needed > 128 VGPRs: with the 1 024-thread default bound the reduce kernels spilled 112 B per lane and
       // their traffic went 1.08x -> 1.55x algorithmic -- round 3's bf16 regression; tests/test_abi_and_host.py now fails on
       // any kernel with scratch.)
-#pragma unroll(V == 4 ? 4 : 2)
+#pragma unroll(UNROLL ? UNROLL : V == 4 ? 4 : 2)
       for (int64_t r = r_begin + my_rg; r < r_end; r += rg) f(r, (cvb + my_cv) * V, acc);
     }
     __syncthreads();
@@ -425,14 +444,14 @@ __device__ __forceinline__ void ordered_fold(float* __restrict__ ws, uint32_t bi
   if (threadIdx.x == 0) __hip_atomic_store(tick + ngrp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <typename T>
+template <typename T, bool GATE = false>
 __device__ __forceinline__ void bn_bwd_reduce_body(const T* __restrict__ dy, int lddy, const T* __restrict__ y, int ldy,
                                                    const T* __restrict__ x, int ldx, const float* __restrict__ mean,
                                                    const float* __restrict__ invstd, int64_t M, int C, int CP, int flags,
                                                    int64_t rows_per_block, float* __restrict__ sums_all, int n_rep,
                                                    uint32_t bid, const float* __restrict__ scale = nullptr,
                                                    const float* __restrict__ shift = nullptr, float* __restrict__ ws = nullptr,
-                                                   uint32_t nblk = 0) {
+                                                   uint32_t nblk = 0, const GateOnLoad& ga = GateOnLoad()) {
   constexpr int V = DT<T>::VEC;
   // Ordered mode (ws != nullptr): the block stores its partial sums to ws[bid][2][CP] (sc1 stores); the block that takes the
   // last ticket (ordered_fold: drained stores -> ticket -> sc1 loads) adds the partials in block order into sums_all[0] -- no
@@ -446,16 +465,27 @@ __device__ __forceinline__ void bn_bwd_reduce_body(const T* __restrict__ dy, int
   // (same expression, same rounding), so the output tensor is not read at all: 2 tensor reads instead of 3
   const bool fromx = mask && (flags & DV_MASK_FROM_X);
   float mu[V], is[V], sc[V], sh[V];
-  column_reduce<V, 2>(
+  // (gated: half the rows in flight -- two more vectors per row -- which keeps the registers at the plain kernel's occupancy;
+  // measured, 2 / 3 / 4 rows in flight run the step's gated reduces in 601 / 611 / 611 us)
+  column_reduce<V, 2, GATE ? (V == 4 ? 2 : 1) : 0>(
       r0, r1, CP,
       [&](int64_t r, int c0, float(&acc)[2][V]) {
-        float g[V], yy[V], xx[V];
+        float g[V], yy[V], xx[V], gv[V], dv[V];
+        if (GATE && ga.g) {                        // the gate's row first: these loads hit in L1 / L2 and come back at once; issued
+          const size_t go = (size_t)fd_div((uint32_t)r, ga.fS) * ga.ldg;      // behind dy and x they cost 15 us more per step
+          load_params<V>(ga.g + go, c0, gv);
+          load_params<V>(ga.dm + go, c0, dv);
+        }
         Pack16<T>::load(dy + r * lddy + c0, g);
         if (mask && !fromx) Pack16<T>::load(y + r * ldy + c0, yy);
         Pack16<T>::load(x + r * ldx + c0, xx);
+        if (GATE && ga.g) {                        // dL/dy behind the gate, as gate_bwd_apply would have left it in dy
+#pragma unroll
+          for (int e = 0; e < V; ++e) g[e] = as_stored<T>(gate_grad(g[e], gv[e], dv[e], ga.invS));
+        }
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-          const float act = fromx ? xx[e] * sc[e] + sh[e] : yy[e];
+          const float act = fromx ? bn_affine(xx[e], sc[e], sh[e]) : yy[e];
           float gg = (mask && !(act > 0.f)) ? 0.f : g[e];
           acc[0][e] += gg;
           acc[1][e] += gg * (xx[e] - mu[e]) * is[e];
@@ -497,6 +527,33 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_multi_kernel(const dv_
                         it.C, CP, it.bwd_flags, rpb, it.sums, it.n_rep, bid, it.scale, it.shift, it.red_ws, nblk);
 }
 
+__device__ __forceinline__ GateOnLoad gate_of_item(const int32_t* __restrict__ gate_off, int i, const float* g, const float* dm,
+                                                   const FastDiv& fS, int ldg) {
+  const int off = gate_off[i];
+  GateOnLoad ga;
+  ga.g = off >= 0 ? g + off : nullptr;
+  ga.dm = off >= 0 ? dm + off : nullptr;
+  ga.fS = fS; ga.ldg = ldg; ga.invS = 1.f / (float)fS.d;
+  return ga;
+}
+
+// the same launch for a group that holds gated members (GateGroupOp, engine.FUSE_GATE): an instantiation of its own, so the
+// plain kernel above keeps its registers
+template <typename T>
+__global__ __launch_bounds__(kThreads) void bn_bwd_reduce_multi_gated_kernel(const dv_bn_item* __restrict__ items, int n,
+                                                                            const int32_t* __restrict__ gate_off,
+                                                                            const float* __restrict__ g, const float* __restrict__ dm,
+                                                                            FastDiv fS, int ldg) {
+  uint32_t bid = blockIdx.x, nblk;
+  const int i = find_item(n, bid, nblk, [&](int k) { return items[k].blk_red; });
+  const dv_bn_item& it = items[i];
+  const int CP = (it.C + 7) & ~7;
+  const int64_t rpb = (it.M + nblk - 1) / nblk;
+  bn_bwd_reduce_body<T, true>((const T*)it.dy, it.lddy, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean, it.invstd, it.M,
+                              it.C, CP, it.bwd_flags, rpb, it.sums, it.n_rep, bid, it.scale, it.shift, it.red_ws, nblk,
+                              gate_of_item(gate_off, i, g, dm, fS, ldg));
+}
+
 // partials [n_blocks][W] -> out[W] (+=): 32 columns x 8 row lanes per block
 __global__ void reduce_rows_kernel(const float* __restrict__ part, int64_t ld, int n_rows, int Wd, float* __restrict__ out,
                                    int accumulate) {
@@ -526,7 +583,7 @@ __global__ void reduce_rows_kernel(const float* __restrict__ part, int64_t ld, i
 
 // dx = k1[c]*g + k2[c]*x + k3[c] with  k1 = gamma*invstd, k2 = -k1*invstd*sgx/M, k3 = -k1*sg/M - k2*mean
 // (sg, sgx = global sums of g and g*xhat).  The table is built once per block in LDS.
-template <typename T>
+template <typename T, bool GATE = false>
 __device__ __forceinline__ void bn_bwd_apply_body(const T* __restrict__ dy, int lddy, const T* __restrict__ y, int ldy,
                                                   const T* __restrict__ x, int ldx, const float* __restrict__ mean,
                                                   const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -535,7 +592,8 @@ __device__ __forceinline__ void bn_bwd_apply_body(const T* __restrict__ dy, int 
                                                   int lddx, T* __restrict__ dres, int lddres, uint32_t total, int C,
                                                   int CP, const FastDiv& fcv, int flags, uint32_t bid, uint32_t nblk,
                                                   const float* __restrict__ scale = nullptr,
-                                                  const float* __restrict__ shift = nullptr) {
+                                                  const float* __restrict__ shift = nullptr,
+                                                  const GateOnLoad& ga = GateOnLoad()) {
   constexpr int V = DT<T>::VEC;
   extern __shared__ __attribute__((aligned(16))) float coef[];      // [3][CP] (+ [2][CP] scale, shift with DV_MASK_FROM_X)
   const bool fromx = !(flags & DV_NO_RELU_MASK) && (flags & DV_MASK_FROM_X);
@@ -570,13 +628,21 @@ __device__ __forceinline__ void bn_bwd_apply_body(const T* __restrict__ dy, int 
     if (mask && !fromx) Pack16<T>::load(y + (size_t)row * ldy + c0, yy);
     Pack16<T>::load(x + (size_t)row * ldx + c0, xx);
     if (dres && (flags & DV_ACCUM)) Pack16<T>::load(dres + (size_t)row * lddres + c0, ro);
+    if (GATE && ga.g) {                            // (as in bn_bwd_reduce_body: the same dL/dy in both passes)
+      const size_t go = (size_t)fd_div(row, ga.fS) * ga.ldg;
+      float gv[V], dv[V];
+      load_params<V>(ga.g + go, c0, gv);
+      load_params<V>(ga.dm + go, c0, dv);
+#pragma unroll
+      for (int e = 0; e < V; ++e) g[e] = as_stored<T>(gate_grad(g[e], gv[e], dv[e], ga.invS));
+    }
     load_params<V>(coef, c0, k1);
     load_params<V>(coef + CP, c0, k2);
     load_params<V>(coef + 2 * CP, c0, k3);
     if (fromx) { load_params<V>(coef + 3 * CP, c0, sc); load_params<V>(coef + 4 * CP, c0, sh); }
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      const float act = fromx ? xx[e] * sc[e] + sh[e] : yy[e];     // the forward's expression: same mask bit for bit
+      const float act = fromx ? bn_affine(xx[e], sc[e], sh[e]) : yy[e];     // the forward's expression: same mask bit for bit
       const float gg = (mask && !(act > 0.f)) ? 0.f : g[e];
       o[e] = k1[e] * gg + k2[e] * xx[e] + k3[e];
       // (pad lanes [C, CP) of dres are written as zeros, whatever dy / y / dres held there, as dx's are through k1..k3 = 0)
@@ -610,6 +676,21 @@ __global__ void bn_bwd_apply_multi_kernel(const dv_bn_item* __restrict__ items, 
                        it.gamma, it.sums, it.n_rep, it.inv_count, it.dparam_scale, it.dgamma, it.dbeta, (T*)it.dx, it.lddx,
                        (T*)it.dres, it.lddres, (uint32_t)(it.M * (CP / V)), it.C, CP, fastdiv_dev((uint32_t)(CP / V)),
                        it.bwd_flags, bid, nblk, it.scale, it.shift);
+}
+
+template <typename T>
+__global__ void bn_bwd_apply_multi_gated_kernel(const dv_bn_item* __restrict__ items, int n, const int32_t* __restrict__ gate_off,
+                                                const float* __restrict__ g, const float* __restrict__ dm, FastDiv fS, int ldg) {
+  uint32_t bid = blockIdx.x, nblk;
+  const int i = find_item(n, bid, nblk, [&](int k) { return items[k].blk_bapply; });
+  const dv_bn_item& it = items[i];
+  constexpr int V = DT<T>::VEC;
+  const int CP = (it.C + 7) & ~7;
+  bn_bwd_apply_body<T, true>((const T*)it.dy, it.lddy, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean, it.invstd,
+                             it.gamma, it.sums, it.n_rep, it.inv_count, it.dparam_scale, it.dgamma, it.dbeta, (T*)it.dx,
+                             it.lddx, (T*)it.dres, it.lddres, (uint32_t)(it.M * (CP / V)), it.C, CP,
+                             fastdiv_dev((uint32_t)(CP / V)), it.bwd_flags, bid, nblk, it.scale, it.shift,
+                             gate_of_item(gate_off, i, g, dm, fS, ldg));
 }
 
 // ------------------------------------------------------------------ MaxPool3d
@@ -822,7 +903,7 @@ __global__ __launch_bounds__(256) void bn_apply_maxpool_kernel(PoolArgs a, const
           Pack16<T>::load(x + ((int64_t)((n * a.Ti + t) * a.Hi + hh) * a.Wi + w) * a.ldx + c0, v);
 #pragma unroll
           for (int e = 0; e < V; ++e) {
-            const float yv = DT<T>::to_f(DT<T>::from_f(fmaxf(v[e] * sc[e] + sh[e], 0.f)));     // what bn_apply stores
+            const float yv = bn_relu_stored<T>(v[e], sc[e], sh[e]);     // what bn_apply stores
             if (first || yv > best[e] || yv != yv) { best[e] = yv; bi[e] = tap; }
           }
           first = false;
@@ -895,7 +976,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_maxpool_kernel(PoolArg
         Pack16<T>::load(x + r * a.ldx + c0, xx);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-          const float act = xx[e] * sc[e] + sh[e];
+          const float act = bn_affine(xx[e], sc[e], sh[e]);
           const float gg = !(act > 0.f) ? 0.f : g[e];
           acc[0][e] += gg;
           acc[1][e] += gg * (xx[e] - mu[e]) * is[e];
@@ -962,7 +1043,7 @@ __global__ void bn_bwd_apply_maxpool_kernel(PoolArgs a, const T* __restrict__ dy
     load_params<V>(coef + 4 * CP, c0, sh);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      const float act = xx[e] * sc[e] + sh[e];
+      const float act = bn_affine(xx[e], sc[e], sh[e]);
       const float gg = !(act > 0.f) ? 0.f : g[e];
       o[e] = k1[e] * gg + k2[e] * xx[e] + k3[e];
     }
@@ -1362,6 +1443,105 @@ __global__ void gate_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const
       });
 }
 
+// Self gating with the BatchNorm + ReLU in front of it applied on load (engine.FUSE_GATE): the un-gated concat is never written.
+// The gated members of a level are `items` (x, ldx, scale, shift, C; y, ldy for the scale), gate_off[k] is member k's first column
+// in the level's [N][Ct] tables (-1: not a gated member, skipped); widths and offsets are multiples of 8 channels, so a 16-byte
+// channel vector never straddles two members.
+//
+// gate_mean_bn_kernel is spatial_mean_kernel over the VIRTUAL concat: same grid, same channel chunks, same column_reduce
+// decomposition as the launch over the real concat buffer -- the same additions in the same order, applied to the values
+// bn_apply_multi would have stored.
+template <typename T>
+__global__ void gate_mean_bn_kernel(const dv_bn_item* __restrict__ items, int n, const int32_t* __restrict__ gate_off, int S, int Ct,
+                                    int ccv, float* __restrict__ out) {
+  constexpr int V = DT<T>::VEC;
+  const int nn = blockIdx.x;
+  const float inv = 1.f / (float)S;
+  const int cb = (int)blockIdx.y * ccv * V, cpl = min(ccv * V, Ct - cb);
+  if (cpl <= 0) return;
+  const T* xp;                                     // the owning member's x at this thread's channel vector
+  int ldx = 0;
+  float sc[V], sh[V];
+  column_reduce<V, 1>(
+      (int64_t)nn * S, (int64_t)(nn + 1) * S, cpl,
+      [&](int64_t r, int c0, float(&acc)[1][V]) {
+        float v[V];
+        Pack16<T>::load(xp + r * ldx, v);
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[0][e] += bn_relu_stored<T>(v[e], sc[e], sh[e]);
+      },
+      [&](int c0, float(&acc)[1][V]) {
+#pragma unroll
+        for (int e = 0; e < V; ++e)
+          if (cb + c0 + e < Ct) out[(size_t)nn * Ct + cb + c0 + e] = acc[0][e] * inv;
+      },
+      [&](int c0) {
+        const int c = cb + c0;
+        // (a vector no member owns -- the members do not tile [0, Ct) -- reads member 0 with a zero map: relu(0) = 0.  No test of
+        // xp in the row loop: a branch there keeps the unrolled rows' loads from being in flight together, 12 -> 24 us.)
+        xp = (const T*)items[0].x;
+        ldx = items[0].ldx;
+#pragma unroll
+        for (int e = 0; e < V; ++e) sc[e] = sh[e] = 0.f;
+        for (int k = 0; k < n; ++k) {
+          const int off = gate_off[k];
+          if (off >= 0 && c >= off && c < off + items[k].C) {
+            xp = (const T*)items[k].x + (c - off);
+            ldx = items[k].ldx;
+            load_params<V>(items[k].scale, c - off, sc);
+            load_params<V>(items[k].shift, c - off, sh);
+          }
+        }
+      });
+}
+
+// blocks of one member in gate_scale_bn_kernel: four vectors per thread, at most 1024 blocks.  (bn_apply_multi's one vector per
+// thread puts three dependent table reads in front of every 16 bytes moved: the 12 544-row levels took 19 us against
+// rowscale's 12.)
+constexpr uint32_t kGateScaleMaxBlocks = 1024;
+__host__ __device__ inline uint32_t gate_scale_blocks(uint32_t vecs) {
+  const uint32_t b = (vecs + 1023u) / 1024u;
+  return b < 1u ? 1u : b > kGateScaleMaxBlocks ? kGateScaleMaxBlocks : b;
+}
+
+// y = relu(x*scale + shift) * g[n][off + c] into the members' concat slices: bn_apply_multi and rowscale_kernel<T, 0> in one
+// pass.  Every block derives the members' block counts from the table (n <= 8), so the host needs no prefix.
+template <typename T>
+__global__ void gate_scale_bn_kernel(const dv_bn_item* __restrict__ items, int n, const int32_t* __restrict__ gate_off,
+                                     const float* __restrict__ g, uint32_t M, FastDiv fS, int ldg) {
+  constexpr int V = DT<T>::VEC;
+  uint32_t bid = blockIdx.x, nblk = 0, start = 0;
+  int i = -1;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const uint32_t b = (k < n && gate_off[k] >= 0) ? gate_scale_blocks(M * (uint32_t)(items[k].C / V)) : 0u;
+    if (i < 0 && bid < start + b) { i = k; nblk = b; bid -= start; }
+    start += b;
+  }
+  if (i < 0) return;                               // (the host's grid is an upper bound of the sum)
+  const dv_bn_item& it = items[i];
+  const T* __restrict__ x = (const T*)it.x;
+  T* __restrict__ y = (T*)it.y;
+  const int ldx = it.ldx, ldy = it.ldy;
+  const float* __restrict__ scale = it.scale;
+  const float* __restrict__ shift = it.shift;
+  const float* __restrict__ gi = g + gate_off[i];
+  const FastDiv fcv = fastdiv_dev((uint32_t)(it.C / V));
+  const uint32_t CV = fcv.d, total = M * CV;
+  for (uint32_t j = bid * blockDim.x + threadIdx.x; j < total; j += nblk * blockDim.x) {
+    const uint32_t row = fd_div(j, fcv);
+    const int c0 = (int)(j - row * CV) * V;
+    float v[V], sc[V], sh[V], gv[V];
+    Pack16<T>::load(x + (size_t)row * ldx + c0, v);
+    load_params<V>(scale, c0, sc);
+    load_params<V>(shift, c0, sh);
+    load_params<V>(gi + (size_t)fd_div(row, fS) * ldg, c0, gv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) v[e] = bn_relu_stored<T>(v[e], sc[e], sh[e]) * gv[e];
+    Pack16<T>::store(y + (size_t)row * ldy + c0, v);
+  }
+}
+
 // MODE 0: y = x*g[n][c]          (gate_scale)
 // MODE 1: dx (+)= dy*g + dmean/S  (gate_bwd_apply)
 // MODE 2: dx (+)= dout[n][c]/S    (spatial_mean_bwd)
@@ -1396,7 +1576,7 @@ __global__ void rowscale_kernel(const T* __restrict__ a, int lda, const float* _
     for (int e = 0; e < V; ++e) {
       float r;
       if (MODE == 0) r = v[e] * gv[e];
-      else if (MODE == 1) r = v[e] * gv[e] + dv[e] * invS;
+      else if (MODE == 1) r = gate_grad(v[e], gv[e], dv[e], invS);
       else r = dv[e] * invS;
       if (!vec && c0 + e >= C) r = 0.f;
       v[e] = accumulate ? old[e] + r : r;
@@ -2044,6 +2224,68 @@ extern "C" int dv_gate_bwd_apply(int32_t dtype, const void* dy, int32_t lddy, co
                        (const T*)dy, lddy, g, dmean, (uint32_t)total, make_fastdiv((uint32_t)(CP / V)),
                        make_fastdiv((uint32_t)S), C, (T*)dx, lddx, (flags & DV_ACCUM) ? 1 : 0);
   });
+  return dv_launch_status();
+}
+
+static int gate_fold_args(const dv_bn_item* items, int32_t n, const int32_t* gate_off, int32_t N, int32_t S, int32_t Ct) {
+  if (!items || !gate_off || n <= 0 || n > 8 || N <= 0 || S <= 0 || Ct <= 0 || Ct % 8) return DV_EINVAL;
+  if ((int64_t)N * S * (Ct / 4) >= (1ll << 31)) return DV_EINVAL;
+  return DV_OK;
+}
+
+extern "C" int dv_gate_mean_bn(int32_t dtype, const dv_bn_item* items, int32_t n, const int32_t* gate_off, int32_t N, int32_t S,
+                               int32_t Ct, float* mean, void* stream) {
+  if (int rc = gate_fold_args(items, n, gate_off, N, S, Ct)) return rc;
+  if (!mean) return DV_EINVAL;
+  DISPATCH_T(dtype, {
+    const int CV = Ct / DT<T>::VEC, ccv = c_chunk_vecs(N, S, CV);
+    hipLaunchKernelGGL((gate_mean_bn_kernel<T>), dim3(N, (CV + ccv - 1) / ccv), dim3(kThreads), 0, ST(stream), items, n, gate_off,
+                       S, Ct, ccv, mean);
+  });
+  return dv_launch_status();
+}
+
+extern "C" int dv_gate_scale_bn(int32_t dtype, const dv_bn_item* items, int32_t n, const int32_t* gate_off, const float* g,
+                                int32_t N, int32_t S, int32_t Ct, void* stream) {
+  if (int rc = gate_fold_args(items, n, gate_off, N, S, Ct)) return rc;
+  if (!g) return DV_EINVAL;
+  if (!aligned16(g)) return DV_EALIGN;
+  DISPATCH_T(dtype, {
+    const uint32_t M = (uint32_t)N * (uint32_t)S, vecs = M * (uint32_t)(Ct / DT<T>::VEC);
+    // sum_k min(cap, ceil(v_k / 1024)) <= min(cap n, ceil(sum_k v_k / 1024) + n); blocks past the members' sum return at once
+    uint32_t grid = (vecs + 1023u) / 1024u + (uint32_t)n;
+    if (grid > kGateScaleMaxBlocks * (uint32_t)n) grid = kGateScaleMaxBlocks * (uint32_t)n;
+    hipLaunchKernelGGL((gate_scale_bn_kernel<T>), dim3(grid), dim3(kThreads), 0, ST(stream), items, n, gate_off, g, M,
+                       make_fastdiv((uint32_t)S), Ct);
+  });
+  return dv_launch_status();
+}
+
+static int gate_bwd_args(const float* g, const float* dmean, int32_t S, int32_t ldg, const int32_t* gate_off) {
+  if (!g || !dmean || !gate_off || S <= 0 || ldg <= 0 || ldg % 8) return DV_EINVAL;
+  if (!aligned16(g) || !aligned16(dmean)) return DV_EALIGN;
+  return DV_OK;
+}
+
+extern "C" int dv_bn_bwd_reduce_multi_gated(int32_t dtype, const dv_bn_item* items, int32_t n, int32_t total_blocks, const float* g,
+                                            const float* dmean, int32_t S, int32_t ldg, const int32_t* gate_off, void* stream) {
+  if (!items || n <= 0 || total_blocks <= 0) return DV_EINVAL;
+  if (int rc = gate_bwd_args(g, dmean, S, ldg, gate_off)) return rc;
+  DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_reduce_multi_gated_kernel<T>), dim3(total_blocks), dim3(kThreads), 0, ST(stream), items,
+                                       n, gate_off, g, dmean, make_fastdiv((uint32_t)S), ldg));
+  return dv_launch_status();
+}
+
+extern "C" int dv_bn_bwd_apply_multi_gated(int32_t dtype, const dv_bn_item* items, int32_t n, int32_t total_blocks, int32_t max_c,
+                                           const float* g, const float* dmean, int32_t S, int32_t ldg, const int32_t* gate_off,
+                                           void* stream) {
+  if (!items || n <= 0 || total_blocks <= 0 || max_c <= 0) return DV_EINVAL;
+  if (int rc = gate_bwd_args(g, dmean, S, ldg, gate_off)) return rc;
+  const int CP = cp8(max_c);
+  if (5 * CP * 4 > 60 * 1024) return DV_EUNSUPPORTED;
+  DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_multi_gated_kernel<T>), dim3(total_blocks), dim3(kThreads),
+                                       5 * CP * sizeof(float), ST(stream), items, n, gate_off, g, dmean, make_fastdiv((uint32_t)S),
+                                       ldg));
   return dv_launch_status();
 }
 

@@ -81,6 +81,13 @@ FUSE_BN_WGRAD = os.environ.get('DUALVAR_FUSE_BN_WGRAD', '1') != '0'      # (A/B 
 FUSE_BN_IN = os.environ.get('DUALVAR_FUSE_BN_IN', '1') != '0'         # (A/B switch; tests monkeypatch the module attribute)
 
 
+# S3D-G self gating folded into the BatchNorm passes around it: the gate's mean and scale apply relu(bn(x)) of the gated members on
+# load (dv_gate_mean_bn / dv_gate_scale_bn: the un-gated concat is never written), and the members' BatchNorm backward forms
+# dy*g + dmean/S where it loads dy (dv_bn_bwd_*_multi_gated: the gated gradient is never written).  4 of the 14 passes over a
+# level's concat buffer and 2 launches per level less, same bits (tests/test_gate_fold_gpu.py).
+FUSE_GATE = os.environ.get('DUALVAR_FUSE_GATE', '1') != '0'        # (A/B switch; tests monkeypatch the module attribute)
+
+
 class Slot:
     __slots__ = ('tensor', 'kind', 'off', 'size', 'Cout', 'Cin', 'taps', 'cin_pitch', 'cout_pitch', 'wd_off',
                  'shape', 'strides', 'parts', 'kw_store', 'w3_off', 'wd3_off')
@@ -732,6 +739,10 @@ class Plan:
                 if d.ldy != m.y.grad.ld or not self.lib.dv_conv3d_wgrad_bn_ok(C.byref(d)):
                     continue
                 cop.bn_apply, m.apply_fused = m, True
+        if self.training and FUSE_GATE:
+            for op in self.ops:
+                if isinstance(op, GateGroupOp):
+                    op.try_fuse()
         # scratch of the deterministic weight gradients (row-split partial tiles): ONE buffer per plan, sized for the
         # largest layer -- the plan's weight gradients all run on one stream (the side stream), each followed by its
         # reduce, so they can share it
@@ -1092,6 +1103,7 @@ class BNMember:
         self.fused_conv = None       # the ConvOp that applies this BatchNorm while it stages x (Plan.finalize, FUSE_BN_IN)
         self.reduce_fused = False    # the backward reduce runs in the epilogue of the consuming conv's data gradient
         self.apply_fused = False     # the backward apply runs inside the producing conv's weight gradient (dv_conv3d_wgrad_bn)
+        self.gate = None             # (GateGroupOp, column offset): the gate applies this BatchNorm on load (FUSE_GATE)
         self.mask_from_x = bool(relu) and residual is None
         self.sums_off = plan.reserve_zero(BN_REPLICAS * 2 * self.CP) if plan.with_grad else 0
         self.sums_len = BN_REPLICAS * 2 * self.CP
@@ -1145,7 +1157,7 @@ class BNGroupOp(Op):
             it.fwd_flags = DV_RELU if m.relu else 0
             total = m.M * (m.CP // V)
             ends[0] += m.C
-            ends[1] += 0 if m.fused_conv is not None else max(1, min(4096, (total + 255) // 256))
+            ends[1] += 0 if (m.fused_conv is not None or m.gate is not None) else max(1, min(4096, (total + 255) // 256))
             it.blk_stats, it.blk_apply = ends[0], ends[1]
             if p.with_grad:
                 dres = res.grad if (res is not None and res.grad is not None) else None
@@ -1176,11 +1188,27 @@ class BNGroupOp(Op):
         self._fin_multi = Launch('bn_finalize_multi', 'bn_finalize_multi', lib.dv_bn_finalize_multi,
                                  (tab, n, sum((m.C + 127) // 128 for m in self.members), self.local.data_ptr(),
                                   self.gathered.data_ptr(), R, self.width))
-        if p.with_grad:
+        gated = [m for m in self.members if m.gate is not None]
+        if p.with_grad and gated:
+            # the group holds gated members: the `+gate` instantiations take dL/dy of those as dy*g + dmean/S on load (the
+            # other members of the launch run as before); they also read the members' columns of the two [N][Ct] tables
+            gop = gated[0].gate[0]
+            assert all(m.gate[0] is gop and not m.reduce_fused and not m.apply_fused for m in gated)
+            self._gate_off = torch.tensor([m.gate[1] if m.gate is not None else -1 for m in self.members],
+                                          dtype=torch.int32).to(p.device)
+            p.bytes += self._gate_off.numel() * 4
+            gargs = (gop.g.data_ptr(), gop.dmean.data_ptr(), gop.cat.S, gop.cat.C, self._gate_off.data_ptr())
+            gbytes = sum(8 * gop.cat.N * m.C for m in gated)
+            b_red = [Launch('bn_bwd_reduce_multi', 'bn_bwd_reduce_multi<%s>+gate' % dt, lib.dv_bn_bwd_reduce_multi_gated,
+                            (p.dtype, tab, n, ends[2]) + gargs, tot(b_red, 'bytes') + gbytes)]
+            b_app = [Launch('bn_bwd_apply_multi', 'bn_bwd_apply_multi<%s>+gate' % dt, lib.dv_bn_bwd_apply_multi_gated,
+                            (p.dtype, tab, n, ends[3], max(m.C for m in self.members)) + gargs, tot(b_app, 'bytes') + gbytes)]
+        elif p.with_grad:
             b_red = [Launch('bn_bwd_reduce_multi', 'bn_bwd_reduce_multi<%s>' % dt, lib.dv_bn_bwd_reduce_multi,
                             (p.dtype, tab, n, ends[2]), tot(b_red, 'bytes'))] if ends[2] else []
             b_app = [Launch('bn_bwd_apply_multi', 'bn_bwd_apply_multi<%s>' % dt, lib.dv_bn_bwd_apply_multi,
                             (p.dtype, tab, n, ends[3], max(m.C for m in self.members)), tot(b_app, 'bytes'))] if ends[3] else []
+        if p.with_grad:
             if b_app:
                 b_app[0].gend = _gend(*[st.slot(t) for m in self.members for t in (m.bn.weight, m.bn.bias)])
         return f_red, f_app, b_red, b_app
@@ -1237,7 +1265,7 @@ class BNGroupOp(Op):
                 f_fin.append(Launch('bn_finalize', 'bn_finalize', lib.dv_bn_finalize,
                                     (self.gathered.data_ptr() + 4 * m.loff, R, self.width, Cn, st.w_master(gs), st.w_master(bs),
                                      eps, mom, rm, rv) + outs))
-            if m.fused_conv is None:         # (else: the consuming conv applies it on load; y is never written)
+            if m.fused_conv is None and m.gate is None:   # (else: the consuming conv / the gate applies it on load)
                 f_app.append(Launch('bn_apply', 'bn_apply<%s>' % dt, lib.dv_bn_apply,
                                     (p.dtype, x.ptr, x.ld, m.scale.data_ptr(), m.shift.data_ptr(),
                                      res.ptr if res is not None else 0, res.ld if res is not None else 0, y.ptr, y.ld, M, Cn,
@@ -1386,7 +1414,11 @@ class GateGroupOp(Op):
         cat[n,s,c] *= sigmoid(fc_i(mean_s cat[n,:,slice_i]))[c]
     Three launches forward (mean, the four FCs as ONE grouped fp32 MFMA GEMM with bias+sigmoid epilogue, scale) and
     four backward.  The un-gated activations are not kept: the gate is positive, so the ReLU mask of the producing
-    BatchNorm is unchanged, and sum_s dy*y = (sum_s dy*out)/g."""
+    BatchNorm is unchanged, and sum_s dy*y = (sum_s dy*out)/g.
+
+    FUSE_GATE (try_fuse): when the four slices are the outputs of BatchNorm + ReLU members, the mean and the scale read the
+    members' conv outputs and apply the BatchNorm on load, and the members' BatchNorm backward forms the gated gradient on
+    load: the un-gated concat and the gated gradient are never written (mean_bn, fc, scale_bn forward; three backward)."""
 
     def __init__(self, plan, fcs, cat):
         super().__init__(plan)
@@ -1396,6 +1428,29 @@ class GateGroupOp(Op):
         self.mean, self.g = plan.f32(N, Ct), plan.f32(N, Ct)
         if plan.with_grad:
             self.dpre, self.dmean = plan.f32(N, Ct), plan.f32(N, Ct)
+        self.fused = None            # the BNMembers behind the four slices, in fcs order (try_fuse)
+
+    def try_fuse(self):
+        """Plan.finalize, after the other fusions are decided: take over the forward apply of the BatchNorms that write the
+        gated slices, if every slice has one and none of them is applied or differentiated somewhere else."""
+        p, cat = self.plan, self.cat
+        owners = {}
+        for op in p.ops:
+            if isinstance(op, BNGroupOp) and len(op.members) > 1:
+                for m in op.members:
+                    if m.y.buf is cat.buf and m.y.rows == cat.rows:
+                        owners[(m.y.off - cat.off, m.C)] = m
+        ms = [owners.get((off, w)) for _, off, w in self.fcs]
+        for m in ms:
+            if (m is None or not m.relu or m.res is not None or m.conv_bias is not None or m.fused_pool is not None
+                    or m.fused_conv is not None or m.reduce_fused or m.apply_fused or m.gate is not None or m.C % 8
+                    or m.M != cat.rows or (p.with_grad and not m.mask_from_x)):
+                return
+        if len(ms) > 8 or cat.rows * (cat.C // 4) >= (1 << 31):
+            return
+        self.fused = ms
+        for m, (_, off, _) in zip(ms, self.fcs):
+            m.gate = (self, off)
 
     def _table(self, descs):
         arr = (L.GemmDesc * len(descs))()
@@ -1437,6 +1492,22 @@ class GateGroupOp(Op):
                     sum(w * w * 4 for _, _, w in self.fcs), sum(2 * N * w * w for _, _, w in self.fcs)),
              Launch('gate_scale', 'rowscale<%s,0>' % dt, lib.dv_gate_scale,
                     (p.dtype, cat.ptr, cat.ld, g, N, S, Ct, cat.ptr, cat.ld), 2 * _abytes(cat))]
+        if self.fused:
+            # the members' own table (only what the two kernels read) and their first columns in mean / g
+            arr = (L.BnItem * len(self.fused))()
+            for it, m in zip(arr, self.fused):
+                it.x, it.ldx, it.y, it.ldy = m.x.ptr, m.x.ld, m.y.ptr, m.y.ld
+                it.scale, it.shift = m.scale.data_ptr(), m.shift.data_ptr()
+                it.M, it.C, it.fwd_flags = m.M, m.C, DV_RELU
+            self._items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(p.device)
+            self._gate_off = torch.tensor([off for _, off, _ in self.fcs], dtype=torch.int32).to(p.device)
+            p.bytes += self._items.numel() + 4 * self._gate_off.numel()
+            tab, goff, nm = self._items.data_ptr(), self._gate_off.data_ptr(), len(self.fused)
+            xbytes = sum(_abytes(m.x) for m in self.fused)
+            f[0] = Launch('gate_mean_bn', 'gate_mean_bn<%s>' % dt, lib.dv_gate_mean_bn,
+                          (p.dtype, tab, nm, goff, N, S, Ct, mean), xbytes)
+            f[2] = Launch('gate_scale_bn', 'gate_scale_bn<%s>' % dt, lib.dv_gate_scale_bn,
+                          (p.dtype, tab, nm, goff, g, N, S, Ct), xbytes + _abytes(cat) + 4 * N * Ct)
         b = []
         if p.with_grad:
             dy = cat.grad
@@ -1450,6 +1521,8 @@ class GateGroupOp(Op):
                         (p.dtype, dy.ptr, dy.ld, g, self.dmean.data_ptr(), N, S, Ct, dy.ptr, dy.ld, 0), 2 * _abytes(cat))]
             b[1].gend = _gend(*[st.slot(fc.weight) for fc, _, _ in self.fcs])
             b[2].gend = _gend(*[st.slot(fc.bias) for fc, _, _ in self.fcs])
+            if self.fused:
+                del b[3]             # (the members' BatchNorm backward forms dy*g + dmean/S on load: BNGroupOp._multi)
         return f, b
 
 

@@ -505,6 +505,37 @@ int dv_gate_bwd_reduce(int32_t dtype, const void* dy, int32_t lddy, const void* 
 int dv_gate_bwd_apply(int32_t dtype, const void* dy, int32_t lddy, const float* g, const float* dmean,
                       int32_t N, int32_t S, int32_t C, void* dx, int32_t lddx, int32_t flags, void* stream);
 
+/* Self gating folded into the BatchNorm passes around it (engine.FUSE_GATE).  The gated members of an Inception level are
+ * BatchNorm + ReLU layers that write disjoint channel slices of one concat buffer [N*S][>= Ct]; the un-gated activation and
+ * the gated gradient exist only so that the next kernel can read them back.  These entry points form them on load instead.
+ * Every result has the bits of the sequence it replaces.
+ *   items    : DEVICE array of dv_bn_item, one per member (n <= 8 for the two forward entries).  Read: x, ldx, scale, shift, C
+ *              (+ y, ldy by dv_gate_scale_bn; everything dv_bn_bwd_*_multi reads by the backward entries).  Members are
+ *              ReLU layers without residual, M = N*S rows, C a multiple of 8, together exactly the columns [0, Ct); the
+ *              forward entries do not read fwd_flags (the ReLU is part of them) and take their grid from N, S and Ct.
+ *   gate_off : DEVICE int32[n]: member k owns columns [gate_off[k], gate_off[k] + C_k) of the level's [N][Ct] fp32 tables
+ *              (mean, g, dmean; 16-byte aligned, offsets multiples of 8); -1 = not a gated member.  The forward entries skip
+ *              such an item; the backward entries treat it exactly as dv_bn_bwd_*_multi do, in the same launch.
+ *   dv_gate_mean_bn  : mean[n][gate_off[k] + c] = mean_s relu(x_k*scale_k + shift_k)
+ *                      == dv_bn_apply_multi (DV_RELU) into the concat, then dv_spatial_mean over it (same grid, same order
+ *                      of additions; in bf16 each activation is rounded to bf16 first, as the stored one was)
+ *   dv_gate_scale_bn : y_k[n][s][c] = relu(x_k*scale_k + shift_k) * g[n][gate_off[k] + c]
+ *                      == dv_bn_apply_multi, then dv_gate_scale in place on the concat
+ *   dv_bn_bwd_reduce_multi_gated / dv_bn_bwd_apply_multi_gated : dv_bn_bwd_reduce_multi / dv_bn_bwd_apply_multi with
+ *                      dL/dy of a gated member taken as dy*g[row / S][.] + dmean[row / S][.]/S where dy is loaded (rounded to
+ *                      bf16 in bf16) == dv_gate_bwd_apply in place on dy, then the plain launches.  dy is left as it was.
+ *                      ldg: row pitch of g and dmean in floats (a multiple of 8).
+ */
+int dv_gate_mean_bn(int32_t dtype, const dv_bn_item* items, int32_t n, const int32_t* gate_off, int32_t N, int32_t S,
+                    int32_t Ct, float* mean, void* stream);
+int dv_gate_scale_bn(int32_t dtype, const dv_bn_item* items, int32_t n, const int32_t* gate_off, const float* g, int32_t N,
+                     int32_t S, int32_t Ct, void* stream);
+int dv_bn_bwd_reduce_multi_gated(int32_t dtype, const dv_bn_item* items, int32_t n, int32_t total_blocks, const float* g,
+                                 const float* dmean, int32_t S, int32_t ldg, const int32_t* gate_off, void* stream);
+int dv_bn_bwd_apply_multi_gated(int32_t dtype, const dv_bn_item* items, int32_t n, int32_t total_blocks, int32_t max_c,
+                                const float* g, const float* dmean, int32_t S, int32_t ldg, const int32_t* gate_off,
+                                void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Small fp32 helpers for the projection heads and parameter gradients.
  *   dv_colsum_f32  : out[c] += sum_r x[r][c]                 (bias gradients)
