@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, 'libdualvar_hip.so')
 ABI_VERSION = 2              # == DV_ABI_VERSION of include/dualvar_hip.h (tests/test_abi_and_host.py compares the two)
 DV_F32, DV_BF16 = 0, 1
 DV_BIAS, DV_RELU, DV_SIGMOID, DV_ACCUM, DV_STATS, DV_NO_RELU_MASK, DV_MASK_FROM_X = 1, 2, 4, 8, 16, 32, 64
+DV_LARS_ADAPT, DV_LARS_DECAY = 1, 2
 DV_W3 = 128                  # conv fwd / dgrad in DV_F32: weights pre-split in fragment order (dv_pack_w3)
 
 _ERR = {-1: 'DV_EINVAL (inconsistent shapes / unsupported parameter)',
@@ -68,6 +69,12 @@ class BnBwd(C.Structure):
 
 class W3Desc(C.Structure):
     _fields_ = [('src_off', C.c_int64), ('dst_off', C.c_int64), ('N', C.c_int32), ('Ktot', C.c_int32)]
+
+
+class LarsSeg(C.Structure):
+    """dv_lars_seg: one trainable tensor of an arena, for dv_lars_norms / dv_lars_step"""
+    _fields_ = [('off', C.c_int64), ('n', C.c_int64), ('flags', C.c_int32), ('first_block', C.c_int32),
+                ('n_blocks', C.c_int32), ('pad', C.c_int32)]
 
 
 class GemmDesc(C.Structure):
@@ -168,6 +175,9 @@ SIGNATURES = {
     'dv_sgd_momentum': [P, P, P, I64, F, F, F, F, I32, P, P],
     'dv_ema': [P, P, I64, F, I32, P, P],
     'dv_adam': [P, P, P, P, I64, F, F, F, F, F, F, F, F, F, I32, P, P],
+    'dv_lars_chunk': [],
+    'dv_lars_norms': [P, P, P, P, I32, I32, F, F, P, P],
+    'dv_lars_step': [P, P, P, P, P, I32, I32, F, F, F, F, F, P, I32, P, P, P],
 }
 
 _lib = None

@@ -1,5 +1,5 @@
-"""Fused SGD over the parameter arenas (pretrain.py:262-272,451: SGD, momentum 0.9, weight decay applied to
-every tensor incl. BN and biases, one lr for all groups).
+"""Fused optimizers over the parameter arenas: SGD (pretrain.py:262-272,451: momentum 0.9, weight decay applied to
+every tensor incl. BN and biases, one lr for all groups), LARS on top of it for large-batch pretraining, and Adam for finetuning.
 
 One launch per encoder updates master weights, momentum and the bf16 compute copy; the class derives from
 torch.optim.Optimizer only so that torch LR schedulers (MultiStepLR, pretrain.py:328) drive `param_groups`."""
@@ -122,6 +122,121 @@ class SGD(torch.optim.Optimizer):
             warnings.warn('optimizer state: %d of %d momentum buffers restored, the rest start at zero'
                           % (restored, len(views)))
         return restored
+
+
+class _LarsTable:
+    """device copies of one store's dv_lars_seg table and block map, with the partials and trust-ratio buffers"""
+    __slots__ = ('key', 'segs', 'block_seg', 'n_segs', 'total_blocks', 'partials', 'q_out', 'slots', 'host')
+
+
+class LARS(SGD):
+    """Momentum SGD with layer-wise adaptive rate scaling over the parameter arenas, in the form of the PyTorch SimCLR / SSL
+    code bases (include/dualvar_hip.h, dv_lars_step): per tensor, with d = g * scale + wd * p,
+        q = eta |p| / |d|  (1 where either norm is 0);   buf = mu buf + q d;   p = p - lr buf
+    -- the update norm is taken after weight decay, the ratio sits inside the momentum, lr outside (MultiStepLR acts at once), and
+    the momentum buffer has SGD's meaning, so state_dict() / load_state_dict() are SGD's (torch.optim.SGD's format with
+    'momentum_buffer'; the groups also carry 'eta' and 'exclude_vec').  Convolution and linear weights ('conv' slots) take the
+    ratio and weight decay; BatchNorm weights / biases and linear biases ('vec' slots) take neither when exclude_vec (they are
+    stepped as plain momentum SGD without weight decay), both otherwise.  Tensors that do not require gradients have no segment
+    and are never touched (the MoCo key encoder, the backbone under --train_what last).
+    Two launches per store and step (dv_lars_norms, dv_lars_step), no host synchronisation: the norms never leave the device.
+    With grad_sync, the norms are those of the all-reduced gradient times the scale grad_sync returns -- the very values of the
+    update -- so every rank forms the same q from the same bits and no further collective is needed.
+    One lr, momentum, weight decay and eta for all groups, as SGD here: step() reads group 0."""
+
+    ADAPT, DECAY = 1, 2
+
+    def __init__(self, params, lr=0.03, momentum=0.9, weight_decay=0.0, eta=1e-3, exclude_vec=True, stores=None, grad_sync=None):
+        if not eta > 0.0:
+            raise ValueError('LARS eta must be > 0: %r' % (eta,))
+        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay, stores=stores, grad_sync=grad_sync)
+        for g in self.param_groups:
+            g['eta'], g['exclude_vec'] = eta, bool(exclude_vec)
+        self.defaults.update(eta=eta, exclude_vec=bool(exclude_vec))
+        self._tab = {}
+
+    def segments(self, st):
+        """[(slot, off, n, flags, first_block, n_blocks)] of one materialised store: one segment per slot whose tensor requires
+        gradients, in arena order, n = the slot's extent rounded up to 8 elements (structural padding holds zeros in both arenas
+        and adds nothing to a norm)"""
+        from . import _lib as L
+        from .engine import _align8
+        chunk = int(L.load().dv_lars_chunk())
+        exclude = bool(self.param_groups[0]['exclude_vec'])
+        out, first = [], 0
+        for s in st.slots:
+            if not s.tensor.requires_grad:
+                continue
+            n = _align8(s.size)
+            flags = 0 if (s.kind == 'vec' and exclude) else (self.ADAPT | self.DECAY)
+            nb = (n + chunk - 1) // chunk
+            out.append((s, s.off, n, flags, first, nb))
+            first += nb
+        return out
+
+    def _table(self, st):
+        from . import _lib as L
+        key = (st.generation, tuple(bool(s.tensor.requires_grad) for s in st.slots), bool(self.param_groups[0]['exclude_vec']),
+               st.master.device)
+        t = self._tab.get(id(st))
+        if t is not None and t.key == key:
+            return t
+        segs = self.segments(st)
+        dev = st.master.device
+        t = _LarsTable()
+        t.key, t.slots, t.n_segs = key, [e[0] for e in segs], len(segs)
+        t.total_blocks = sum(e[5] for e in segs)
+        arr = (L.LarsSeg * max(len(segs), 1))()
+        bmap = []
+        for i, (_, off, n, flags, first, nb) in enumerate(segs):
+            a = arr[i]
+            a.off, a.n, a.flags, a.first_block, a.n_blocks = off, n, flags, first, nb
+            bmap += [i] * nb
+        t.host = (arr, bmap)
+        t.segs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        t.block_seg = torch.tensor(bmap or [0], dtype=torch.int32).to(dev)
+        t.partials = torch.zeros(2 * max(t.total_blocks, 1), dtype=torch.float32, device=dev)
+        t.q_out = torch.ones(max(t.n_segs, 1), dtype=torch.float32, device=dev)
+        self._tab[id(st)] = t
+        return t
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        g = self.param_groups[0]
+        lr, mu, wd, eta = float(g['lr']), float(g['momentum']), float(g['weight_decay']), float(g['eta'])
+        for st in self.stores:
+            if st.master is None:
+                continue
+            scale = 1.0
+            if self.grad_sync is not None:
+                scale = self.grad_sync(st)
+            t = self._table(st)
+            if t.n_segs:
+                copy = st.cc if st.dtype != ops.DV_F32 else None
+                buf = self._momentum_buf(st)
+                ops.call('dv_lars_norms', st.master, st.grad, t.segs, t.block_seg, t.n_segs, t.total_blocks, wd, scale, t.partials)
+                ops.call('dv_lars_step', st.master, st.grad, buf, t.segs, t.block_seg, t.n_segs, t.total_blocks, lr, mu, wd, eta,
+                         scale, t.partials, st.dtype, copy, t.q_out)
+            st.mark_dirty(cast_done=True)
+            st.pending_backward = 0
+
+    def trust_ratios(self):
+        """[(parameter name or index in torch's flat parameter order, q of the last step)] for every stepped tensor, 1.0 for the
+        tensors that take no ratio.  Copies to the host (a synchronisation): for logging, never called from step()."""
+        where, i = {}, 0
+        for g in self.param_groups:
+            names = g.get('param_names')
+            for j, p in enumerate(g['params']):
+                where[id(p)] = names[j] if names else i
+                i += 1
+        out = []
+        for st in self.stores:
+            if st.master is None:
+                continue
+            t = self._table(st)
+            q = t.q_out.cpu().tolist()
+            out += [(where[id(s.tensor)], q[k]) for k, s in enumerate(t.slots) if id(s.tensor) in where]
+        return out
 
 
 def _step_value(s):

@@ -37,7 +37,7 @@ extern "C" {
    2: dv_conv3d_wgrad (workspace, workspace_bytes), dv_bn_bwd_reduce (ws), dv_infonce_fwd (workspace, bytes),
       dv_augment_ingest (blur, blur_scratch) gained arguments; dv_bn_item grew by red_ws (round 2 of this build).
    (dv_conv3d_ksplit_cols, dv_conv3d_wgrad_bn, dv_conv3d_wgrad_bn_ok, dv_augment_ingest_blocks / dv_aug_patch,
-   dv_resample_u8 / dv_resample_desc, dv_adam were ADDED under version 2: additions do not bump it.) */
+   dv_resample_u8 / dv_resample_desc, dv_adam, dv_lars_* / dv_lars_seg were ADDED under version 2: additions do not bump it.) */
 #define DV_ABI_VERSION 2
 
 enum { DV_F32 = 0, DV_BF16 = 1 };
@@ -636,6 +636,45 @@ int dv_ema(float* k, const float* q, int64_t n, float m, int32_t copy_dtype, voi
  * p, g, m, v 16-byte aligned. */
 int dv_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float omb1, float b2, float omb2, float eps,
             float wd, float bc1, float bc2, float grad_scale, int32_t copy_dtype, void* p_copy, void* stream);
+
+/* LARS (layer-wise adaptive rate scaling, the form of the PyTorch SimCLR / SSL code bases) over the TENSORS of an arena: each
+ * trainable tensor is one segment [off, off + n) of p / g / buf, with two flags.  Per element, fp32, one rounding per operation,
+ * nothing contracted into an FMA (as dv_sgd_momentum):
+ *   a1 = g*grad_scale;   d = DECAY ? a1 + wd*p : a1
+ * per segment:   Sp = sum p*p,  Sd = sum d*d,   q = (ADAPT && Sp > 0 && Sd > 0) ? eta * sqrt(Sp) / sqrt(Sd) : 1
+ *   (q is formed in double from the folded sums and from eta, and rounded once to float)
+ * per element:   t = q*d;   buf = mu*buf + t;   p = p - lr*buf;   optional compute-dtype copy of p (as dv_sgd_momentum).
+ * The update norm is taken after weight decay, the ratio sits inside the momentum and lr outside it (a learning-rate schedule
+ * acts at once; the momentum buffer has SGD's meaning).  A segment with DECAY and without ADAPT gets the bits of dv_sgd_momentum.
+ *
+ * Summation tree (fixed; a segment's sums depend on its own data and length only, not on its place in the table, and repeated
+ * launches give the same bits; no floating-point atomics).  A segment is cut into chunks of dv_lars_chunk() = 256 threads x 4
+ * elements x 16 trips consecutive elements, one block each.  In trip k = 0..15 thread t holds elements (k*256 + t)*4 + e,
+ * e = 0..3, of its chunk.  Each square x*x is rounded to fp32 and added to the thread's single fp32 accumulator in the order
+ * (k, e) -- at most 64 terms; elements at or past n add nothing.  The 64 lanes of a wavefront are folded by a butterfly
+ * (lane ^ 32, 16, 8, 4, 2, 1: six fp32 additions deep), the four wavefronts' sums are added in wavefront order in fp32, and
+ * the block writes the pair (Sp, Sd) to partials[2*block] (segments without ADAPT write and read none).  dv_lars_step folds a segment's partials
+ * [first_block, first_block + n_blocks) in double, in index order.  So a sum's relative error is at most (1 + 2^-24)^75 - 1
+ * (1 squaring + at most 64 + 6 + 4 additions of non-negative terms) plus n_blocks * 2^-53.
+ *
+ * The table lives in DEVICE memory and the caller owns its consistency: segs[n_segs]; block_seg[total_blocks] names the
+ * segment of every block (the concatenation of the segments' block ranges: block b of the grid works on chunk
+ * b - segs[block_seg[b]].first_block); n_blocks = ceil(n / dv_lars_chunk()); off a multiple of 4 elements; segments disjoint.
+ * partials: 2 * total_blocks floats.  Elements between segments are neither read nor written.
+ * dv_lars_norms writes the partials, dv_lars_step (same stream, after it) reads them, updates p / buf / the copy and writes
+ * q_out[segment] when q_out is given.  Null pointers (p_copy and q_out excepted), n_segs <= 0 or total_blocks <= 0: DV_EINVAL;
+ * p, g, buf not 16-byte aligned: DV_EALIGN.  Nothing is launched then. */
+enum { DV_LARS_ADAPT = 1, DV_LARS_DECAY = 2 };
+struct dv_lars_seg {
+  int64_t off, n;
+  int32_t flags, first_block, n_blocks, pad;
+};
+int dv_lars_chunk(void);
+int dv_lars_norms(const float* p, const float* g, const struct dv_lars_seg* segs, const int32_t* block_seg, int32_t n_segs,
+                  int32_t total_blocks, float wd, float grad_scale, float* partials, void* stream);
+int dv_lars_step(float* p, const float* g, float* buf, const struct dv_lars_seg* segs, const int32_t* block_seg, int32_t n_segs,
+                 int32_t total_blocks, float lr, float mu, float wd, float eta, float grad_scale, const float* partials,
+                 int32_t copy_dtype, void* p_copy, float* q_out, void* stream);
 
 #ifdef __cplusplus
 }

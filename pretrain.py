@@ -88,7 +88,10 @@ def parse_args(argv=None):
     p.add_argument('--frame_root', default=None, type=str,
                    help='*-2clip-stage-prototype: <class>/<video>/image_%%05d.jpg (default: the reference\'s path)')
     # optimizer
-    p.add_argument('--optim', default='sgd', type=str, help="'adam' selects dualvar_amd.optim.Adam; anything else SGD")
+    p.add_argument('--optim', default='sgd', type=str, help="'adam' selects dualvar_amd.optim.Adam, 'lars' dualvar_amd.optim.LARS (momentum SGD with a "
+                        "per-tensor trust ratio --lars_eta; BatchNorm parameters and biases take neither the ratio nor weight decay); "
+                        "anything else SGD")
+    p.add_argument('--lars_eta', default=1e-3, type=float, help='--optim lars: trust coefficient eta of q = eta |w| / |g + wd w|')
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--lr', default=0.03, type=float)
     p.add_argument('--wd', default=5e-4, type=float)
@@ -322,6 +325,10 @@ def main_worker(gpu, ngpus_per_node, args):
     if args.optim == 'adam':
         from dualvar_amd.optim import Adam
         optimizer = Adam(params, lr=args.lr, weight_decay=args.wd, stores=model.stores(), grad_sync=gsync)
+    elif args.optim == 'lars':
+        from dualvar_amd.optim import LARS
+        optimizer = LARS(params, lr=args.lr, weight_decay=args.wd, momentum=0.9, eta=args.lars_eta, stores=model.stores(),
+                         grad_sync=gsync)
     else:
         optimizer = SGD(params, lr=args.lr, weight_decay=args.wd, momentum=0.9, stores=model.stores(), grad_sync=gsync)
 
@@ -373,7 +380,7 @@ def main_worker(gpu, ngpus_per_node, args):
                     if hasattr(m_, 'prepare') and hasattr(m_, 'store'):
                         m_.prepare(torch.device('cuda', args.gpu))
                 n = optimizer.load_state_dict(ck['optimizer'])
-                args.logger.info('optimizer state restored (%d %s)' % (n, 'Adam moment pairs' if args.optim == 'adam' else 'momentum buffers'))
+                args.logger.info('optimizer state restored (%d %s)' % (n, {'adam': 'Adam moment pairs', 'lars': 'LARS momentum buffers'}.get(args.optim, 'momentum buffers')))
             except Exception as e:
                 args.logger.info('optimizer state not restored: %s' % e)
     elif args.pretrain and os.path.isfile(args.pretrain):
