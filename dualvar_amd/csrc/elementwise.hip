@@ -1552,7 +1552,9 @@ __global__ void rowscale_kernel(const T* __restrict__ a, int lda, const float* _
   constexpr int V = DT<T>::VEC;
   const uint32_t CV = fcv.d;
   const float invS = 1.f / (float)fS.d;
-  const bool vec = (C % V) == 0 && (MODE == 2 || ((uintptr_t)g & 15) == 0) && (MODE == 0 || ((uintptr_t)dm & 15) == 0);
+  // 16-byte reads of the [N][C] tables only when a row of them is whole vectors up to CP: with C % V == 0 but C < CP (fp32,
+  // C = 4 mod 8) the pad vector of the LAST sample would be read from behind the table
+  const bool vec = (int)CV * V == C && (MODE == 2 || ((uintptr_t)g & 15) == 0) && (MODE == 0 || ((uintptr_t)dm & 15) == 0);
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const uint32_t row = fd_div(i, fcv);
     const int c0 = (int)(i - row * CV) * V;
@@ -1561,7 +1563,7 @@ __global__ void rowscale_kernel(const T* __restrict__ a, int lda, const float* _
     if (MODE != 2) Pack16<T>::load(a + (size_t)row * lda + c0, v);
     if (accumulate) Pack16<T>::load(o + (size_t)row * ldo + c0, old);
     float gv[V], dv[V];
-    if (vec) {                                     // C % V == 0: the [N][C] fp32 rows are read as float4s
+    if (vec) {                                     // C == CP: the [N][C] fp32 rows are read as float4s
       if (MODE != 2) load_params<V>(g + (size_t)n * C, c0, gv);
       if (MODE != 0) load_params<V>(dm + (size_t)n * C, c0, dv);
     } else {
@@ -2015,6 +2017,41 @@ static int pool_args(const dv_pool_desc* d, PoolArgs& a) {
   return DV_OK;
 }
 
+// The ONE place that picks a pool launch (dv_maxpool3d_route answers from it, dv_maxpool3d_fwd / _bwd launch what it says):
+// 0 = per-element gather kernel, 1 = 2x2-quad backward, 2 = LDS-staged 3x3x3 tile (ta, tw, cv filled).  idx_aligned: idx is
+// 8-byte aligned (the quad and staged kernels read it in 32-bit words).
+enum { kPoolGather = 0, kPoolQuad = 1, kPoolTile = 2 };
+static int pool_route(const dv_pool_desc* d, const PoolArgs& a, bool bwd, bool idx_aligned, int accumulate, PoolTileArgs& ta,
+                      int& tw, int& cv) {
+  tw = cv = 0;
+  if (pool333_shape(d) && !pool_tile_off() && idx_aligned) {
+    const int V = d->dtype == DV_F32 ? 4 : 8;
+    const int cv_ = pool_tile_cv(bwd ? (d->dtype == DV_BF16 ? 2 : 4) : 4);
+    const int tw_ = pool_tile_tw(a.Wi, bwd || d->dtype == DV_BF16);
+    if ((cv_ == 2 || cv_ == 4 || cv_ == 8) && pool_tile_args(a, V, 7, tw_, cv_, accumulate, ta)) {
+      tw = tw_; cv = cv_;
+      return kPoolTile;
+    }
+  }
+  if (bwd && a.kh == 3 && a.kw == 3 && a.sh == 2 && a.sw == 2 && a.ph == 1 && a.pw == 1 && idx_aligned) return kPoolQuad;
+  return kPoolGather;
+}
+
+extern "C" int dv_maxpool3d_route(const dv_pool_desc* d, int32_t bwd, int32_t* tile_w, int32_t* chunk_vecs) {
+  PoolArgs a;
+  int rc = pool_args(d, a);
+  if (rc) return rc;
+  if (d->dtype != DV_F32 && d->dtype != DV_BF16) return DV_EINVAL;
+  PoolTileArgs ta;
+  int tw, cv;
+  const int route = pool_route(d, a, bwd != 0, true, 0, ta, tw, cv);
+  if (route == kPoolTile) {
+    if (tile_w) *tile_w = tw;
+    if (chunk_vecs) *chunk_vecs = cv;
+  }
+  return route;
+}
+
 extern "C" int dv_maxpool3d_fwd(const dv_pool_desc* d, const void* x, void* y, uint8_t* idx, void* stream) {
   PoolArgs a;
   int rc = pool_args(d, a);
@@ -2022,11 +2059,11 @@ extern "C" int dv_maxpool3d_fwd(const dv_pool_desc* d, const void* x, void* y, u
   if (!x || !y || !idx) return DV_EINVAL;
   if (!aligned16(x) || !aligned16(y) || (reinterpret_cast<uintptr_t>(idx) & 7)) return DV_EALIGN;
   PoolTileArgs ta;
-  if (pool333_shape(d) && !pool_tile_off()) {
-    const int cv = pool_tile_cv(4), tw = pool_tile_tw(a.Wi, d->dtype == DV_BF16);
+  int tw, cv;
+  if (pool_route(d, a, false, true, 0, ta, tw, cv) == kPoolTile) {
 #define POOL_FWD_TILE(TW_, CV_)                                                                                             \
   DISPATCH_T(d->dtype, {                                                                                                     \
-    if (cv == CV_ && tw == TW_ && pool_tile_args(a, DT<T>::VEC, 7, TW_, CV_, 0, ta)) {                                       \
+    if (cv == CV_ && tw == TW_) {                                                                                            \
       hipLaunchKernelGGL((pool333_fwd_tile_kernel<T, 7, TW_, CV_>), dim3(8 * ta.per_xcd), dim3(kThreads), 0, ST(stream), ta, \
                          (const T*)x, (T*)y, idx);                                                                           \
       return dv_launch_status();                                                                                             \
@@ -2035,6 +2072,7 @@ extern "C" int dv_maxpool3d_fwd(const dv_pool_desc* d, const void* x, void* y, u
     POOL_FWD_TILE(7, 2); POOL_FWD_TILE(7, 4); POOL_FWD_TILE(7, 8);
     POOL_FWD_TILE(14, 2); POOL_FWD_TILE(14, 4); POOL_FWD_TILE(14, 8);
 #undef POOL_FWD_TILE
+    return DV_EUNSUPPORTED;                       // (pool_route only names the tiles instantiated above)
   }
   DISPATCH_T(d->dtype, {
     const int64_t total = (int64_t)a.N * a.To * a.Ho * a.Wo * (a.CP / DT<T>::VEC);
@@ -2052,12 +2090,13 @@ extern "C" int dv_maxpool3d_bwd(const dv_pool_desc* d, const void* dy, const uin
   if (!dy || !dx || !idx) return DV_EINVAL;
   if (!aligned16(dy) || !aligned16(dx)) return DV_EALIGN;
   PoolTileArgs ta;
-  if (pool333_shape(d) && !pool_tile_off() && (reinterpret_cast<uintptr_t>(idx) & 7) == 0) {
-    const int cv = pool_tile_cv(d->dtype == DV_BF16 ? 2 : 4), tw = pool_tile_tw(a.Wi, true);
-    const int acc = (flags & DV_ACCUM) ? 1 : 0;
+  int tw, cv;
+  const int acc = (flags & DV_ACCUM) ? 1 : 0;
+  const int route = pool_route(d, a, true, (reinterpret_cast<uintptr_t>(idx) & 7) == 0, acc, ta, tw, cv);
+  if (route == kPoolTile) {
 #define POOL_BWD_TILE(TW_, CV_)                                                                                             \
   DISPATCH_T(d->dtype, {                                                                                                     \
-    if (cv == CV_ && tw == TW_ && pool_tile_args(a, DT<T>::VEC, 7, TW_, CV_, acc, ta)) {                                     \
+    if (cv == CV_ && tw == TW_) {                                                                                            \
       hipLaunchKernelGGL((pool333_bwd_tile_kernel<T, 7, TW_, CV_>), dim3(8 * ta.per_xcd), dim3(kThreads), 0, ST(stream), ta, \
                          (const T*)dy, idx, (T*)dx);                                                                         \
       return dv_launch_status();                                                                                             \
@@ -2066,20 +2105,21 @@ extern "C" int dv_maxpool3d_bwd(const dv_pool_desc* d, const void* dy, const uin
     POOL_BWD_TILE(7, 2); POOL_BWD_TILE(7, 4); POOL_BWD_TILE(7, 8);
     POOL_BWD_TILE(14, 2); POOL_BWD_TILE(14, 4); POOL_BWD_TILE(14, 8);
 #undef POOL_BWD_TILE
+    return DV_EUNSUPPORTED;
   }
-  if (a.kh == 3 && a.kw == 3 && a.sh == 2 && a.sw == 2 && a.ph == 1 && a.pw == 1 && (reinterpret_cast<uintptr_t>(idx) & 7) == 0) {
+  if (route == kPoolQuad) {
     const int Hq = (a.Hi + 1) / 2, Wq = (a.Wi + 1) / 2;
     DISPATCH_T(d->dtype, {
       const int64_t total = (int64_t)a.N * a.Ti * Hq * Wq * (a.CP / DT<T>::VEC);
       hipLaunchKernelGGL((maxpool_bwd_quad_kernel<T>), dim3(grid8_for(total, 16384)), dim3(kThreads), 0, ST(stream), a,
-                         make_fastdiv((uint32_t)Wq), make_fastdiv((uint32_t)Hq), (const T*)dy, idx, (T*)dx, (flags & DV_ACCUM) ? 1 : 0);
+                         make_fastdiv((uint32_t)Wq), make_fastdiv((uint32_t)Hq), (const T*)dy, idx, (T*)dx, acc);
     });
     return dv_launch_status();
   }
   DISPATCH_T(d->dtype, {
     const int64_t total = (int64_t)a.N * a.Ti * a.Hi * a.Wi * (a.CP / DT<T>::VEC);
     hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(grid8_for(total, 16384)), dim3(kThreads), 0, ST(stream), a, (const T*)dy,
-                       idx, (T*)dx, (flags & DV_ACCUM) ? 1 : 0);
+                       idx, (T*)dx, acc);
   });
   return dv_launch_status();
 }
@@ -2147,6 +2187,17 @@ static int c_chunk_vecs(int N, int S, int CV) {
   if (chunks < 1 || S < 128) chunks = 1;
   return (CV + chunks - 1) / chunks;
 }
+// grid.y of the three per-sample column reductions: the launches and dv_spatial_chunks both take it from here
+static int spatial_grid_y(int N, int S, int CV, int& ccv) {
+  ccv = c_chunk_vecs(N, S, CV);
+  return (CV + ccv - 1) / ccv;
+}
+
+extern "C" int dv_spatial_chunks(int32_t dtype, int32_t N, int32_t S, int32_t C) {
+  if ((dtype != DV_F32 && dtype != DV_BF16) || N <= 0 || S <= 0 || C <= 0) return DV_EINVAL;
+  int ccv;
+  return spatial_grid_y(N, S, cp8(C) / (dtype == DV_F32 ? 4 : 8), ccv);
+}
 
 extern "C" int dv_spatial_mean(int32_t dtype, const void* x, int32_t ldx, int32_t N, int32_t S, int32_t C, float* out,
                                void* stream) {
@@ -2155,8 +2206,9 @@ extern "C" int dv_spatial_mean(int32_t dtype, const void* x, int32_t ldx, int32_
   if (!aligned16(x)) return DV_EALIGN;
   DISPATCH_T(dtype, {
     if (ldx % DT<T>::VEC) return DV_EALIGN;
-    const int CV = CP / DT<T>::VEC, ccv = c_chunk_vecs(N, S, CV);
-    hipLaunchKernelGGL((spatial_mean_kernel<T>), dim3(N, (CV + ccv - 1) / ccv), dim3(kThreads), 0, ST(stream), (const T*)x, ldx, S,
+    int ccv;
+    const int gy = spatial_grid_y(N, S, CP / DT<T>::VEC, ccv);
+    hipLaunchKernelGGL((spatial_mean_kernel<T>), dim3(N, gy), dim3(kThreads), 0, ST(stream), (const T*)x, ldx, S,
                        C, CP, ccv, out);
   });
   return dv_launch_status();
@@ -2203,8 +2255,9 @@ extern "C" int dv_gate_bwd_reduce(int32_t dtype, const void* dy, int32_t lddy, c
   if (!aligned16(dy) || !aligned16(x)) return DV_EALIGN;
   DISPATCH_T(dtype, {
     if (lddy % DT<T>::VEC || ldx % DT<T>::VEC) return DV_EALIGN;
-    const int CV = CP / DT<T>::VEC, ccv = c_chunk_vecs(N, S, CV);
-    hipLaunchKernelGGL((gate_bwd_reduce_kernel<T>), dim3(N, (CV + ccv - 1) / ccv), dim3(kThreads), 0, ST(stream), (const T*)dy,
+    int ccv;
+    const int gy = spatial_grid_y(N, S, CP / DT<T>::VEC, ccv);
+    hipLaunchKernelGGL((gate_bwd_reduce_kernel<T>), dim3(N, gy), dim3(kThreads), 0, ST(stream), (const T*)dy,
                        lddy, (const T*)x, ldx, g, S, C, CP, ccv, dpre, x_is_output);
   });
   return dv_launch_status();
@@ -2238,8 +2291,9 @@ extern "C" int dv_gate_mean_bn(int32_t dtype, const dv_bn_item* items, int32_t n
   if (int rc = gate_fold_args(items, n, gate_off, N, S, Ct)) return rc;
   if (!mean) return DV_EINVAL;
   DISPATCH_T(dtype, {
-    const int CV = Ct / DT<T>::VEC, ccv = c_chunk_vecs(N, S, CV);
-    hipLaunchKernelGGL((gate_mean_bn_kernel<T>), dim3(N, (CV + ccv - 1) / ccv), dim3(kThreads), 0, ST(stream), items, n, gate_off,
+    int ccv;
+    const int gy = spatial_grid_y(N, S, Ct / DT<T>::VEC, ccv);
+    hipLaunchKernelGGL((gate_mean_bn_kernel<T>), dim3(N, gy), dim3(kThreads), 0, ST(stream), items, n, gate_off,
                        S, Ct, ccv, mean);
   });
   return dv_launch_status();

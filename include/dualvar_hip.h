@@ -37,7 +37,8 @@ extern "C" {
    2: dv_conv3d_wgrad (workspace, workspace_bytes), dv_bn_bwd_reduce (ws), dv_infonce_fwd (workspace, bytes),
       dv_augment_ingest (blur, blur_scratch) gained arguments; dv_bn_item grew by red_ws (round 2 of this build).
    (dv_conv3d_ksplit_cols, dv_conv3d_wgrad_bn, dv_conv3d_wgrad_bn_ok, dv_augment_ingest_blocks / dv_aug_patch,
-   dv_resample_u8 / dv_resample_desc, dv_adam, dv_lars_* / dv_lars_seg were ADDED under version 2: additions do not bump it.) */
+   dv_resample_u8 / dv_resample_desc, dv_adam, dv_lars_* / dv_lars_seg, dv_maxpool3d_route, dv_spatial_chunks were ADDED under version 2:
+   additions do not bump it.) */
 #define DV_ABI_VERSION 2
 
 enum { DV_F32 = 0, DV_BF16 = 1 };
@@ -455,7 +456,15 @@ int dv_bn_bwd_apply(int32_t dtype, const void* dy, int32_t lddy, const void* y, 
 
 /* ---------------------------------------------------------------------------------------
  * MaxPool3d (s3dg.py:105,151,162,173,190; resnet_2d3d.py:212,280): -inf padding, first maximum
- * in (t,h,w) scan order wins (PyTorch CPU semantics).  idx holds the winning tap per element.
+ * in (t,h,w) scan order wins (PyTorch CPU semantics).  idx holds the winning tap per element,
+ * (dt*kh + dh)*kw + dw.  One qualification, signed zeros: the per-element kernels compare values, so -0.0 and +0.0 tie
+ * and the first of them wins, as in PyTorch; the LDS-staged 3x3x3 / stride 1 / padding 1 forward (dv_maxpool3d_route
+ * = 2) compares order-preserving integer keys, which place -0.0 BELOW +0.0: in a window whose maximum is zero and
+ * that holds both zeros it reports the first +0.0.  The pooled value is numerically equal either way (0 == -0), only
+ * the tap, and with it the element that receives the gradient, can differ.  The pools of the networks read
+ * post-ReLU activations, which hold no -0.0.  (NaN inputs: the per-element kernels propagate any NaN; the staged
+ * forward ranks a NaN with the sign bit clear above +inf and one with the sign bit set below -inf.  Which of several
+ * NaNs is reported is not specified.)
  */
 typedef struct dv_pool_desc {
   int32_t dtype;
@@ -465,6 +474,13 @@ typedef struct dv_pool_desc {
   int32_t ldx, ldy;
 } dv_pool_desc;
 int dv_maxpool3d_fwd(const dv_pool_desc* d, const void* x, void* y, uint8_t* idx, void* stream);
+/* informational: the kernel dv_maxpool3d_fwd (bwd = 0) / dv_maxpool3d_bwd (bwd = 1) will run this problem on, from the
+ * planning function the launches themselves call: 0 = per-element gather, 1 = 2x2-quad gather (backward of the 3x3 /
+ * stride 2 / padding 1 windows in (h, w)), 2 = LDS-staged tile (3x3x3 / stride 1 / padding 1 with Hi*Wi >= 25); a negative
+ * DV_E* code where the launch would return it for this descriptor.  The answer assumes an 8-byte aligned idx: with any
+ * other idx the backward runs on the gather kernel (same bits) and the forward returns DV_EALIGN.  For route 2, *tile_w
+ * (7 / 14, tiles are 7 rows high) and *chunk_vecs (16-byte channel vectors per workgroup) are filled; both may be NULL. */
+int dv_maxpool3d_route(const dv_pool_desc* d, int32_t bwd, int32_t* tile_w, int32_t* chunk_vecs);
 /* dx (+)= scatter of dy through idx (gather formulation, deterministic); flags: DV_ACCUM */
 int dv_maxpool3d_bwd(const dv_pool_desc* d, const void* dy, const uint8_t* idx, void* dx, int32_t flags,
                      void* stream);
@@ -496,6 +512,10 @@ int dv_bn_bwd_apply_maxpool(const dv_pool_desc* d, const void* dy_pool, const ui
  */
 int dv_spatial_mean(int32_t dtype, const void* x, int32_t ldx, int32_t N, int32_t S, int32_t C, float* out,
                     void* stream);
+/* informational: grid.y of dv_spatial_mean, dv_gate_bwd_reduce and dv_gate_mean_bn (the last with C = Ct) -- the channel
+ * chunks a sample's columns are split over (1 when S < 128 or a row has at most 16 16-byte vectors); the launches take it
+ * from the same function.  DV_EINVAL for a bad dtype or a non-positive size. */
+int dv_spatial_chunks(int32_t dtype, int32_t N, int32_t S, int32_t C);
 int dv_spatial_mean_bwd(int32_t dtype, const float* dout, int32_t N, int32_t S, int32_t C, void* dx,
                         int32_t lddx, int32_t flags, void* stream);
 int dv_gate_scale(int32_t dtype, const void* x, int32_t ldx, const float* g, int32_t N, int32_t S, int32_t C,

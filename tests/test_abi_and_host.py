@@ -698,3 +698,76 @@ def test_conv_case_table_routes_and_coverage():
     need = list(CONV_REQUIRED) + ['row:' + n for n in CONV_TABLE_ROWS]
     missing = [m for m in need if m not in seen]
     assert not missing, 'not covered by the table: %s' % ', '.join(missing)
+
+
+POOL_TABLE_ROWS = [
+    'st_5x5_t2_c4', 'g_4x6_t2', 'st_8x15_t1_c36', 'st_15x8_t5_c72_n3', 'st_6x6_t2_sliced', 'q_133_7x8', 'q_133_1x2', 'q_333s2_8x7',
+    'q_333s122_2x1', 'q_333s122_7x7', 'g_222_odd', 'g_311_s2', 'g_333_p0']
+POOL_REQUIRED = (
+    ['%s:%s:route2' % (w, dt) for w in ('fwd', 'bwd') for dt in ('f32', 'bf16')] +
+    ['fwd:f32:route0', 'fwd:bf16:route0', 'bwd:f32:route0', 'bwd:bf16:route0', 'bwd:f32:route1', 'bwd:bf16:route1',
+     'fwd:f32:tw14', 'fwd:f32:tw7', 'fwd:bf16:tw7', 'bwd:f32:tw7', 'bwd:bf16:tw7',
+     'tile:boundary25', 'staged-shape:below25->gather', 'tile:tw14-one-pixel-last-tile', 'tile:three-tiles-w',
+     'tile:tiles-along-h', 'tile:T1', 'tile:T2', 'tile:T5', 'tile:cpv<CV', 'tile:partial-last-chunk',
+     'tile:bf16-chunks-differ-fwd-bwd', 'tile:groups%8!=0',
+     'quad:k133/s122', 'quad:k333/s222', 'quad:k333/s122', 'quad:pad-lanes',
+     'gather:k222/s222/p000', 'gather:k311/s211/p100', 'gather:k333/s111/p000',
+     'sliced:route2', 'idx+4:route1', 'idx+4:route2'] +
+    ['quad:%s%d' % (a, v) for a in 'HW' for v in (1, 2, 7, 8)])
+
+
+def test_pool_case_table_routes_and_coverage():
+    """tests/pool_cases.py, the tables tests/test_pool_gate_float64_gpu.py runs: through dv_maxpool3d_route and
+    dv_spatial_chunks -- the planning functions the launches call -- every row still takes the route, tile width, chunk width
+    and channel-chunk count it was written for, the tables reach every member of POOL_REQUIRED (gather / quad / staged in both
+    directions and dtypes, the staged boundary and its tile geometries, the three quad geometries, channel chunks: one because
+    S < 128, partial last chunk, capped by N, the gate-fold level), and every capped grid-stride launch has a case just over
+    its cap with a ragged last block."""
+    from dualvar_amd import _lib
+    from tests import pool_cases as T
+    lib = _lib.load()
+    moved, seen = [], set()
+    for c in T.POOL_CASES + T.BN_POOL_CASES + list(T.WRAP_POOLS.values()):
+        for i, dt in enumerate((_lib.DV_F32, _lib.DV_BF16)):
+            for bwd, want in ((0, c.fwd[i]), (1, c.bwd[i])):
+                got = T.query(c, dt, bwd)
+                if got != want:
+                    moved.append('%s dtype %d bwd %d: expected %r, the library reports %r' % (c.name, dt, bwd, want, got))
+    for c in T.POOL_CASES:
+        seen |= set(T.members(c))
+    assert len({c.name for c in T.POOL_CASES}) == len(T.POOL_CASES)
+    # channel chunks
+    tags = set()
+    for c in T.CHUNK_CASES:
+        for i, dt in enumerate((_lib.DV_F32, _lib.DV_BF16)):
+            got = lib.dv_spatial_chunks(dt, c.N, c.S, c.C[i])
+            if got != c.chunks:
+                moved.append('%s dtype %d: expected %d channel chunks, the library reports %d' % (c.name, dt, c.chunks, got))
+        tags.add(c.tag)
+    g = T.GATE_LEVEL
+    for i, dt in enumerate((_lib.DV_F32, _lib.DV_BF16)):
+        got = lib.dv_spatial_chunks(dt, g['N'], g['S'], g['Ct'])
+        if got != g['chunks'][i]:
+            moved.append('gate level dtype %d: expected %d channel chunks, the library reports %d' % (dt, g['chunks'][i], got))
+    assert not moved, '\n'.join(moved)
+    assert tags >= {'S<128', 'partial-last-chunk', 'capped-by-N', 'CV<=16', 'C%V!=0'}
+    pl = [c for c in T.CHUNK_CASES if c.tag == 'partial-last-chunk'][0]
+    for i, v in enumerate((4, 8)):
+        cvn = T.cp8(pl.C[i]) // v
+        assert cvn % -(-cvn // pl.chunks) != 0 and pl.S == 128
+    cn = [c for c in T.CHUNK_CASES if c.tag == 'capped-by-N'][0]
+    assert -(-1024 // cn.N) < -(-(T.cp8(cn.C[0]) // 4) // 16)
+    assert sum(g['widths']) == g['Ct'] == 256 and g['S'] == 128 and g['N'] == 3 and len(g['sliced']) == 2
+    need = list(POOL_REQUIRED) + ['row:' + n for n in POOL_TABLE_ROWS]
+    missing = [m for m in need if m not in seen]
+    assert not missing, 'not covered by the table: %s' % ', '.join(missing)
+    # the queries reject what the launches reject
+    bad = T.desc(T.POOL_CASES[0], _lib.DV_F32)
+    bad.To += 1
+    assert lib.dv_maxpool3d_route(bad, 0, None, None) == -1 and lib.dv_maxpool3d_route(None, 0, None, None) == -1
+    assert lib.dv_spatial_chunks(_lib.DV_F32, 0, 128, 8) == -1 and lib.dv_spatial_chunks(5, 1, 128, 8) == -1
+    # grid wrap: every capped launch has a case with more than cap * 256 work items and a ragged last block
+    assert set(T.WRAP_CAPS) == {'rowscale0', 'rowscale1', 'rowscale2', 'relu_bwd', 'ingest'} | set(T.WRAP_POOLS)
+    for name, cap in T.WRAP_CAPS.items():
+        items = T.wrap_items(name)
+        assert cap * 256 < items < cap * 256 * 1.01 and items % 256 != 0, (name, items)

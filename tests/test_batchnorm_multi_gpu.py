@@ -63,19 +63,25 @@ def n_blocks(lib, phase, M, C_, dtype):
     return max(1, min(4096 if phase == 'apply' else 2048, ceil_div(total, 256)))
 
 
-def bwd_reduce_chain(M, C_, dtype, nblk):
-    """longest chain of sequential fp32 additions of bn_bwd_reduce_body + ordered_fold (elementwise.hip): rows per thread
-    of column_reduce, its pairwise fold of the row groups, the fold of a group of <= 32 block rows, the fold of the groups"""
-    V, CV = vec(dtype), cp8(C_) // vec(dtype)
-    rpb = ceil_div(M, nblk)
+def column_chain(rows, CP, dtype, NS, extra=0):
+    """longest chain of sequential fp32 additions column_reduce (elementwise.hip) forms over `rows` rows of CP columns with NS
+    sums per column: rows per thread, then ceil(log2 rg) for the pairwise fold of the rg row groups; `extra` is what the caller
+    adds behind it (block folds, or the blocks that add to one replica with float atomics; 0: every output has one owner)"""
+    V, CV = vec(dtype), CP // vec(dtype)
     chain = 0
     for cvb in range(0, CV, 256):
         cvc = min(256, CV - cvb)
         rg = 256 // cvc
-        while rg > 1 and rg * cvc * V * 2 > 4096:
+        while rg > 1 and rg * cvc * V * NS > 4096:
             rg >>= 1
-        chain = max(chain, ceil_div(rpb, rg) + math.ceil(math.log2(rg)))
-    return chain + min(32, nblk) + ceil_div(nblk, 32)
+        chain = max(chain, ceil_div(rows, rg) + math.ceil(math.log2(rg)))
+    return chain + extra
+
+
+def bwd_reduce_chain(M, C_, dtype, nblk):
+    """longest chain of sequential fp32 additions of bn_bwd_reduce_body + ordered_fold (elementwise.hip): column_chain over
+    the rows of one block, the fold of a group of <= 32 block rows, the fold of the groups"""
+    return column_chain(ceil_div(M, nblk), cp8(C_), dtype, 2, min(32, nblk) + ceil_div(nblk, 32))
 
 
 def stats_chain(n_tiles):
