@@ -87,6 +87,9 @@ class IngestOp(Op):
                                           self.perm.data_ptr() if self.perm is not None else 0,
                                           self.n_seg if self.perm is not None else 0, self.pad, stream), 'dv_ingest_ncdhw_pad')
 
+    def inputs(self):
+        return []                    # (the source clips are the caller's, not an activation of the plan)
+
     def launches(self):
         return [_IngestStep(self)], []
 
@@ -243,6 +246,7 @@ class HipBackbone(nn.Module):
         pl.ingest = pl._push(IngestOp(pl, N, T, H, W, n_seg, pad=self.stem_pad))
         out = self.emit(pl, pl.ingest.y)
         pl.out_act = out
+        pl.host_reads.append(out)    # (forward() returns it; the backward writes its gradient)
         pl.mean_op = None
         if not want_map:
             pl.pooled = pl.spatial_mean(out)

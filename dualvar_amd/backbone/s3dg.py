@@ -194,7 +194,7 @@ class S3D(HipBackbone):
             if isinstance(m, nn.MaxPool3d):
                 # the network is a chain here: the pool is the only reader of what precedes it (after a conv + BN + ReLU
                 # -- MaxPool_2a, MaxPool_3a -- the engine then fuses the three)
-                x = plan.maxpool(x, t3(m.kernel_size), t3(m.stride), t3(m.padding), sole_consumer=True)
+                x = plan.maxpool(x, t3(m.kernel_size), t3(m.stride), t3(m.padding))
             else:
                 x = m.emit(plan, x)
         return x

@@ -49,8 +49,8 @@ WGRAD_BATCH = int(os.environ.get('DUALVAR_WGRAD_BATCH', '4'))
 WGRAD_FLUSH_FLOPS = float(os.environ.get('DUALVAR_WGRAD_FLUSH_GFLOP', '3')) * 1e9
 WGRAD_EARLY_RATIO = 0.5
 WGRAD_EARLY = os.environ.get('DUALVAR_WGRAD_EARLY', 'auto')        # 'auto' | '0' | '1' (A/B)
-# BatchNorm + ReLU whose only consumer is a max-pool (the stems) run fused with it (module switch: the tests compare both forms)
-FUSE_BN_POOL = True
+# The fusions of a BatchNorm with its neighbours, decided by Plan.finalize from the plan's PlanGraph.  (A lone BatchNorm + ReLU
+# whose only reader is a max-pool -- the stems -- always runs fused with it: that one has no switch.)
 # conv -> BatchNorm -> conv with a single reader: the BatchNorm-backward reduce can run in the second conv's data-gradient
 # epilogue (dv_conv3d_dgrad_bn).  OFF by default -- measured on the S3D-G step (MI355X, fp32 / bf16): the reduce launches shrink
 # 1.36 -> 0.66 / 1.07 -> 0.55 ms per step, but the data gradients that carry them grow by 0.62 / 0.52 ms (a serial tail per
@@ -509,6 +509,52 @@ def _dt(dtype):
     return 'f32' if dtype == DV_F32 else 'bf16'
 
 
+def _bufkey(a):
+    """the allocation an activation lives in (views and channel slices of one buffer share it)"""
+    return a.buf.untyped_storage().data_ptr()
+
+
+class PlanGraph:
+    """Who reads each activation and who writes each gradient, over a plan's ops in forward order (anything with inputs(),
+    grad_targets() and an `acc` dict) and the activations the host reads: what every fusion of Plan.finalize asks.  A read of
+    any channel slice counts as a read of the whole buffer (conservative); gradient writers are per (buffer, channel offset)."""
+
+    def __init__(self, ops, host_reads=()):
+        self._readers, self._writers, self._host = {}, {}, {_bufkey(a) for a in host_reads}
+        for op in ops:
+            for a in op.inputs():
+                r = self._readers.setdefault(_bufkey(a), [])
+                if op not in r:
+                    r.append(op)
+            for name, a in op.grad_targets():
+                w = self._writers.setdefault(self._gkey(a), [])
+                assert not w or w[-1][0] is not op, '%s writes one gradient twice' % type(op).__name__
+                w.append((op, name, a))
+
+    @staticmethod
+    def _gkey(a):
+        g = a.grad if a.grad is not None else a      # (an activation fused away has no buffer of its own: key on the gradient)
+        return _bufkey(g), g.off
+
+    def readers(self, a):
+        return self._readers.get(_bufkey(a), [])
+
+    def sole_reader(self, a):
+        """the one op that reads a's buffer; None if there are several, or the host reads it too"""
+        r = self.readers(a)
+        return r[0] if len(r) == 1 and _bufkey(a) not in self._host else None
+
+    def grad_writers(self, a):
+        """[(op, name, activation)]: the grad_targets() that write a's gradient"""
+        return self._writers.get(self._gkey(a), [])
+
+    def set_accumulate_flags(self):
+        """the last consumer (forward order) of an activation is the first writer of its gradient: the earlier ones add to it"""
+        for w in self._writers.values():
+            for op, name, _ in w:
+                op.acc[name] = op is not w[-1][0]
+
+
 class Plan:
     """Static forward/backward launch lists for one backbone at one input shape."""
 
@@ -518,6 +564,8 @@ class Plan:
         assert training or not with_grad, 'eval-mode plans are forward only' 
         self.comm = comm if comm is not None else Comm()
         self.ops = []
+        self.host_reads = []         # activations the host reads after run_forward (the caller registers them before finalize)
+        self.bn_out = {}             # (buffer, channel offset) -> (BNGroupOp, BNMember) that writes there (bn_group)
         self.f_list, self.b_list = [], []
         self.bytes = 0
         self.lib = L.load()
@@ -596,7 +644,7 @@ class Plan:
         layers -> their outputs.  One statistics exchange for the whole group."""
         op = self._push(BNGroupOp(self, specs))
         for m in op.members:
-            m.y.bn_member = (op, m)
+            self.bn_out[(_bufkey(m.y), m.y.off)] = (op, m)
         return [m.y for m in op.members]
 
     def bn(self, bn_mod, x, relu=True, residual=None, out=None, conv_bias=None):
@@ -607,16 +655,10 @@ class Plan:
         self.ops[-1].members[0].conv_bias = conv_bias
         return ys[0]
 
-    def maxpool(self, x, k, s, p, sole_consumer=False):
-        """sole_consumer: the caller guarantees that nothing else reads x.  If x is then the output of a lone
-        BatchNorm + ReLU, the pair runs fused (dv_bn_apply_maxpool / dv_bn_bwd_*_maxpool): x is never materialised."""
-        member = None
-        if sole_consumer and FUSE_BN_POOL and getattr(x, 'bn_member', None) is not None:
-            op, m = x.bn_member
-            if (len(op.members) == 1 and m.relu and m.res is None and m.conv_bias is None and m.fused_pool is None
-                    and m.y is x and x.off == 0 and (not self.with_grad or m.mask_from_x)):
-                member = m
-        return self._push(PoolOp(self, x, k, s, p, bn_member=member)).y
+    def maxpool(self, x, k, s, p):
+        """If x turns out to be the output of a lone BatchNorm + ReLU that nothing else reads, the pair runs fused
+        (finalize: _fuse_pools)."""
+        return self._push(PoolOp(self, x, k, s, p)).y
 
     def gate_group(self, fcs, cat):
         """in-place self gating of a concat buffer: fcs = [(nn.Linear, channel offset, width), ...]"""
@@ -627,122 +669,107 @@ class Plan:
         return self._push(MeanOp(self, x)).out
 
     def finalize(self):
-        for op in self.ops:          # a BatchNorm output fused into its pool does not exist in memory: nobody else may read it
-            if isinstance(op, PoolOp) and op.bn_member is not None:
-                gone = op.bn_member.y
-                for other in self.ops:
-                    if other is op:
-                        continue
-                    readers = [getattr(other, a, None) for a in ('x', 'cat')]
-                    readers += [t for m in getattr(other, 'members', ()) for t in (m.x, m.res)]
-                    assert all(r is None or r.buf is not gone.buf for r in readers), \
-                        'maxpool(sole_consumer=True) on an activation that %s also reads' % type(other).__name__
-        # the last consumer (forward order) of an activation is the first writer of its gradient
-        seen = set()
-        for op in reversed(self.ops):
-            for name, a in op.grad_targets():
-                g = a.grad if a.grad is not None else a      # (an activation fused away has no buffer of its own: key on the gradient)
-                key = (g.buf.data_ptr(), g.off)
-                op.acc[name] = key in seen
-                seen.add(key)
-        # conv -> BatchNorm(+ReLU) -> conv chains: when the second conv is the only reader of the BatchNorm's output, its
-        # data gradient IS dL/dy of that BatchNorm, complete after one launch -- the BatchNorm backward's reduce (sum g,
-        # sum g*xhat) runs in that launch's epilogue (dv_conv3d_dgrad_bn) instead of re-reading dL/dy in a pass of its own
-        if self.with_grad and self.training and FUSE_BN_REDUCE:
-            writers = {}
-            for op in self.ops:
-                for name, a in op.grad_targets():
-                    g = a.grad if a.grad is not None else a
-                    writers.setdefault((g.buf.data_ptr(), g.off), []).append((op, a))
-            for op in self.ops:
-                if not isinstance(op, BNGroupOp):
-                    continue
-                for m in op.members:
-                    y = m.y
-                    if y.grad is None or m.res is not None or m.fused_pool is not None or (m.relu and not m.mask_from_x):
-                        continue
-                    w = writers.get((y.grad.buf.data_ptr(), y.grad.off), [])
-                    if len(w) != 1 or not isinstance(w[0][0], ConvOp):
-                        continue
-                    cop, a = w[0]
-                    if (cop.fp8 or not cop.need_dx or cop.acc.get('x') or a.buf is not y.buf or a.off != y.off or a.C != y.C
-                            or a.rows != y.rows or cop.bn_fuse is not None):
-                        continue
-                    cop.bn_fuse, m.reduce_fused = m, True
-        if self.training and FUSE_BN_IN and self.dtype == DV_F32:
-            for op in self.ops:
-                if not isinstance(op, BNGroupOp):
-                    continue
-                for m in op.members:
-                    if (m.res is not None or m.fused_pool is not None or m.conv_bias is not None
-                            or (self.with_grad and m.relu and not m.mask_from_x)):
-                        continue
-                    y = m.y
-                    readers = [o for o in self.ops if o is not op and any(
-                        r is not None and r.buf is y.buf for r in [getattr(o, 'x', None), getattr(o, 'cat', None)] +
-                        [t for mm in getattr(o, 'members', ()) for t in (mm.x, mm.res)])]
-                    if len(readers) != 1 or not isinstance(readers[0], ConvOp):
-                        continue
-                    cop = readers[0]
-                    if (cop.fp8 or cop.bn_in is not None or cop.x.buf is not y.buf or cop.x.off != y.off or cop.x.C != y.C
-                            or m.x.cpitch != cop.slot.cin_pitch or m.x.rows != y.rows or m.x.C != y.C):
-                        continue
-                    d = ops.conv_desc(cop.dtype, m.x, cop.y, cop.k, cop.s, cop.p, flags=cop.d.flags)
-                    if not int(self.lib.dv_conv3d_bn_in_ok(C.byref(d))) or ops.tile_rows(d) != cop.tile_rows:
-                        continue
-                    cop.bn_in, m.fused_conv = m, cop
+        """Decide the fusions -- each pass asks the graph who reads an activation and who writes a gradient -- then emit the
+        launch lists.  The order matters: a pass sees what the ones before it took."""
+        g = PlanGraph(self.ops, self.host_reads)
+        self._fuse_pools(g)
+        g.set_accumulate_flags()
+        grad, f32 = self.with_grad and self.training, self.dtype == DV_F32
+        if grad and FUSE_BN_REDUCE:
+            for m, cop in self._bn_reduce_candidates(g):     # the atomic form (dv_conv3d_dgrad_bn)
+                cop.bn_fuse, m.reduce_fused = m, True
+        if self.training and FUSE_BN_IN and f32:
+            self._fuse_bn_in(g)
         self.bn_fuse_ws = None
-        if self.with_grad and self.training and FUSE_BN_REDUCE_TAP and self.dtype == DV_F32 and not FUSE_BN_REDUCE:
-            writers, need_ws = {}, 0
-            for op in self.ops:
-                for name, a in op.grad_targets():
-                    g = a.grad if a.grad is not None else a
-                    writers.setdefault((g.buf.data_ptr(), g.off), []).append((op, a))
-            for op in self.ops:
-                if not isinstance(op, BNGroupOp):
-                    continue
-                for m in op.members:
-                    y = m.y
-                    if y.grad is None or m.res is not None or m.fused_pool is not None or (m.relu and not m.mask_from_x):
-                        continue
-                    w = writers.get((y.grad.buf.data_ptr(), y.grad.off), [])
-                    if len(w) != 1 or not isinstance(w[0][0], ConvOp):
-                        continue
-                    cop, a = w[0]
-                    if (cop.fp8 or not cop.need_dx or cop.acc.get('x') or a.buf is not y.buf or a.off != y.off or a.C != y.C
-                            or a.rows != y.rows or cop.bn_fuse is not None or m.x.ld * 4 * (m.x.rows - 1) >= (1 << 31)):
-                        continue
-                    _, wdflag = self.store.w_dgrad(cop.slot, strided=False)
-                    if not wdflag or max(cop.s) > 1 or cop.slot.cout_pitch * cop.k[0] * cop.k[1] * cop.k[2] < FUSE_BN_REDUCE_TAP_MIN_K:
-                        continue                 # (short K loops: the epilogue's read of the BatchNorm input is not hidden)
-                    d3 = ops.conv_desc(cop.dtype, cop.x, cop.y, cop.k, cop.s, cop.p, flags=wdflag)
-                    nb = int(self.lib.dv_conv3d_dgrad_bn_workspace(C.byref(d3)))
-                    if nb <= 0:
-                        continue
-                    cop.bn_fuse, cop.bn_fuse_tap, m.reduce_fused = m, True, True
-                    need_ws = max(need_ws, nb)
-            if need_ws:
-                # one workspace for all of them (they run one after the other on the main stream; the ticket words are zero
-                # between launches, and after a failed launch: _lib.register_ticket_workspace)
-                self.bn_fuse_ws = L.register_ticket_workspace(self.f32(need_ws // 4))
-        if self.with_grad and self.training and FUSE_BN_WGRAD and self.dtype == DV_F32:
-            for op in self.ops:
-                if not isinstance(op, BNGroupOp) or len(op.members) != 1:
-                    continue
-                m = op.members[0]
-                cop = m.conv
-                if (not isinstance(cop, ConvOp) or cop.need_dx or cop.fp8 or cop.bn_apply is not None or m.res is not None
-                        or (m.relu and not m.mask_from_x) or m.x.buf is not cop.y.buf or m.x.off != cop.y.off
-                        or m.x.C != cop.y.C or m.x.grad is None or m.y.grad is None or m.x.ld != m.y.grad.ld):
-                    continue
-                d = ops.conv_desc(cop.dtype, cop.x, cop.y, cop.k, cop.s, cop.p, flags=0)
-                if d.ldy != m.y.grad.ld or not self.lib.dv_conv3d_wgrad_bn_ok(C.byref(d)):
-                    continue
-                cop.bn_apply, m.apply_fused = m, True
+        if grad and FUSE_BN_REDUCE_TAP and f32 and not FUSE_BN_REDUCE:
+            self._fuse_bn_reduce_tap(g)
+        if grad and FUSE_BN_WGRAD and f32:
+            self._fuse_bn_wgrad()
         if self.training and FUSE_GATE:
             for op in self.ops:
                 if isinstance(op, GateGroupOp):
-                    op.try_fuse()
+                    op.try_fuse(g)
+        self._emit()
+
+    def _bn_members(self, lone=False):
+        return [m for op in self.ops if isinstance(op, BNGroupOp) and not (lone and len(op.members) > 1) for m in op.members]
+
+    def _fuse_pools(self, g):
+        """A lone BatchNorm + ReLU whose output only a max-pool reads (the stems): the pool applies it while it reads its
+        windows (dv_bn_apply_maxpool / dv_bn_bwd_*_maxpool) and the output is never written -- nor kept."""
+        for m in self._bn_members(lone=True):
+            pool = g.sole_reader(m.y)
+            if isinstance(pool, PoolOp) and pool.x is m.y and m.y.off == 0 and m.plain() and m.relu and m.conv_bias is None:
+                pool.fuse_bn(m)
+                self.bytes -= m.y.buf.numel() * m.y.buf.element_size()
+                m.y.buf = m.y.buf.new_empty(0)
+
+    def _bn_reduce_candidates(self, g):
+        """conv -> BatchNorm(+ReLU) -> conv chains: when the second conv is the only writer of the gradient of the BatchNorm's
+        output, its data gradient IS dL/dy of that BatchNorm, complete after one launch -- the BatchNorm backward's reduce
+        (sum g, sum g*xhat) can run in that launch's epilogue instead of re-reading dL/dy in a pass of its own.
+        -> (member, consuming ConvOp), lazily: a conv that has taken one member is not offered another."""
+        for m in self._bn_members():
+            y = m.y
+            if y.grad is None or not m.plain() or m.fused_pool is not None:
+                continue
+            w = g.grad_writers(y)
+            if len(w) != 1 or not isinstance(w[0][0], ConvOp):
+                continue
+            cop, _, a = w[0]
+            if cop.fp8 or a.buf is not y.buf or a.off != y.off or a.C != y.C or a.rows != y.rows or cop.bn_fuse is not None:
+                continue
+            yield m, cop
+
+    def _fuse_bn_reduce_tap(self, g):
+        """the ordered form on the LDS-staged input-tile kernel (dv_conv3d_dgrad_bn_ws)"""
+        need_ws = 0
+        for m, cop in self._bn_reduce_candidates(g):
+            if m.x.ld * 4 * (m.x.rows - 1) >= (1 << 31):
+                continue
+            _, wdflag = self.store.w_dgrad(cop.slot, strided=False)
+            if not wdflag or max(cop.s) > 1 or cop.slot.cout_pitch * cop.k[0] * cop.k[1] * cop.k[2] < FUSE_BN_REDUCE_TAP_MIN_K:
+                continue                 # (short K loops: the epilogue's read of the BatchNorm input is not hidden)
+            d3 = ops.conv_desc(cop.dtype, cop.x, cop.y, cop.k, cop.s, cop.p, flags=wdflag)
+            nb = int(self.lib.dv_conv3d_dgrad_bn_workspace(C.byref(d3)))
+            if nb <= 0:
+                continue
+            cop.bn_fuse, cop.bn_fuse_tap, m.reduce_fused = m, True, True
+            need_ws = max(need_ws, nb)
+        if need_ws:
+            # one workspace for all of them (they run one after the other on the main stream; the ticket words are zero
+            # between launches, and after a failed launch: _lib.register_ticket_workspace)
+            self.bn_fuse_ws = L.register_ticket_workspace(self.f32(need_ws // 4))
+
+    def _fuse_bn_in(self, g):
+        """BatchNorm on load: the conv that alone reads a BatchNorm's output applies it while it stages the BatchNorm's input"""
+        for m in self._bn_members():
+            y, cop = m.y, g.sole_reader(m.y)
+            if not m.plain() or m.fused_pool is not None or m.conv_bias is not None or not isinstance(cop, ConvOp):
+                continue
+            if (cop.fp8 or cop.bn_in is not None or cop.x.buf is not y.buf or cop.x.off != y.off or cop.x.C != y.C
+                    or m.x.cpitch != cop.slot.cin_pitch or m.x.rows != y.rows or m.x.C != y.C):
+                continue
+            d = ops.conv_desc(cop.dtype, m.x, cop.y, cop.k, cop.s, cop.p, flags=cop.d.flags)
+            if not int(self.lib.dv_conv3d_bn_in_ok(C.byref(d))) or ops.tile_rows(d) != cop.tile_rows:
+                continue
+            cop.bn_in, m.fused_conv = m, cop
+
+    def _fuse_bn_wgrad(self):
+        """BatchNorm-backward apply inside the weight gradient of the producing conv, when that conv's input needs no gradient:
+        the weight gradient is the only reader of dL/d(conv output) then"""
+        for m in self._bn_members(lone=True):
+            cop = m.conv
+            if (not isinstance(cop, ConvOp) or cop.need_dx or cop.fp8 or cop.bn_apply is not None or not m.plain()
+                    or m.x.buf is not cop.y.buf or m.x.off != cop.y.off or m.x.C != cop.y.C or m.x.grad is None
+                    or m.y.grad is None or m.x.ld != m.y.grad.ld):
+                continue
+            d = ops.conv_desc(cop.dtype, cop.x, cop.y, cop.k, cop.s, cop.p, flags=0)
+            if d.ldy != m.y.grad.ld or not self.lib.dv_conv3d_wgrad_bn_ok(C.byref(d)):
+                continue
+            cop.bn_apply, m.apply_fused = m, True
+
+    def _emit(self):
         # scratch of the deterministic weight gradients (row-split partial tiles): ONE buffer per plan, sized for the
         # largest layer -- the plan's weight gradients all run on one stream (the side stream), each followed by its
         # reduce, so they can share it
@@ -893,7 +920,12 @@ def overlap_bn_exchange(b_list):
 class Op:
     def __init__(self, plan):
         self.plan = plan
-        self.acc = {}
+        self.acc = {}            # per grad_targets() name: this op ADDS to that gradient (PlanGraph.set_accumulate_flags)
+
+    def inputs(self):
+        """-> the activations this op's forward reads.  No default: an op that PlanGraph cannot see would let a fusion take
+        away an activation it still reads."""
+        raise NotImplementedError('%s.inputs()' % type(self).__name__)
 
     def grad_targets(self):
         return []
@@ -931,6 +963,9 @@ class ConvOp(Op):
         self.bn_fuse_tap = False     # ... in the ordered form of the LDS-staged kernel (dv_conv3d_dgrad_bn_ws)
         self.bn_apply = None         # BNMember (of this conv's output) whose backward apply this conv's weight gradient carries
         self.bn_in = None            # BNMember (of this conv's INPUT) applied on load: x is never materialised (FUSE_BN_IN)
+
+    def inputs(self):
+        return [self.x]
 
     def grad_targets(self):
         return [('x', self.x)] if self.need_dx else []
@@ -1099,7 +1134,7 @@ class BNMember:
         # y = relu(x*scale + shift) with nothing added: the backward recomputes the ReLU mask from x (which it reads for
         # xhat anyway) with the forward's expression and never touches y -- 5 tensor passes per BatchNorm instead of 7
         self.conv_bias = None        # Plan.bn(conv_bias=...)
-        self.fused_pool = None       # the PoolOp that consumes y on the fly (Plan.maxpool(sole_consumer=True))
+        self.fused_pool = None       # the PoolOp that consumes y on the fly (Plan.finalize: y's only reader)
         self.fused_conv = None       # the ConvOp that applies this BatchNorm while it stages x (Plan.finalize, FUSE_BN_IN)
         self.reduce_fused = False    # the backward reduce runs in the epilogue of the consuming conv's data gradient
         self.apply_fused = False     # the backward apply runs inside the producing conv's weight gradient (dv_conv3d_wgrad_bn)
@@ -1110,6 +1145,11 @@ class BNMember:
         # per-block partial sums + ticket of the ordered backward reduce (zero once: the kernel leaves the ticket zero)
         self.red_ws = (L.register_ticket_workspace(plan.f32(int(plan.lib.dv_bn_bwd_reduce_workspace(self.M, self.C)) // 4))
                        if plan.with_grad else None)
+
+    def plain(self):
+        """y = act(x*scale + shift) with nothing added: whoever holds x can form y itself, and the backward takes the ReLU mask
+        from x.  What every fusion of Plan.finalize asks first; each adds its own conditions."""
+        return self.res is None and (self.mask_from_x or not self.relu)
 
 
 class BNGroupOp(Op):
@@ -1130,6 +1170,9 @@ class BNGroupOp(Op):
         for m in self.members:
             m.loff = off
             off += m.width
+
+    def inputs(self):
+        return [t for m in self.members for t in (m.x, m.res) if t is not None]
 
     def grad_targets(self):
         if not self.plan.with_grad:
@@ -1368,23 +1411,25 @@ class BNGroupOp(Op):
 
 
 class PoolOp(Op):
-    def __init__(self, plan, x, k, s, p, bn_member=None):
+    def __init__(self, plan, x, k, s, p):
         super().__init__(plan)
-        self.bn_member = bn_member
-        self.x = x
+        self.bn_member = None        # the lone BatchNorm + ReLU applied while the windows are read (fuse_bn)
+        self.x, self.k, self.s, self.p = x, k, s, p
         To, Ho, Wo = ops.conv_out_dims(x, k, s, p)
         self.y = plan.act(x.N, To, Ho, Wo, x.C)
         self.idx = torch.empty(self.y.rows, cp8(x.C), dtype=torch.uint8, device=plan.device)
         plan.bytes += self.idx.numel()
         self.d = ops.pool_desc(plan.dtype, x, self.y, k, s, p)
         self.need_dx = plan.with_grad and x.grad is not None
-        if bn_member is not None:
-            # forward fused with the BatchNorm + ReLU that produces x: the windows are read from the conv output and
-            # normalised on the fly, x itself is never written (its gradient still is: the BatchNorm backward reads it)
-            bn_member.fused_pool = self
-            self.d_fused = ops.pool_desc(plan.dtype, bn_member.x, self.y, k, s, p)
-            plan.bytes -= x.buf.numel() * x.buf.element_size()
-            x.buf = x.buf.new_empty(0)
+
+    def fuse_bn(self, m):
+        """forward fused with the BatchNorm + ReLU that produces x: the windows are read from the conv output and normalised
+        on the fly, x itself is never written (its gradient still is: the BatchNorm backward reads it)"""
+        self.bn_member, m.fused_pool = m, self
+        self.d_fused = ops.pool_desc(self.plan.dtype, m.x, self.y, self.k, self.s, self.p)
+
+    def inputs(self):
+        return [self.x]
 
     def grad_targets(self):
         return [('x', self.x)] if self.need_dx else []
@@ -1430,24 +1475,24 @@ class GateGroupOp(Op):
             self.dpre, self.dmean = plan.f32(N, Ct), plan.f32(N, Ct)
         self.fused = None            # the BNMembers behind the four slices, in fcs order (try_fuse)
 
-    def try_fuse(self):
+    def inputs(self):
+        return [self.cat]
+
+    def try_fuse(self, g):
         """Plan.finalize, after the other fusions are decided: take over the forward apply of the BatchNorms that write the
-        gated slices, if every slice has one and none of them is applied or differentiated somewhere else."""
+        gated slices, if every slice has one, none of them is applied or differentiated somewhere else, and nothing reads
+        the concat before the gate has written it."""
         p, cat = self.plan, self.cat
-        owners = {}
-        for op in p.ops:
-            if isinstance(op, BNGroupOp) and len(op.members) > 1:
-                for m in op.members:
-                    if m.y.buf is cat.buf and m.y.rows == cat.rows:
-                        owners[(m.y.off - cat.off, m.C)] = m
-        ms = [owners.get((off, w)) for _, off, w in self.fcs]
-        for m in ms:
-            if (m is None or not m.relu or m.res is not None or m.conv_bias is not None or m.fused_pool is not None
-                    or m.fused_conv is not None or m.reduce_fused or m.apply_fused or m.gate is not None or m.C % 8
-                    or m.M != cat.rows or (p.with_grad and not m.mask_from_x)):
-                return
-        if len(ms) > 8 or cat.rows * (cat.C // 4) >= (1 << 31):
+        if g.readers(cat)[0] is not self or len(self.fcs) > 8 or cat.rows * (cat.C // 4) >= (1 << 31):
             return
+        ms = []
+        for _, off, w in self.fcs:
+            op, m = p.bn_out.get((_bufkey(cat), cat.off + off), (None, None))
+            if (m is None or len(op.members) < 2 or m.C != w or m.M != cat.rows or not m.plain() or not m.relu
+                    or m.conv_bias is not None or m.fused_pool is not None or m.fused_conv is not None or m.reduce_fused
+                    or m.apply_fused or m.gate is not None or m.C % 8):
+                return
+            ms.append(m)
         self.fused = ms
         for m, (_, off, _) in zip(ms, self.fcs):
             m.gate = (self, off)
@@ -1534,6 +1579,9 @@ class MeanOp(Op):
         self.x = x
         self.out = plan.f32(x.N, x.C)
         self.dout = plan.f32(x.N, x.C) if plan.with_grad else None
+
+    def inputs(self):
+        return [self.x]
 
     def grad_targets(self):
         return [('x', self.x)] if (self.plan.with_grad and self.x.grad is not None) else []
