@@ -1120,11 +1120,15 @@ def _fp8_methods():
 ConvOp._fp8_forward, ConvOp._fp8_dgrad = _fp8_methods()
 
 
+BN_PHASES = ('stats', 'apply', 'red', 'bapply')     # forward statistics and apply, backward reduce and apply: dv_bn_item's blk_*
+
+
 class BNMember:
-    """one BatchNorm of a BNGroupOp (state only; the group emits the launches)"""
+    """One BatchNorm of a BNGroupOp: its state, and the ONE description of it every launch is derived from -- item() holds each
+    pointer, flag and constant, fused() / blocks() / nbytes() say per phase who runs it, on how many blocks, over how many bytes."""
 
     def __init__(self, plan, bn, x, relu, residual, out):
-        self.bn, self.x, self.relu, self.res, self.conv = bn, x, relu, residual, x.producer
+        self.plan, self.bn, self.x, self.relu, self.res, self.conv = plan, bn, x, relu, residual, x.producer
         self.C, self.M = x.C, x.rows
         self.CP = cp8(self.C)
         self.y = out if out is not None else plan.act(x.N, x.T, x.H, x.W, x.C)
@@ -1145,11 +1149,83 @@ class BNMember:
         # per-block partial sums + ticket of the ordered backward reduce (zero once: the kernel leaves the ticket zero)
         self.red_ws = (L.register_ticket_workspace(plan.f32(int(plan.lib.dv_bn_bwd_reduce_workspace(self.M, self.C)) // 4))
                        if plan.with_grad else None)
+        self.group, self.index, self.loff = None, 0, 0      # BNGroupOp: the group, the place in it, the offset in its statistics
+        self._item = None
 
     def plain(self):
         """y = act(x*scale + shift) with nothing added: whoever holds x can form y itself, and the backward takes the ReLU mask
         from x.  What every fusion of Plan.finalize asks first; each adds its own conditions."""
         return self.res is None and (self.mask_from_x or not self.relu)
+
+    def item(self):
+        """This member as a dv_bn_item, filled once when the plan emits its launches (the accumulate flags are set by then).  The
+        blk_* prefixes stay zero: they belong to the table an item is copied into (BNGroupOp._table)."""
+        if self._item is not None:
+            return self._item
+        p, st, bn, x, y, res, conv = self.plan, self.plan.store, self.bn, self.x, self.y, self.res, self.conv
+        it = self._item = L.BnItem()
+        gs, bs = st.slot(bn.weight), st.slot(bn.bias)
+        it.gamma, it.beta = st.w_master(gs), st.w_master(bs)
+        it.running_mean, it.running_var = (t.data_ptr() if t is not None else 0 for t in (bn.running_mean, bn.running_var))
+        it.mean, it.invstd, it.scale, it.shift = (t.data_ptr() for t in (self.mean, self.invstd, self.scale, self.shift))
+        it.x, it.ldx, it.y, it.ldy = x.ptr, x.ld, y.ptr, y.ld
+        it.residual, it.ldr = (res.ptr, res.ld) if res is not None else (0, 0)
+        it.M, it.C, it.fwd_flags = self.M, self.C, DV_RELU if self.relu else 0
+        it.eps, it.momentum = float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.1)
+        if p.training:   # x may be a channel slice of a merged conv's output: columns [coff, coff+C) of a wider [2][Cout][tiles] table
+            it.partials = conv.stats.data_ptr() + 4 * (x.off - conv.y.off) * conv.tiles
+            it.n_tiles, it.tile_rows, it.pitch = conv.tiles, conv.tile_rows, conv.slot.Cout
+            it.local_stats = self.group.local.data_ptr() + 4 * self.loff
+        if p.training and p.with_grad:
+            R = p.comm.world
+            dres = res.grad if (res is not None and res.grad is not None) else None
+            it.dy, it.lddy, it.dx, it.lddx = y.grad.ptr, y.grad.ld, x.grad.ptr, x.grad.ld
+            it.dres, it.lddres = (dres.ptr, dres.ld) if dres is not None else (0, 0)
+            it.sums, it.n_rep, it.red_ws = p.zero_ptr(self.sums_off), BN_REPLICAS, self.red_ws.data_ptr()
+            it.dgamma, it.dbeta = st.w_grad(gs), st.w_grad(bs)
+            it.inv_count, it.dparam_scale = 1.0 / (self.M * R), 1.0 / R
+            it.bwd_flags = ((0 if self.relu else DV_NO_RELU_MASK) | (DV_MASK_FROM_X if self.mask_from_x else 0)
+                            | (DV_ACCUM if (dres is not None and self.group.acc.get('res%d' % self.index)) else 0))
+        return it
+
+    def fused(self, phase):
+        """a fusion of Plan.finalize runs `phase` of this member in place of the group's own launch (the apply: on load in the
+        consuming conv, in the gate or in the max-pool)"""
+        return {'stats': False, 'apply': not (self.fused_conv is None and self.gate is None and self.fused_pool is None),
+                'red': self.reduce_fused, 'bapply': self.apply_fused}[phase]
+
+    def blocks(self, phase):
+        """blocks of this member in the group's launch of `phase` (the contract of dv_bn_item's blk_*, include/dualvar_hip.h);
+        none where a fusion runs the phase"""
+        if self.fused(phase):
+            return 0
+        if phase == 'stats':
+            return self.C
+        if phase == 'red':
+            return int(self.plan.lib.dv_bn_bwd_blocks(self.M, self.C))
+        total = self.M * (self.CP // (4 if self.plan.dtype == DV_F32 else 8))
+        return max(1, min(4096 if phase == 'apply' else 2048, (total + 255) // 256))
+
+    def nbytes(self, phase):
+        """algorithmic bytes of `phase` where the group runs it"""
+        if self.fused(phase):
+            return 0
+        if phase == 'stats':
+            return self.conv.tiles * 2 * self.C * 4
+        if phase == 'apply':
+            return _abytes(self.x) * (3 if self.res is not None else 2)
+        it = self.item()
+        nact = 3 if (self.relu and not self.mask_from_x) else 2      # dy, x (and y for a mask that x does not give)
+        nres = 0 if not it.dres else (2 if it.bwd_flags & DV_ACCUM else 1)
+        return _abytes(self.x) * (nact if phase == 'red' else nact + 1 + nres)
+
+
+def _bn_apply_launch(m):
+    """y = act(x*scale + shift (+res)) of one member, in training and in eval mode"""
+    p, it = m.plan, m.item()
+    return Launch('bn_apply', 'bn_apply<%s>' % _dt(p.dtype), p.lib.dv_bn_apply,
+                  (p.dtype, it.x, it.ldx, it.scale, it.shift, it.residual, it.ldr, it.y, it.ldy, it.M, it.C, it.fwd_flags),
+                  m.nbytes('apply'), 0, 'M%d C%d' % (m.M, m.C))
 
 
 class BNGroupOp(Op):
@@ -1162,13 +1238,12 @@ class BNGroupOp(Op):
     def __init__(self, plan, specs):
         super().__init__(plan)
         self.members = [BNMember(plan, *sp) for sp in specs]
-        R = plan.comm.world
         self.width = sum(m.width for m in self.members)
         self.local = plan.f32(self.width)
-        self.gathered = plan.f32(R, self.width) if plan.comm.exchange else self.local
+        self.gathered = plan.f32(plan.comm.world, self.width) if plan.comm.exchange else self.local
         off = 0
-        for m in self.members:
-            m.loff = off
+        for i, m in enumerate(self.members):
+            m.group, m.index, m.loff = self, i, off
             off += m.width
 
     def inputs(self):
@@ -1179,235 +1254,173 @@ class BNGroupOp(Op):
             return []
         return [('res%d' % i, m.res) for i, m in enumerate(self.members) if m.res is not None and m.res.grad is not None]
 
-    def _multi(self, R, f_red, f_app, b_red, b_app):
-        p, st, lib = self.plan, self.plan.store, self.plan.lib
-        V = 4 if p.dtype == DV_F32 else 8
-        arr = (L.BnItem * len(self.members))()
-        ends = [0, 0, 0, 0]
-        for i, m in enumerate(self.members):
-            it, bn, x, y, res = arr[i], m.bn, m.x, m.y, m.res
-            gs, bs = st.slot(bn.weight), st.slot(bn.bias)
-            it.partials = m.conv.stats.data_ptr() + 4 * (x.off - m.conv.y.off) * m.conv.tiles      # [2][Cout][tiles]
-            it.local_stats = self.local.data_ptr() + 4 * m.loff
-            it.gamma, it.beta = st.w_master(gs), st.w_master(bs)
-            it.running_mean = bn.running_mean.data_ptr() if bn.running_mean is not None else 0
-            it.running_var = bn.running_var.data_ptr() if bn.running_var is not None else 0
-            it.mean, it.invstd, it.scale, it.shift = (t.data_ptr() for t in (m.mean, m.invstd, m.scale, m.shift))
-            it.x, it.ldx, it.y, it.ldy = x.ptr, x.ld, y.ptr, y.ld
-            it.residual, it.ldr = (res.ptr, res.ld) if res is not None else (0, 0)
-            it.M, it.C, it.n_tiles, it.tile_rows, it.pitch = m.M, m.C, m.conv.tiles, m.conv.tile_rows, m.conv.slot.Cout
-            it.eps, it.momentum = float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.1)
-            it.fwd_flags = DV_RELU if m.relu else 0
-            total = m.M * (m.CP // V)
-            ends[0] += m.C
-            ends[1] += 0 if (m.fused_conv is not None or m.gate is not None) else max(1, min(4096, (total + 255) // 256))
-            it.blk_stats, it.blk_apply = ends[0], ends[1]
-            if p.with_grad:
-                dres = res.grad if (res is not None and res.grad is not None) else None
-                mflag = 0 if m.relu else DV_NO_RELU_MASK
-                if m.mask_from_x:
-                    mflag |= DV_MASK_FROM_X
-                it.dy, it.lddy, it.dx, it.lddx = y.grad.ptr, y.grad.ld, x.grad.ptr, x.grad.ld
-                it.dres, it.lddres = (dres.ptr, dres.ld) if dres is not None else (0, 0)
-                it.sums, it.n_rep = p.zero_ptr(m.sums_off), BN_REPLICAS
-                it.red_ws = m.red_ws.data_ptr()
-                it.dgamma, it.dbeta = st.w_grad(gs), st.w_grad(bs)
-                it.inv_count, it.dparam_scale = 1.0 / (m.M * R), 1.0 / R
-                it.bwd_flags = mflag | (DV_ACCUM if (dres is not None and self.acc.get('res%d' % i)) else 0)
-                ends[2] += 0 if m.reduce_fused else lib.dv_bn_bwd_blocks(m.M, m.C)
-                ends[3] += 0 if m.apply_fused else max(1, min(2048, (total + 255) // 256))
-                it.blk_red, it.blk_bapply = ends[2], ends[3]
+    def _table(self):
+        """the members' items on the device, each with the running block count of every phase up to and including itself
+        -> (pointer, {phase: blocks of the whole group})"""
+        p = self.plan
+        arr = (L.BnItem * len(self.members))(*[m.item() for m in self.members])
+        ends = dict.fromkeys(BN_PHASES, 0)
+        for it, m in zip(arr, self.members):
+            for ph in BN_PHASES if p.with_grad else BN_PHASES[:2]:
+                ends[ph] += m.blocks(ph)
+                setattr(it, 'blk_' + ph, ends[ph])
         self._items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(p.device)
         p.bytes += self._items.numel()
-        tab, n, dt = self._items.data_ptr(), len(self.members), _dt(p.dtype)
-
-        def tot(lst, attr):
-            return sum(getattr(l, attr) for l in lst)
-        f_red = [Launch('bn_stats_multi', 'bn_stats_multi', lib.dv_bn_stats_multi, (tab, n, 0 if p.comm.exchange else 1, ends[0]),
-                        tot(f_red, 'bytes'))]
-        f_app = [Launch('bn_apply_multi', 'bn_apply_multi<%s>' % dt, lib.dv_bn_apply_multi, (p.dtype, tab, n, ends[1]),
-                        tot(f_app, 'bytes'))] if ends[1] else []
-        # multi-rank step: ONE finalize launch for the group after the all-gather (instead of one per member)
-        self._fin_multi = Launch('bn_finalize_multi', 'bn_finalize_multi', lib.dv_bn_finalize_multi,
-                                 (tab, n, sum((m.C + 127) // 128 for m in self.members), self.local.data_ptr(),
-                                  self.gathered.data_ptr(), R, self.width))
-        gated = [m for m in self.members if m.gate is not None]
-        if p.with_grad and gated:
-            # the group holds gated members: the `+gate` instantiations take dL/dy of those as dy*g + dmean/S on load (the
-            # other members of the launch run as before); they also read the members' columns of the two [N][Ct] tables
-            gop = gated[0].gate[0]
-            assert all(m.gate[0] is gop and not m.reduce_fused and not m.apply_fused for m in gated)
-            self._gate_off = torch.tensor([m.gate[1] if m.gate is not None else -1 for m in self.members],
-                                          dtype=torch.int32).to(p.device)
-            p.bytes += self._gate_off.numel() * 4
-            gargs = (gop.g.data_ptr(), gop.dmean.data_ptr(), gop.cat.S, gop.cat.C, self._gate_off.data_ptr())
-            gbytes = sum(8 * gop.cat.N * m.C for m in gated)
-            b_red = [Launch('bn_bwd_reduce_multi', 'bn_bwd_reduce_multi<%s>+gate' % dt, lib.dv_bn_bwd_reduce_multi_gated,
-                            (p.dtype, tab, n, ends[2]) + gargs, tot(b_red, 'bytes') + gbytes)]
-            b_app = [Launch('bn_bwd_apply_multi', 'bn_bwd_apply_multi<%s>+gate' % dt, lib.dv_bn_bwd_apply_multi_gated,
-                            (p.dtype, tab, n, ends[3], max(m.C for m in self.members)) + gargs, tot(b_app, 'bytes') + gbytes)]
-        elif p.with_grad:
-            b_red = [Launch('bn_bwd_reduce_multi', 'bn_bwd_reduce_multi<%s>' % dt, lib.dv_bn_bwd_reduce_multi,
-                            (p.dtype, tab, n, ends[2]), tot(b_red, 'bytes'))] if ends[2] else []
-            b_app = [Launch('bn_bwd_apply_multi', 'bn_bwd_apply_multi<%s>' % dt, lib.dv_bn_bwd_apply_multi,
-                            (p.dtype, tab, n, ends[3], max(m.C for m in self.members)), tot(b_app, 'bytes'))] if ends[3] else []
-        if p.with_grad:
-            if b_app:
-                b_app[0].gend = _gend(*[st.slot(t) for m in self.members for t in (m.bn.weight, m.bn.bias)])
-        return f_red, f_app, b_red, b_app
+        return self._items.data_ptr(), ends
 
     def _eval_launches(self):
         """module.eval(): y = act(x * scale + shift (+res)) with the affine map of the RUNNING statistics; no
         exchange, no update, no backward"""
-        p, st, lib, dt = self.plan, self.plan.store, self.plan.lib, _dt(self.plan.dtype)
+        st, lib = self.plan.store, self.plan.lib
         f = []
         for m in self.members:
-            bn, x, y, res = m.bn, m.x, m.y, m.res
-            gs, bs = st.slot(bn.weight), st.slot(bn.bias)
-            if bn.running_mean is None:
+            it = m.item()
+            if m.bn.running_mean is None:
                 raise NotImplementedError('eval-mode BatchNorm without running statistics')
             f.append(Launch('bn_eval_coeffs', 'bn_eval_coeffs', lib.dv_bn_eval_coeffs,
-                            (st.w_master(gs), st.w_master(bs), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                             float(bn.eps), m.C, m.scale.data_ptr(), m.shift.data_ptr())))
+                            (it.gamma, it.beta, it.running_mean, it.running_var, it.eps, it.C, it.scale, it.shift)))
             if m.conv_bias is not None:          # y = scale*(conv + b) + shift
                 f.append(Launch('bn_bias_shift', 'addcmul', lib.dv_addcmul_f32,
-                                (m.shift.data_ptr(), m.scale.data_ptr(), st.w_master(st.slot(m.conv_bias)), 1.0, m.C)))
-            if m.fused_pool is not None:
-                continue                     # applied by the pool op while it reads its windows
-            f.append(Launch('bn_apply', 'bn_apply<%s>' % dt, lib.dv_bn_apply,
-                            (p.dtype, x.ptr, x.ld, m.scale.data_ptr(), m.shift.data_ptr(),
-                             res.ptr if res is not None else 0, res.ld if res is not None else 0, y.ptr, y.ld, m.M, m.C,
-                             DV_RELU if m.relu else 0), _abytes(x) * (3 if res is not None else 2), 0, 'M%d C%d' % (m.M, m.C)))
+                                (it.shift, it.scale, st.w_master(st.slot(m.conv_bias)), 1.0, it.C)))
+            if not m.fused('apply'):             # (else: the pool op applies it while it reads its windows)
+                f.append(_bn_apply_launch(m))
         return f, []
 
+    def _exchange(self):
+        """-> (forward, backward) steps that exchange the group's statistics between the ranks: the all-gather of `local` into
+        `gathered` between the statistics and their finalize, the all-reduce of the replica sums between the backward reduce
+        and apply"""
+        p, R = self.plan, self.plan.comm.world
+        f, b = [], []
+        local, gathered, group = self.local, self.gathered, p.comm.group
+        rc = p.comm.rccl
+        if rc is not None:       # in-stream: ordered with the reduce kernels before and the finalize after, no hop
+            f.append(Launch('syncbn_allgather', 'rccl:all_gather', rc.all_gather,
+                            (local.data_ptr(), gathered.data_ptr(), self.width), 4 * self.width * (R + 1)))
+        elif p.comm.flat_gather:
+            f.append(HostStep('syncbn_allgather', lambda: dist.all_gather_into_tensor(gathered, local, group=group)))
+        else:
+            f.append(HostStep('syncbn_allgather', lambda: dist.all_gather(list(gathered.unbind(0)), local, group=group)))
+        if p.with_grad:
+            first, last = self.members[0], self.members[-1]
+            lo, n = first.sums_off, last.sums_off + last.sums_len - first.sums_off
+            pending = []
+
+            # In place on the (contiguous) replica accumulators of the group, asynchronously: Plan.finalize moves
+            # the weight-gradient kernels of the layers above between `start` and `wait`, so the exchange latency
+            # (the dominant multi-GPU cost of this path, SURVEY 8e) hides behind work that does not need it.
+            def _start():
+                pending.append(dist.all_reduce(p.zero_arena.narrow(0, lo, n), group=group, async_op=True))
+
+            def _wait():
+                pending.pop().wait()
+            if rc is not None and os.environ.get('DUALVAR_BN_BWD_ASYNC') != '1':
+                # in-stream between the group's reduce and apply kernels.  Measured (one rank, every collective issued):
+                # the two event hops of the overlapped form cost ~24 us per exchange, more than a small RCCL
+                # all-reduce inside a node takes -- step 11.71 ms overlapped vs 10.95 ms in-stream (10.74 without exchange)
+                b.append(Launch('syncbn_allreduce', 'rccl:all_reduce', lambda stream: rc.all_reduce(p.zero_ptr(lo), n, stream), (),
+                                8 * n))
+            elif rc is not None:
+                # same overlap with RCCL called directly: main --event--> exchange stream: all-reduce --event--> main
+                ev_a, ev_b = torch.cuda.Event(), torch.cuda.Event()
+                dev = p.device
+
+                def _start_direct(stream):
+                    xs = p.comm.xstream(dev)
+                    ev_a.record(torch.cuda.current_stream(dev))
+                    xs.wait_event(ev_a)
+                    L.check(rc.all_reduce(p.zero_ptr(lo), n, xs.cuda_stream), 'ncclAllReduce')
+                    ev_b.record(xs)
+
+                def _wait_direct(stream):
+                    torch.cuda.current_stream(dev).wait_event(ev_b)
+                b.append(StreamStep('syncbn_allreduce_start', _start_direct))
+                b.append(StreamStep('syncbn_allreduce_wait', _wait_direct))
+            else:
+                b.append(HostStep('syncbn_allreduce_start', _start))
+                b.append(HostStep('syncbn_allreduce_wait', _wait))
+        return f, b
+
     def launches(self):
-        p, st, lib = self.plan, self.plan.store, self.plan.lib
+        p, st, lib, ms = self.plan, self.plan.store, self.plan.lib, self.members
         if not p.training:
             return self._eval_launches()
-        R, dt = p.comm.world, _dt(p.dtype)
-        f_red, f_fin, f_app, b_red, b_app = [], [], [], [], []
-        for i, m in enumerate(self.members):
-            bn, x, y, res, Cn, M = m.bn, m.x, m.y, m.res, m.C, m.M
-            gs, bs = st.slot(bn.weight), st.slot(bn.bias)
-            rm = bn.running_mean.data_ptr() if bn.running_mean is not None else 0
-            rv = bn.running_var.data_ptr() if bn.running_var is not None else 0
-            eps, mom = float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.1)
-            local = self.local.data_ptr() + 4 * m.loff
-            outs = (m.mean.data_ptr(), m.invstd.data_ptr(), m.scale.data_ptr(), m.shift.data_ptr())
-            # x may be a channel slice of a merged conv's output: its partials are columns [coff, coff+C) of a wider table
-            coff = x.off - m.conv.y.off
-            spitch = m.conv.slot.Cout
-            sptr = m.conv.stats.data_ptr() + 4 * coff * m.conv.tiles        # partials are [2][Cout][tiles]
-            if not p.comm.exchange:
-                f_red.append(Launch('bn_stats_finalize', 'bn_reduce_stats', lib.dv_bn_stats_finalize,
-                                    (sptr, m.conv.tiles, m.conv.tile_rows, spitch, M, Cn, local, st.w_master(gs), st.w_master(bs),
-                                     eps, mom, rm, rv) + outs, m.conv.tiles * 2 * Cn * 4))
-            else:
-                f_red.append(Launch('bn_reduce_stats', 'bn_reduce_stats', lib.dv_bn_reduce_stats,
-                                    (sptr, m.conv.tiles, m.conv.tile_rows, spitch, M, Cn, local), m.conv.tiles * 2 * Cn * 4))
-                f_fin.append(Launch('bn_finalize', 'bn_finalize', lib.dv_bn_finalize,
-                                    (self.gathered.data_ptr() + 4 * m.loff, R, self.width, Cn, st.w_master(gs), st.w_master(bs),
-                                     eps, mom, rm, rv) + outs))
-            if m.fused_conv is None and m.gate is None:   # (else: the consuming conv / the gate applies it on load)
-                f_app.append(Launch('bn_apply', 'bn_apply<%s>' % dt, lib.dv_bn_apply,
-                                    (p.dtype, x.ptr, x.ld, m.scale.data_ptr(), m.shift.data_ptr(),
-                                     res.ptr if res is not None else 0, res.ld if res is not None else 0, y.ptr, y.ld, M, Cn,
-                                     DV_RELU if m.relu else 0), _abytes(x) * (3 if res is not None else 2), 0, 'M%d C%d' % (M, Cn)))
-            if p.with_grad:
-                dy = y.grad
-                mflag = 0 if m.relu else DV_NO_RELU_MASK
-                nact = 3 if (m.relu and not m.mask_from_x) else 2
-                sums = p.zero_ptr(m.sums_off)
-                if not m.reduce_fused:
-                    b_red.append(Launch('bn_bwd_reduce', 'bn_bwd_reduce<%s>' % dt, lib.dv_bn_bwd_reduce,
-                                        (p.dtype, dy.ptr, dy.ld, y.ptr, y.ld, x.ptr, x.ld, m.mean.data_ptr(), m.invstd.data_ptr(),
-                                         M, Cn, mflag, sums, BN_REPLICAS, m.red_ws.data_ptr()), _abytes(x) * nact, 0,
-                                        'M%d C%d' % (M, Cn)))
-                dres = res.grad if (res is not None and res.grad is not None) else None
-                bflags = mflag | (DV_ACCUM if (dres is not None and self.acc.get('res%d' % i)) else 0)
-                nres = 0 if dres is None else (2 if bflags & DV_ACCUM else 1)
-                if m.apply_fused:
-                    continue
+        R, dt, n, exchange = p.comm.world, _dt(p.dtype), len(ms), p.comm.exchange
+        # The form of each direction, decided here: the forward of two or more members is one multi-tensor launch per phase (the
+        # layers are small and latency bound), a lone (large) layer keeps the single-tensor kernels (1024-thread stats); the
+        # backward is multi-tensor for a lone member too when it takes the ReLU mask from x (the form that carries scale / shift).
+        fwd_multi = n > 1
+        bwd_multi = p.with_grad and (n > 1 or ms[0].mask_from_x)
+        tab, ends = self._table() if (fwd_multi or bwd_multi) else (0, None)
+        m, it = ms[0], ms[0].item()          # (the single-tensor forms: the lone member)
+        shape = 'M%d C%d' % (m.M, m.C)
+        stats_in = (it.partials, it.n_tiles, it.tile_rows, it.pitch, it.M, it.C, it.local_stats)
+        finalize = (it.gamma, it.beta, it.eps, it.momentum, it.running_mean, it.running_var, it.mean, it.invstd, it.scale, it.shift)
+        bwd_in = (p.dtype, it.dy, it.lddy, it.y, it.ldy, it.x, it.ldx, it.mean, it.invstd)
+        xf, xb = self._exchange() if exchange else ([], [])
+        nb = {ph: sum(m.nbytes(ph) for m in ms) for ph in (BN_PHASES if p.with_grad else BN_PHASES[:2])}      # bytes per phase
+
+        # forward: statistics -> exchange -> finalize -> conv bias -> apply
+        if fwd_multi:
+            f = [Launch('bn_stats_multi', 'bn_stats_multi', lib.dv_bn_stats_multi, (tab, n, 0 if exchange else 1, ends['stats']),
+                        nb['stats'])]
+        elif exchange:
+            f = [Launch('bn_reduce_stats', 'bn_reduce_stats', lib.dv_bn_reduce_stats, stats_in, nb['stats'])]
+        else:
+            f = [Launch('bn_stats_finalize', 'bn_reduce_stats', lib.dv_bn_stats_finalize, stats_in + finalize, nb['stats'])]
+        f += xf
+        if exchange and fwd_multi:       # ONE finalize launch for the group after the all-gather (instead of one per member)
+            f.append(Launch('bn_finalize_multi', 'bn_finalize_multi', lib.dv_bn_finalize_multi,
+                            (tab, n, sum((m.C + 127) // 128 for m in ms), self.local.data_ptr(), self.gathered.data_ptr(), R,
+                             self.width)))
+        elif exchange:
+            f.append(Launch('bn_finalize', 'bn_finalize', lib.dv_bn_finalize,
+                            (self.gathered.data_ptr() + 4 * m.loff, R, self.width, it.C) + finalize))
+        if any(m.conv_bias is not None and m.bn.running_mean is not None for m in ms):
+            assert n == 1                # conv bias in front of the BN: only the running mean sees it
+            f.append(Launch('bn_bias_running_mean', 'addcmul', lib.dv_addcmul_f32,
+                            (it.running_mean, st.w_master(st.slot(m.conv_bias)), 0, it.momentum, it.C)))
+        if fwd_multi and ends['apply']:
+            f.append(Launch('bn_apply_multi', 'bn_apply_multi<%s>' % dt, lib.dv_bn_apply_multi, (p.dtype, tab, n, ends['apply']),
+                            nb['apply']))
+        elif not fwd_multi and not m.fused('apply'):
+            f.append(_bn_apply_launch(m))
+        if not p.with_grad:
+            return f, []
+
+        # backward: reduce -> exchange -> apply; a phase that a fusion runs for every member is not launched
+        b_red, b_app = [], []
+        gated = [m for m in ms if m.gate is not None]
+        if bwd_multi:
+            red_fn, app_fn, suffix, gargs, gbytes = lib.dv_bn_bwd_reduce_multi, lib.dv_bn_bwd_apply_multi, '', (), 0
+            if gated:
+                # the `+gate` instantiations take dL/dy of the gated members as dy*g + dmean/S on load (the other members of
+                # the launch run as before); they also read the members' columns of the two [N][Ct] tables
+                gop = gated[0].gate[0]
+                assert all(m.gate[0] is gop and not m.reduce_fused and not m.apply_fused for m in gated)
+                self._gate_off = torch.tensor([m.gate[1] if m.gate is not None else -1 for m in ms], dtype=torch.int32).to(p.device)
+                p.bytes += self._gate_off.numel() * 4
+                red_fn, app_fn, suffix = lib.dv_bn_bwd_reduce_multi_gated, lib.dv_bn_bwd_apply_multi_gated, '+gate'
+                gargs = (gop.g.data_ptr(), gop.dmean.data_ptr(), gop.cat.S, gop.cat.C, self._gate_off.data_ptr())
+                gbytes = sum(8 * gop.cat.N * m.C for m in gated)
+            if ends['red'] or gated:
+                b_red.append(Launch('bn_bwd_reduce_multi', 'bn_bwd_reduce_multi<%s>%s' % (dt, suffix), red_fn,
+                                    (p.dtype, tab, n, ends['red']) + gargs, nb['red'] + gbytes))
+            if ends['bapply'] or gated:
+                b_app.append(Launch('bn_bwd_apply_multi', 'bn_bwd_apply_multi<%s>%s' % (dt, suffix), app_fn,
+                                    (p.dtype, tab, n, ends['bapply'], max(m.C for m in ms)) + gargs, nb['bapply'] + gbytes))
+        else:
+            if not m.fused('red'):       # (the reduce writes no dres: without DV_ACCUM)
+                b_red.append(Launch('bn_bwd_reduce', 'bn_bwd_reduce<%s>' % dt, lib.dv_bn_bwd_reduce,
+                                    bwd_in + (it.M, it.C, it.bwd_flags & ~DV_ACCUM, it.sums, it.n_rep, it.red_ws),
+                                    nb['red'], 0, shape))
+            if not m.fused('bapply'):
                 b_app.append(Launch('bn_bwd_apply', 'bn_bwd_apply<%s>' % dt, lib.dv_bn_bwd_apply,
-                                    (p.dtype, dy.ptr, dy.ld, y.ptr, y.ld, x.ptr, x.ld, m.mean.data_ptr(), m.invstd.data_ptr(),
-                                     st.w_master(gs), sums, BN_REPLICAS, 1.0 / (M * R), 1.0 / R, st.w_grad(gs), st.w_grad(bs),
-                                     x.grad.ptr, x.grad.ld, dres.ptr if dres is not None else 0,
-                                     dres.ld if dres is not None else 0, M, Cn, bflags), _abytes(x) * (nact + 1 + nres), 0,
-                                    'M%d C%d' % (M, Cn)))
-                b_app[-1].gend = _gend(gs, bs)
-        if len(self.members) > 1 or (p.with_grad and self.members[0].mask_from_x):
-            # multi-tensor launches: one per phase for the whole group (the layers are small and latency bound); also
-            # the form that carries scale / shift for the mask-from-x backward
-            f1, a1 = f_red, f_app
-            f_red, f_app, b_red, b_app = self._multi(R, f_red, f_app, b_red, b_app)
-            if len(self.members) == 1:
-                f_red, f_app = f1, a1        # a lone (large) layer keeps the single-tensor forward kernels (1024-thread stats)
-            else:
-                f_fin = [self._fin_multi]
-        if self.members[0].fused_pool is not None:
-            # y = relu(bn(x)) only feeds a max-pool: the pool op applies the BatchNorm while it reads its windows (its
-            # backward writes dL/dy as before; the BatchNorm backward takes the ReLU mask from x, so y itself is never needed)
-            f_app = []
-        f = list(f_red)
-        b = list(b_red)
-        if p.comm.exchange:
-            local, gathered, group = self.local, self.gathered, p.comm.group
-            rc = p.comm.rccl
-            if rc is not None:       # in-stream: ordered with the reduce kernels before and the finalize after, no hop
-                f.append(Launch('syncbn_allgather', 'rccl:all_gather', rc.all_gather,
-                                (local.data_ptr(), gathered.data_ptr(), self.width), 4 * self.width * (R + 1)))
-            elif p.comm.flat_gather:
-                f.append(HostStep('syncbn_allgather', lambda: dist.all_gather_into_tensor(gathered, local, group=group)))
-            else:
-                f.append(HostStep('syncbn_allgather', lambda: dist.all_gather(list(gathered.unbind(0)), local, group=group)))
-            f += f_fin
-            if p.with_grad:
-                first, last = self.members[0], self.members[-1]
-                lo, n = first.sums_off, last.sums_off + last.sums_len - first.sums_off
-                pending = []
-
-                # In place on the (contiguous) replica accumulators of the group, asynchronously: Plan.finalize moves
-                # the weight-gradient kernels of the layers above between `start` and `wait`, so the exchange latency
-                # (the dominant multi-GPU cost of this path, SURVEY 8e) hides behind work that does not need it.
-                def _start():
-                    pending.append(dist.all_reduce(p.zero_arena.narrow(0, lo, n), group=group, async_op=True))
-
-                def _wait():
-                    pending.pop().wait()
-                if rc is not None and os.environ.get('DUALVAR_BN_BWD_ASYNC') != '1':
-                    # in-stream between the group's reduce and apply kernels.  Measured (one rank, every collective issued):
-                    # the two event hops of the overlapped form cost ~24 us per exchange, more than a small RCCL
-                    # all-reduce inside a node takes -- step 11.71 ms overlapped vs 10.95 ms in-stream (10.74 without exchange)
-                    b.append(Launch('syncbn_allreduce', 'rccl:all_reduce', lambda stream: rc.all_reduce(p.zero_ptr(lo), n, stream), (),
-                                    8 * n))
-                elif rc is not None:
-                    # same overlap with RCCL called directly: main --event--> exchange stream: all-reduce --event--> main
-                    ev_a, ev_b = torch.cuda.Event(), torch.cuda.Event()
-                    dev = p.device
-
-                    def _start_direct(stream):
-                        xs = p.comm.xstream(dev)
-                        ev_a.record(torch.cuda.current_stream(dev))
-                        xs.wait_event(ev_a)
-                        L.check(rc.all_reduce(p.zero_ptr(lo), n, xs.cuda_stream), 'ncclAllReduce')
-                        ev_b.record(xs)
-
-                    def _wait_direct(stream):
-                        torch.cuda.current_stream(dev).wait_event(ev_b)
-                    b.append(StreamStep('syncbn_allreduce_start', _start_direct))
-                    b.append(StreamStep('syncbn_allreduce_wait', _wait_direct))
-                else:
-                    b.append(HostStep('syncbn_allreduce_start', _start))
-                    b.append(HostStep('syncbn_allreduce_wait', _wait))
-        for m in self.members:               # conv bias in front of the BN: only the running mean sees it
-            if m.conv_bias is not None and m.bn.running_mean is not None:
-                assert len(self.members) == 1
-                mom = float(m.bn.momentum if m.bn.momentum is not None else 0.1)
-                f.append(Launch('bn_bias_running_mean', 'addcmul', lib.dv_addcmul_f32,
-                                (m.bn.running_mean.data_ptr(), st.w_master(st.slot(m.conv_bias)), 0, mom, m.C)))
-        f += f_app
-        b += b_app
-        return f, b
+                                    bwd_in + (it.gamma, it.sums, it.n_rep, it.inv_count, it.dparam_scale, it.dgamma, it.dbeta, it.dx,
+                                              it.lddx, it.dres, it.lddres, it.M, it.C, it.bwd_flags), nb['bapply'], 0, shape))
+        for l in b_app:
+            l.gend = _gend(*[st.slot(t) for m in ms for t in (m.bn.weight, m.bn.bias)])
+        return f, b_red + xb + b_app
 
 
 class PoolOp(Op):
@@ -1538,12 +1551,8 @@ class GateGroupOp(Op):
              Launch('gate_scale', 'rowscale<%s,0>' % dt, lib.dv_gate_scale,
                     (p.dtype, cat.ptr, cat.ld, g, N, S, Ct, cat.ptr, cat.ld), 2 * _abytes(cat))]
         if self.fused:
-            # the members' own table (only what the two kernels read) and their first columns in mean / g
-            arr = (L.BnItem * len(self.fused))()
-            for it, m in zip(arr, self.fused):
-                it.x, it.ldx, it.y, it.ldy = m.x.ptr, m.x.ld, m.y.ptr, m.y.ld
-                it.scale, it.shift = m.scale.data_ptr(), m.shift.data_ptr()
-                it.M, it.C, it.fwd_flags = m.M, m.C, DV_RELU
+            # the members' own table (the two kernels read x, y, scale, shift and C of it) and their first columns in mean / g
+            arr = (L.BnItem * len(self.fused))(*[m.item() for m in self.fused])
             self._items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(p.device)
             self._gate_off = torch.tensor([off for _, off, _ in self.fcs], dtype=torch.int32).to(p.device)
             p.bytes += self._items.numel() + 4 * self._gate_off.numel()
@@ -1567,7 +1576,7 @@ class GateGroupOp(Op):
             b[1].gend = _gend(*[st.slot(fc.weight) for fc, _, _ in self.fcs])
             b[2].gend = _gend(*[st.slot(fc.bias) for fc, _, _ in self.fcs])
             if self.fused:
-                del b[3]             # (the members' BatchNorm backward forms dy*g + dmean/S on load: BNGroupOp._multi)
+                del b[3]             # (the members' BatchNorm backward forms dy*g + dmean/S on load: BNGroupOp.launches)
         return f, b
 
 

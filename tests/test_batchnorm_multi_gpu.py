@@ -1,7 +1,7 @@
 """The multi-tensor BatchNorm entries (dv_bn_stats_multi, dv_bn_finalize_multi, dv_bn_apply_multi, the ORDERED
 dv_bn_bwd_reduce_multi and dv_bn_bwd_apply_multi) against a plain float64 reference of the same operation.
 
-Every training-mode BatchNorm of the step runs through these entries (dualvar_amd/engine.py BNGroupOp._multi).  The item
+Every training-mode BatchNorm of the step runs through these entries (dualvar_amd/engine.py BNGroupOp.launches).  The item
 tables here are built from explicit tensors, never by the engine, with the engine's block-count rules; a member may be given
 0 blocks in any phase.  Two kinds of data:
 
@@ -54,7 +54,7 @@ def ceil_div(a, b):
 
 
 def n_blocks(lib, phase, M, C_, dtype):
-    """engine.BNGroupOp._multi's block counts"""
+    """engine.BNMember.blocks' block counts"""
     if phase == 'stats':
         return C_
     if phase == 'red':
@@ -275,7 +275,7 @@ def tile_partials(x, tile_rows):
 
 
 def make_table(members, lib, dev, dtype, stats_outputs=False, sums_idx=0, rank_local=None):
-    """the device dv_bn_item array with the block prefixes of engine._multi (a member may have 0 blocks in a phase)"""
+    """the device dv_bn_item array with the block prefixes of engine.BNGroupOp._table (a member may have 0 blocks in a phase)"""
     arr = (L.BnItem * len(members))()
     ends = dict.fromkeys(PHASES, 0)
     for i, m in enumerate(members):
