@@ -771,3 +771,217 @@ def test_pool_case_table_routes_and_coverage():
     for name, cap in T.WRAP_CAPS.items():
         items = T.wrap_items(name)
         assert cap * 256 < items < cap * 256 * 1.01 and items % 256 != 0, (name, items)
+
+
+BN_TABLE_ROWS = [
+    't1_r64_full', 't255_r128_one', 't257_r256_full', 't257_r224_one_sliced', 't2047_r224_one', 't2047_r64_full_sliced',
+    't2048_r64_full', 't2048_r224_one_sliced', 't2049_r128_one', 't5000_r64_full_sliced', 't5000_r64_one', 'bn1d_m2_c8',
+    'bn1d_m7_c136', 'bn1d_m128_c128', 'bn1d_m7_c512',
+    'r1_c1', 'r2_c127', 'r3_c128_wide', 'r8_c129_wide', 'r3_c230', 'r2_c2048_wide',
+    'c1', 'c3_res_views', 'c24_norelu_res', 'c83_views', 'c230_norelu', 'c2048_res', 'overcap_m220000_c40',
+    'm1_c3', 'm31_c8_nomask', 'm33_c83_accum', 'm2048_c3', 'm2049_c8_nomask_noparams', 'm20480_c83', 'm20481_c8_r2',
+    'm300000_c3_nomask', 'm300033_c8', 'c2048_m300', 'overcap_bwd_m220000_c40', 'c5120_m40_nomask_noparams']
+
+
+def test_bn_case_table_blocks_and_coverage():
+    """tests/bn_cases.py, the tables tests/test_batchnorm_single_gpu.py runs: every literal of every row against the host
+    queries (dv_bn_bwd_blocks, dv_bn_bwd_reduce_workspace) and against the launch rules the table quotes from
+    csrc/elementwise.hip -- each of which is found in the source as quoted -- and the tables as a whole reach every member of
+    bn_cases.REQUIRED and every row listed above.  A retune of dv_bn_bwd_blocks, of the 2048-tile threshold or of a grid cap
+    that moves a row off its edge is named here."""
+    from tests import bn_cases as T
+    src = open(os.path.join(ROOT, 'dualvar_amd', 'csrc', 'elementwise.hip')).read()
+    for text, count in T.QUOTED_RULES:
+        assert src.count(text) == count, 'csrc/elementwise.hip no longer reads %r %d time(s): tests/bn_cases.py quotes it' % (text, count)
+    assert (T.BLOCK, T.APPLY_CAP, T.BAPPLY_CAP, T.FOLD_GROUP, T.STATS_WIDE_FROM, T.BAPPLY_MAX_C) == (256, 4096, 2048, 32, 2048, 5120)
+    moved, seen = [], set()
+    for c in T.STATS_CASES:
+        if T.stats_threads(c.n_tiles) != c.threads:
+            moved.append('%s: expected %d threads, the rule gives %d' % (c.name, c.threads, T.stats_threads(c.n_tiles)))
+        assert 1 <= c.last_rows <= c.tile_rows and -(-T.stats_rows(c) // c.tile_rows) == c.n_tiles, c.name
+    for c in T.FINALIZE_CASES:
+        assert c.blocks == -(-c.C // 128) and c.base <= c.stride_extra and len(c.counts) >= 1, c.name
+    for c in T.APPLY_CASES:
+        for i, v in enumerate((4, 8)):
+            got = T.stride_trip(c.M, c.C, v, T.APPLY_CAP)
+            if got != (c.trip[i], c.wraps[i]):
+                moved.append('%s apply, %d-wide vectors: expected %r, the rule gives %r' % (c.name, v, (c.trip[i], c.wraps[i]), got))
+    for c in T.BWD_CASES:
+        got = T.reduce_query(c.M, c.C)
+        if got[:5] != c.red:
+            moved.append('%s reduce: expected %r, the library reports %r' % (c.name, c.red, got[:5]))
+        assert got[5] == T.workspace_bytes(got[0], c.C), (c.name, 'dv_bn_bwd_reduce_workspace')
+        for i, v in enumerate((4, 8)):
+            got = T.stride_trip(c.M, c.C, v, T.BAPPLY_CAP)
+            if got != (c.bapply[0][i], c.bapply[1][i]):
+                moved.append('%s bwd_apply, %d-wide vectors: expected %r, the rule gives %r'
+                             % (c.name, v, (c.bapply[0][i], c.bapply[1][i]), got))
+        assert T.cp8(c.C) <= T.BAPPLY_MAX_C and c.R in (1, 2) and c.res in (None, 'plain', 'accum'), c.name
+    assert not moved, '\n'.join(moved)
+    rows = T.STATS_CASES + T.FINALIZE_CASES + T.APPLY_CASES + T.BWD_CASES
+    for c in rows:
+        seen |= set(T.members(c))
+    names = [c.name for c in rows]
+    assert len(set(names)) == len(names)
+    assert names == BN_TABLE_ROWS, 'rows added, removed or reordered: list them in BN_TABLE_ROWS'
+    need = list(T.REQUIRED) + ['row:' + n for n in BN_TABLE_ROWS]
+    missing = [m for m in need if m not in seen]
+    assert not missing, 'not covered by the table: %s' % ', '.join(missing)
+    # the two rows the issue of the empty trailing blocks was written around
+    by = {c.name: c for c in T.BWD_CASES}
+    assert by['m20481_c8_r2'].red[:3] == (320, 65, 316) and by['m300033_c8'].red[:3] == (1024, 294, 1021)
+    # the host queries refuse what the launches refuse
+    from dualvar_amd import _lib
+    lib = _lib.load()
+    assert lib.dv_bn_bwd_reduce_workspace(0, 8) == 0 and lib.dv_bn_bwd_reduce_workspace(8, 0) == 0
+    assert lib.dv_bn_bwd_blocks(0, 8) == 1
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='a library without the check would launch: CPU-only hosts only')
+def test_single_tensor_bn_entries_refuse_bad_arguments():
+    """every refusal of the single-tensor BatchNorm entries and their helpers that launches nothing: in each call every other
+    argument is valid, so the named argument is the only reason to refuse (-1 DV_EINVAL, -2 DV_EALIGN, -3 DV_EUNSUPPORTED)"""
+    from dualvar_amd import _lib as L
+    lib = L.load()
+    p, q = 1 << 20, (1 << 20) + 4                # non-null and 16-byte aligned / 4-byte aligned only: nothing is dereferenced
+    M, C_, CP, eps, mom = 64, 12, 16, 1e-5, 0.1
+    F, B = L.DV_F32, L.DV_BF16
+
+    def stats(n_tiles=4, tile_rows=16, pitch=C_, M_=M, c=C_, part=p, local=p):
+        return lib.dv_bn_reduce_stats(part, n_tiles, tile_rows, pitch, M_, c, local, None)
+
+    def stats_fin(n_tiles=4, pitch=C_, M_=M, c=C_, gamma=p, rm=p, rv=p, shift=p):
+        return lib.dv_bn_stats_finalize(p, n_tiles, 16, pitch, M_, c, p, gamma, p, eps, mom, rm, rv, p, p, p, shift, None)
+
+    def fin(R=2, stride=2 * C_ + 1, c=C_, stats_=p, rm=p, rv=p, mean=p):
+        return lib.dv_bn_finalize(stats_, R, stride, c, p, p, eps, mom, rm, rv, mean, p, p, p, None)
+
+    def app(dt=F, x=p, ldx=CP, scale=p, shift=p, res=p, ldr=CP, y=p, ldy=CP, M_=M, c=C_):
+        return lib.dv_bn_apply(dt, x, ldx, scale, shift, res, ldr, y, ldy, M_, c, 0, None)
+
+    def red(dt=F, dy=p, lddy=CP, y=p, ldy=CP, x=p, ldx=CP, mean=p, M_=M, c=C_, flags=0, sums=p, n_rep=1, ws=p):
+        return lib.dv_bn_bwd_reduce(dt, dy, lddy, y, ldy, x, ldx, mean, p, M_, c, flags, sums, n_rep, ws, None)
+
+    def bapp(dt=F, dy=p, lddy=CP, y=p, ldy=CP, x=p, ldx=CP, rep=1, dgamma=p, dbeta=p, dx=p, lddx=CP, dres=p, lddres=CP, M_=M,
+             c=C_, flags=0):
+        return lib.dv_bn_bwd_apply(dt, dy, lddy, y, ldy, x, ldx, p, p, p, p, rep, 1.0 / M, 1.0, dgamma, dbeta, dx, lddx, dres,
+                                   lddres, M_, c, flags, None)
+
+    inval = [
+        # non-positive sizes, missing pointers
+        stats(n_tiles=0), stats(c=0), stats(M_=0), stats(part=None), stats(local=None),
+        stats_fin(n_tiles=0), stats_fin(c=0), stats_fin(M_=0), stats_fin(gamma=None), stats_fin(shift=None),
+        fin(R=0), fin(c=0), fin(stats_=None), fin(mean=None),
+        app(M_=0), app(c=0), app(x=None), app(y=None), app(scale=None),
+        red(M_=0), red(c=0), red(n_rep=0), red(n_rep=-1), red(dy=None), red(y=None), red(sums=None), red(mean=None),
+        bapp(M_=0), bapp(c=0), bapp(rep=0), bapp(dx=None), bapp(y=None),
+        lib.dv_bn_eval_coeffs(p, p, p, p, eps, 0, p, p, None), lib.dv_bn_eval_coeffs(p, p, p, None, eps, C_, p, p, None),
+        lib.dv_bn_eval_coeffs(p, p, p, p, eps, C_, None, p, None),
+        lib.dv_bn_rows_partials_f32(p, C_, 0, C_, p, None), lib.dv_bn_rows_partials_f32(p, C_, M, 0, p, None),
+        lib.dv_bn_rows_partials_f32(None, C_, M, C_, p, None), lib.dv_bn_rows_partials_f32(p, C_, M, C_, None, None),
+        lib.dv_addcmul_f32(p, p, p, 1.0, 0, None), lib.dv_addcmul_f32(None, p, p, 1.0, 8, None),
+        lib.dv_addcmul_f32(p, None, None, 1.0, 8, None),
+        lib.dv_fill_cols_f32(p, 0, 8, 0, 8, 0.0, None), lib.dv_fill_cols_f32(p, 4, 8, 0, 0, 0.0, None),
+        lib.dv_fill_cols_f32(None, 4, 8, 0, 8, 0.0, None), lib.dv_fill_cols_f32(p, 4, 8, -1, 4, 0.0, None),
+        # pitch < C, stride < 2C + 1, col0 + ncols > pitch
+        stats(pitch=C_ - 1), stats_fin(pitch=C_ - 1), fin(stride=2 * C_), lib.dv_bn_rows_partials_f32(p, C_ - 1, M, C_, p, None),
+        lib.dv_fill_cols_f32(p, 4, 8, 5, 4, 0.0, None), lib.dv_fill_cols_f32(p, 4, 8, 0, 9, 0.0, None),
+        # exactly one of running_mean / running_var, of dgamma / dbeta
+        stats_fin(rm=None), stats_fin(rv=None), fin(rm=None), fin(rv=None), bapp(dgamma=None), bapp(dbeta=None),
+        # pitches below CP (C = 12: CP = 16)
+        app(ldx=C_), app(ldy=C_), app(ldr=C_), red(lddy=C_), red(ldx=C_), red(ldy=C_), bapp(lddy=C_), bapp(ldx=C_),
+        bapp(ldy=C_), bapp(lddx=C_), bapp(lddres=C_),
+    ]
+    assert all(rc == -1 for rc in inval), [i for i, rc in enumerate(inval) if rc != -1]
+    # (a pitch below CP is not asked of what is not read: the residual / y / dres that is absent)
+    align = [
+        # pitches that are no multiple of the vector width (4 fp32, 8 bf16 values)
+        app(ldx=CP + 2), app(ldy=CP + 2), app(ldr=CP + 2), app(dt=B, ldx=CP + 4), app(dt=B, ldy=CP + 4), app(dt=B, ldr=CP + 4),
+        red(lddy=CP + 2), red(ldx=CP + 2), red(ldy=CP + 2), red(dt=B, lddy=CP + 4), red(dt=B, ldx=CP + 4), red(dt=B, ldy=CP + 4),
+        bapp(lddy=CP + 2), bapp(ldx=CP + 2), bapp(ldy=CP + 2), bapp(lddx=CP + 2), bapp(lddres=CP + 2), bapp(dt=B, lddx=CP + 4),
+        bapp(dt=B, lddres=CP + 4),
+        # misaligned pointers
+        app(x=q), app(y=q), app(res=q), app(scale=q), app(shift=q), red(dy=q), red(x=q), red(y=q), red(mean=q), red(ws=p + 2),
+        bapp(dy=q), bapp(x=q), bapp(y=q), bapp(dx=q), bapp(dres=q),
+    ]
+    assert all(rc == -2 for rc in align), [i for i, rc in enumerate(align) if rc != -2]
+    unsupported = [app(dt=7), red(dt=7), bapp(dt=7),
+                   # C = 5121: 3 * 5128 floats of LDS are more than 60 KiB (C = 5120 launches: tests/test_batchnorm_single_gpu.py)
+                   bapp(c=5121, lddy=5128, ldy=5128, ldx=5128, lddx=5128, lddres=5128)]
+    assert all(rc == -3 for rc in unsupported), unsupported
+    # with DV_NO_RELU_MASK y is not read: a missing, short or misaligned y is no reason to refuse (not called: it would launch)
+
+
+def test_bn_float64_references_match_torch():
+    """tests/bn_reference.py -- the references tests/test_batchnorm_single_gpu.py adds to those of the multi-tensor file -- against
+    torch's own float64 modules and autograd on the CPU: the eval-mode layer behind a biased conv, training-mode BatchNorm1d
+    with its backward and running statistics, and the R-rank combine against the statistics of the pooled rows"""
+    from tests import bn_reference as REF
+    g = torch.Generator().manual_seed(5)
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)           # noqa: E731
+    eps, mom = 1e-5, 0.1
+    # eval mode: BatchNorm3d(conv(x) + b) with running statistics, some of them zero
+    N, C_, T_, H, W = 2, 7, 3, 4, 5
+    x, b = rnd(N, C_, T_, H, W), rnd(C_)
+    bn = torch.nn.BatchNorm3d(C_, eps=eps).double().eval()
+    with torch.no_grad():
+        bn.weight.copy_(1 + 0.3 * rnd(C_))
+        bn.bias.copy_(rnd(C_))
+        bn.running_mean.copy_(rnd(C_))
+        bn.running_var.copy_(torch.rand(C_, generator=g, dtype=torch.float64))
+        bn.running_var[::3] = 0
+        want = bn(x + b.view(1, C_, 1, 1, 1))
+    rows = x.permute(0, 2, 3, 4, 1).reshape(-1, C_)                              # the kernels' [M][C] view
+    got = REF.eval_reference(rows, b, bn.running_mean, bn.running_var, bn.weight.detach(), bn.bias.detach(), eps)
+    assert torch.allclose(got, want.permute(0, 2, 3, 4, 1).reshape(-1, C_), rtol=1e-12, atol=1e-12)
+    got = REF.eval_reference(rows, None, bn.running_mean, bn.running_var, bn.weight.detach(), bn.bias.detach(), eps)
+    assert torch.allclose(got, bn(x).detach().permute(0, 2, 3, 4, 1).reshape(-1, C_), rtol=1e-12, atol=1e-12)
+    # training-mode BatchNorm1d, M = 2 and a head-sized batch
+    for M in (2, 37):
+        C_ = 9
+        x, dy = rnd(M, C_) * 1.5 + 0.4, rnd(M, C_)
+        bn1 = torch.nn.BatchNorm1d(C_, eps=eps, momentum=mom).double().train()
+        with torch.no_grad():
+            bn1.weight.copy_(1 + 0.3 * rnd(C_))
+            bn1.bias.copy_(rnd(C_))
+            bn1.running_mean.copy_(rnd(C_))
+            bn1.running_var.copy_(1 + torch.rand(C_, generator=g, dtype=torch.float64))
+        rm0, rv0 = bn1.running_mean.clone(), bn1.running_var.clone()
+        xr = x.clone().requires_grad_(True)
+        out = bn1(xr)
+        out.backward(dy)
+        r = REF.bn1d_reference(x, bn1.weight.detach(), bn1.bias.detach(), rm0, rv0, dy, eps, mom)
+        for k, w in (('y', out.detach()), ('rm', bn1.running_mean), ('rv', bn1.running_var), ('dx', xr.grad),
+                     ('dgamma', bn1.weight.grad), ('dbeta', bn1.bias.grad)):
+            assert torch.allclose(r[k], w, rtol=1e-9, atol=1e-11), (M, k)
+        assert torch.allclose(r['S'], x.sum(0)) and torch.allclose(r['M2'], x.var(0, unbiased=False) * M, rtol=1e-12)
+        assert torch.allclose(r['invstd'], (x.var(0, unbiased=False) + eps).rsqrt(), rtol=1e-12)
+    # the R-rank combine: ranks of unequal row counts (one of a single row) against the pooled rows
+    counts = (64, 65, 1, 300, 2)
+    x = rnd(sum(counts), 6) * 2 + 1
+    parts = torch.split(x, counts)
+    S_r = torch.stack([q.sum(0) for q in parts])
+    Q_r = torch.stack([((q - q.mean(0)) ** 2).sum(0) for q in parts])
+    cnt, S, mean, M2 = REF.combine(S_r, Q_r, torch.tensor(counts))
+    assert cnt == sum(counts) and torch.allclose(S, x.sum(0), rtol=1e-13) and torch.allclose(mean, x.mean(0), rtol=1e-12, atol=1e-14)
+    assert torch.allclose(M2, x.var(0, unbiased=False) * cnt, rtol=1e-12)
+
+
+def test_every_abi_entry_names_its_strongest_test():
+    """tests/abi_coverage.py maps every entry of _lib.SIGNATURES to the test file that holds its strongest reference test and
+    to the kind of that reference; each file mentions its entry.  (dv_check_device and dv_quantize_fp8_workspace are checked
+    here only to be exported with the declared signature; dv_bn_bwd_blocks and dv_bn_bwd_reduce_workspace by the case-table
+    test above.)  No BatchNorm entry is 'torch fp32 only'; what still is -- the fp8 trio -- is the next gap."""
+    from dualvar_amd import _lib
+    from tests import abi_coverage as A
+    assert set(A.ENTRY_COVERAGE) == set(_lib.SIGNATURES), sorted(set(A.ENTRY_COVERAGE) ^ set(_lib.SIGNATURES))
+    here = os.path.join(ROOT, 'tests')
+    text = {}
+    for name, (fname, kind) in A.ENTRY_COVERAGE.items():
+        assert kind in A.KINDS, (name, kind)
+        if fname not in text:
+            text[fname] = open(os.path.join(here, fname)).read()
+        assert re.search(r'\b%s\b' % name, text[fname]), '%s is not mentioned in tests/%s' % (name, fname)
+    weak = sorted(n for n, (_, k) in A.ENTRY_COVERAGE.items() if k == A.TORCH_FP32)
+    assert not [n for n in weak if n.startswith('dv_bn_') or n in ('dv_addcmul_f32', 'dv_fill_cols_f32')], weak
+    assert weak == ['dv_conv3d_dgrad_fp8', 'dv_conv3d_fwd_fp8', 'dv_quantize_fp8'], weak

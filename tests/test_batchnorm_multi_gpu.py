@@ -1,9 +1,11 @@
 """The multi-tensor BatchNorm entries (dv_bn_stats_multi, dv_bn_finalize_multi, dv_bn_apply_multi, the ORDERED
 dv_bn_bwd_reduce_multi and dv_bn_bwd_apply_multi) against a plain float64 reference of the same operation.
 
-Every training-mode BatchNorm of the step runs through these entries (dualvar_amd/engine.py BNGroupOp.launches).  The item
-tables here are built from explicit tensors, never by the engine, with the engine's block-count rules; a member may be given
-0 blocks in any phase.  Two kinds of data:
+A training-mode BatchNorm group of two or more members runs its forward through these entries, and so does the backward of
+every group and of a lone member that takes its ReLU mask from x (dualvar_amd/engine.py BNGroupOp.launches); the other lone
+members take the single-tensor entries (tests/test_batchnorm_single_gpu.py).  The item tables here are built from explicit
+tensors, never by the engine, with the engine's block-count rules; a member may be given 0 blocks in any phase.  Two kinds of
+data:
 
   (A) exactly representable: integer x in [-2, 2], g in {-1, 0, 1} (sparse), dyadic mean / invstd / scale / shift / gamma
       and dparam_scale in {1, 1/2}.  Every sum the kernels form is then exact in fp32 whatever the order (asserted on the
@@ -84,9 +86,10 @@ def bwd_reduce_chain(M, C_, dtype, nblk):
     return column_chain(ceil_div(M, nblk), cp8(C_), dtype, 2, min(32, nblk) + ceil_div(nblk, 32))
 
 
-def stats_chain(n_tiles):
-    """bn_reduce_stats_body with 256 threads: tiles per thread, the 64-lane shuffle tree, the 4 wave sums in a row"""
-    return ceil_div(n_tiles, 256) + 6 + 4
+def stats_chain(n_tiles, threads=256):
+    """bn_reduce_stats_body with `threads` threads: tiles per thread, the 64-lane shuffle tree, the threads / 64 wave sums in a
+    row (256 threads: 4; the single-tensor launch runs 1024 from 2048 tiles: 16)"""
+    return ceil_div(n_tiles, threads) + 6 + threads // 64
 
 
 # ----------------------------------------------------------------------------------------------------------- buffers
@@ -364,6 +367,8 @@ def check_finalized(m, out, S, M2, cnt, dS, dM2, rm, rv, what):
     check_bound(g('invstd'), inv, inv * rel_inv * (1 + 2 * U), f'{what} invstd')
     check_bound(g('scale'), sc, dsc * (1 + 2 * U), f'{what} scale')
     check_bound(g('shift'), sh, dsh * (1 + 2 * U), f'{what} shift')
+    if rm is None:                               # running_mean = running_var = NULL: nothing more was written
+        return
     mom = float(torch.tensor(MOM, dtype=torch.float32))
     rm0, rv0 = m.rm0.double(), m.rv0.double()
     unb = M2 / (cnt - 1) if cnt > 1 else var
@@ -374,13 +379,13 @@ def check_finalized(m, out, S, M2, cnt, dS, dM2, rm, rv, what):
     check_bound(rv[:C_].double(), rv_ref, 4 * U * ((1 - mom) * rv0.abs() + mom * unb.abs()) + mom * dunb, f'{what} running_var')
 
 
-def stats_reference(m):
+def stats_reference(m, threads=256):
     """float64 of the stored partials: S, M2, and the bounds of the kernel's fold of them (stats_chain)"""
     ps, pq = m.ps(), m.pq()
     n = m.tile_n[:, None]
     S = ps.sum(0)
     mean = S / m.M
-    chain = stats_chain(m.n_tiles)
+    chain = stats_chain(m.n_tiles, threads)
     dS = chain * U * ps.abs().sum(0)
     a = ps / n
     d = a - mean
@@ -462,11 +467,13 @@ def check_ticket_area(m, what):
     assert bool((tick == 0).all()), f'{what}: ticket words left behind'
 
 
-def check_bwd_apply(m, g, sums_in, inv_count, what, dg0=None, db0=None):
+def check_bwd_apply(m, g, sums_in, inv_count, what, dg0=None, db0=None, dsums=None, dparams=True):
     """dx = k1 g + k2 x + k3 (k1 = gamma invstd, k2 = -k1 invstd sgx inv_count, k3 = -k1 sg inv_count - k2 mean): k1 one
     rounding, k2 four, k3 <= 5 u |k3| + 10 u |k2 mean| (|k1 sg inv_count| <= |k3| + |k2 mean|), the fp32 expression
     three more -> 12 u (|k1 g| + |k2 x| + |k3| + |k2 mean|).  dres (+)= g: exact, one rounding with DV_ACCUM.
-    dgamma += dparam_scale sgx, dbeta += dparam_scale sg: two roundings."""
+    dgamma += dparam_scale sgx, dbeta += dparam_scale sg: two roundings.
+    dsums = (dsg, dsgx): what the kernel's own fp32 fold of n_rep replicas may differ by from the sums_in given here (their
+    float64 total); it enters k2, k3 and dgamma / dbeta.  dparams = False: dgamma = dbeta = NULL was passed, both stay."""
     C_, CP = m.C, m.CP
     x = m.x.val()
     sin = sums_in.double()
@@ -476,6 +483,9 @@ def check_bwd_apply(m, g, sums_in, inv_count, what, dg0=None, db0=None):
     k3 = -k1 * sg * inv_count - k2 * m.mean
     ref = k1 * g + k2 * x + k3
     bound = 12 * U * ((k1 * g).abs() + (k2 * x).abs() + k3.abs() + (k2 * m.mean).abs())
+    if dsums is not None:
+        dk2 = (k1 * m.invstd * inv_count).abs() * dsums[1]
+        bound = bound + (dk2 * x.abs() + (k1 * inv_count).abs() * dsums[0] + dk2 * m.mean.abs()) * (1 + 16 * U)
     if m.dtype == DV_BF16:
         bound = bound * (1 + BF16_U) + BF16_U * ref.abs()
     m.dx.check_frame(f'{what} dx')
@@ -493,13 +503,17 @@ def check_bwd_apply(m, g, sums_in, inv_count, what, dg0=None, db0=None):
             check_bound(m.dres.val(), dref, b, f'{what} dres')
     dg0 = m.dg0 if dg0 is None else dg0
     db0 = m.db0 if db0 is None else db0
+    if not dparams:
+        assert torch.equal(m.dgamma[:C_].double(), dg0) and torch.equal(m.dbeta[:C_].double(), db0), f'{what}: NULL dgamma / dbeta'
+        return
     dgr, dbr = dg0 + m.dscale * sgx, db0 + m.dscale * sg
     dgk, dbk = m.dgamma[:C_].double(), m.dbeta[:C_].double()
     assert bool((m.dgamma[C_:] == 0.625).all()) and bool((m.dbeta[C_:] == 0.625).all()), f'{what}: dgamma / dbeta pad lanes'
     if m.exact_dparams:
         assert torch.equal(dgk, dgr) and torch.equal(dbk, dbr), f'{what}: dgamma / dbeta not exact'
-    check_bound(dgk, dgr, 2 * U * (dg0.abs() + (m.dscale * sgx).abs()), f'{what} dgamma')
-    check_bound(dbk, dbr, 2 * U * (db0.abs() + (m.dscale * sg).abs()), f'{what} dbeta')
+    extra = (0, 0) if dsums is None else (m.dscale * dsums[0], m.dscale * dsums[1])
+    check_bound(dgk, dgr, 2 * U * (dg0.abs() + (m.dscale * sgx).abs()) + extra[1], f'{what} dgamma')
+    check_bound(dbk, dbr, 2 * U * (db0.abs() + (m.dscale * sg).abs()) + extra[0], f'{what} dbeta')
 
 
 def assert_exact_data_fits(m, g, xhat):
