@@ -107,6 +107,9 @@ def parse_args(argv=None):
     p.add_argument('--pretrain', default='', type=str)
     p.add_argument('--test', default='', type=str)
     p.add_argument('--retrieval', action='store_true')
+    p.add_argument('--knn', action='store_true', help='with --test ... --retrieval: also the weighted k-NN classifier on the same features')
+    p.add_argument('--knn_k', default=200, type=int)
+    p.add_argument('--knn_t', default=0.07, type=float)
     p.add_argument('--center_crop', action='store_true')
     p.add_argument('--five_crop', action='store_true')
     p.add_argument('--ten_crop', action='store_true')
@@ -153,6 +156,12 @@ def check_args(args, environ=None):
         refuse('unknown --optim %r: sgd or adam' % args.optim)
     if args.save_freq % args.eval_freq != 0:
         refuse('--save_freq must be a multiple of --eval_freq')
+    if args.knn and not (args.test and args.retrieval):
+        refuse('--knn votes on the retrieval features: pass --test <checkpoint> --retrieval with it')
+    if not 1 <= args.knn_k <= 256:
+        refuse('--knn_k must be between 1 and 256 (the selection kernel keeps at most 256 neighbours)')
+    if not args.knn_t > 0:
+        refuse('--knn_t must be positive')
     if args.test:
         if args.retrieval:
             if args.num_seq != 10:
@@ -508,6 +517,16 @@ def test_retrieval(model, epoch, args):
     args.logger.info('NN-Retrieval on %s:' % args.dataset)
     for k, a in acc.items():
         args.logger.info('\t%dNN acc = %.4f' % (k, a))
+    if args.knn:
+        from dualvar_amd.utils.knn import knn_eval
+        res = knn_eval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1], args.num_class, k=args.knn_k,
+                       T=args.knn_t, ks=())              # the retrieval accuracies are reported above: lists of the voters only
+        if res['k'] < args.knn_k:
+            args.logger.info('kNN classifier: k reduced from %d to the train-set size %d' % (args.knn_k, res['k']))
+        args.logger.info('kNN classifier (k=%d, T=%g) on %s: Acc@1 = %.4f Acc@5 = %.4f'
+                         % (res['k'], args.knn_t, args.dataset, res['knn_top1'], res['knn_top5']))
+        torch.save(res['idx'].cpu(), os.path.join(out_dir, '%s_knn_idx.pth.tar' % args.dataset))
+        torch.save(res['val'].cpu(), os.path.join(out_dir, '%s_knn_val.pth.tar' % args.dataset))
     return acc
 
 

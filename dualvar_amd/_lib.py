@@ -13,6 +13,7 @@ ABI_VERSION = 2              # == DV_ABI_VERSION of include/dualvar_hip.h (tests
 DV_F32, DV_BF16 = 0, 1
 DV_BIAS, DV_RELU, DV_SIGMOID, DV_ACCUM, DV_STATS, DV_NO_RELU_MASK, DV_MASK_FROM_X = 1, 2, 4, 8, 16, 32, 64
 DV_LARS_ADAPT, DV_LARS_DECAY = 1, 2
+DV_TOPK_MAX_K = 256          # == DV_TOPK_MAX_K of include/dualvar_select.h: the largest k of dv_topk_merge_f32 / dv_knn_vote
 DV_W3 = 128                  # conv fwd / dgrad in DV_F32: weights pre-split in fragment order (dv_pack_w3)
 
 _ERR = {-1: 'DV_EINVAL (inconsistent shapes / unsupported parameter)',
@@ -182,6 +183,12 @@ SIGNATURES = {
     'dv_lars_step': [P, P, P, P, P, I32, I32, F, F, F, F, F, P, I32, P, P, P],
 }
 
+# name -> argtypes of include/dualvar_select.h (the evaluation entries of csrc/select.hip)
+SELECT_SIGNATURES = {
+    'dv_topk_merge_f32': [P, I32, I32, I32, I32, I32, P, P, I32, I32, P],
+    'dv_knn_vote': [P, P, I32, I32, I32, P, I32, I32, F, P, I32, P, P],
+}
+
 _lib = None
 
 
@@ -202,7 +209,7 @@ def load():
     # same HIP runtime (loading ours first binds it to /opt/rocm's copy and every launch then reports "no device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI and this table disagree
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
