@@ -46,6 +46,7 @@ import os as _os
 _os.environ.setdefault('HIP_FORCE_DEV_KERNARG', '1')
 import argparse
 import json
+import math
 import os
 import pickle
 import random
@@ -110,6 +111,9 @@ def parse_args(argv=None):
     p.add_argument('--knn', action='store_true', help='with --test ... --retrieval: also the weighted k-NN classifier on the same features')
     p.add_argument('--knn_k', default=200, type=int)
     p.add_argument('--knn_t', default=0.07, type=float)
+    p.add_argument('--variance', action='store_true', help='with --test ... --retrieval: also the inter- / intra-video variance report of the clip features')
+    p.add_argument('--var_bins', default=64, type=int)
+    p.add_argument('--var_t', default=2.0, type=float)
     p.add_argument('--center_crop', action='store_true')
     p.add_argument('--five_crop', action='store_true')
     p.add_argument('--ten_crop', action='store_true')
@@ -162,6 +166,12 @@ def check_args(args, environ=None):
         refuse('--knn_k must be between 1 and 256 (the selection kernel keeps at most 256 neighbours)')
     if not args.knn_t > 0:
         refuse('--knn_t must be positive')
+    if args.variance and not (args.test and args.retrieval):
+        refuse('--variance reports on the retrieval clip features: pass --test <checkpoint> --retrieval with it')
+    if not 1 <= args.var_bins <= 256:
+        refuse('--var_bins must be between 1 and 256 (the pair-statistics kernel keeps at most 256 bins)')
+    if not (args.var_t >= 0 and math.isfinite(args.var_t)):
+        refuse('--var_t must be finite and not negative')
     if args.test:
         if args.retrieval:
             if args.num_seq != 10:
@@ -490,7 +500,7 @@ def test_retrieval(model, epoch, args):
     name = args.dataset + '-10clip'
     out_dir = os.path.join(os.path.dirname(args.test), args.dirname if args.dirname is not None else 'feature')
     os.makedirs(out_dir, exist_ok=True)
-    feats = {}
+    feats, clips = {}, {}
     with torch.no_grad():
         for split in ('test', 'train'):
             dataset = get_data(split, args, dataset=name, transform_mode='test', which_split=1)
@@ -510,8 +520,11 @@ def test_retrieval(model, epoch, args):
             torch.save(label, os.path.join(out_dir, '%s_%s_label.pth.tar' % (args.dataset, split)))
             with open(os.path.join(out_dir, '%s_%s_vname.pkl' % (args.dataset, split)), 'wb') as fp:
                 pickle.dump(vnames, fp)
-            torch.save(torch.cat(per_feature, dim=0), os.path.join(out_dir, '%s_%s_per_feature.pth.tar' % (args.dataset, split)))
+            per_feature = torch.cat(per_feature, dim=0)
+            torch.save(per_feature, os.path.join(out_dir, '%s_%s_per_feature.pth.tar' % (args.dataset, split)))
             feats[split] = (feature, label)
+            if args.variance:
+                clips[split] = per_feature
     acc, sim = nn_retrieval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1], ks=(1, 5, 10, 20, 50))
     torch.save(sim, os.path.join(out_dir, '%s_sim.pth.tar' % args.dataset))
     args.logger.info('NN-Retrieval on %s:' % args.dataset)
@@ -527,6 +540,21 @@ def test_retrieval(model, epoch, args):
                          % (res['k'], args.knn_t, args.dataset, res['knn_top1'], res['knn_top5']))
         torch.save(res['idx'].cpu(), os.path.join(out_dir, '%s_knn_idx.pth.tar' % args.dataset))
         torch.save(res['val'].cpu(), os.path.join(out_dir, '%s_knn_val.pth.tar' % args.dataset))
+    if args.variance:
+        from dualvar_amd.utils.variance import CATEGORIES, variance_eval
+
+        def show(v):                     # a figure whose pairs are missing is None
+            return 'n/a' if v is None else '%.4f' % v
+        for split in ('test', 'train'):
+            rep = variance_eval(clips[split], feats[split][1], bins=args.var_bins, t=args.var_t)
+            args.logger.info('Variance report on %s %s (%d clips, t=%g):' % (args.dataset, split, clips[split].shape[0] * clips[split].shape[1], args.var_t))
+            args.logger.info('\tintra-video = %s inter-video = %s ratio = %s' % tuple(show(rep[k]) for k in ('var_intra_video', 'var_inter_video', 'ratio_video')))
+            args.logger.info('\tintra-class = %s inter-class = %s ratio = %s' % tuple(show(rep[k]) for k in ('var_intra_class', 'var_inter_class', 'ratio_class')))
+            args.logger.info('\talignment = %s uniformity = %s' % (show(rep['alignment']), show(rep['uniformity'])))
+            for name in CATEGORIES:
+                args.logger.info('\tmean similarity, %s: %s over %d pairs' % (name, show(rep['categories'][name]['mean']), rep['categories'][name]['count']))
+            with open(os.path.join(out_dir, '%s_%s_variance.json' % (args.dataset, split)), 'w') as fp:
+                json.dump(rep, fp, indent=1)
     return acc
 
 

@@ -14,6 +14,7 @@ DV_F32, DV_BF16 = 0, 1
 DV_BIAS, DV_RELU, DV_SIGMOID, DV_ACCUM, DV_STATS, DV_NO_RELU_MASK, DV_MASK_FROM_X = 1, 2, 4, 8, 16, 32, 64
 DV_LARS_ADAPT, DV_LARS_DECAY = 1, 2
 DV_TOPK_MAX_K = 256          # == DV_TOPK_MAX_K of include/dualvar_select.h: the largest k of dv_topk_merge_f32 / dv_knn_vote
+DV_PAIRSTAT_MAX_BINS = 256    # == DV_PAIRSTAT_MAX_BINS of include/dualvar_pairstat.h: the most histogram bins of dv_pairstat_accum_f32
 DV_W3 = 128                  # conv fwd / dgrad in DV_F32: weights pre-split in fragment order (dv_pack_w3)
 
 _ERR = {-1: 'DV_EINVAL (inconsistent shapes / unsupported parameter)',
@@ -86,7 +87,8 @@ class GemmDesc(C.Structure):
 
 
 P, I32, I64, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-RETURNS_INT64 = ('dv_conv3d_wgrad_workspace', 'dv_conv3d_dgrad_bn_workspace', 'dv_w3_bytes', 'dv_bn_bwd_reduce_workspace', 'dv_infonce_workspace')       # everything else returns int
+RETURNS_INT64 = ('dv_conv3d_wgrad_workspace', 'dv_conv3d_dgrad_bn_workspace', 'dv_w3_bytes', 'dv_bn_bwd_reduce_workspace', 'dv_infonce_workspace',
+                 'dv_pairstat_workspace')       # everything else returns int
 CD, PD = C.POINTER(ConvDesc), C.POINTER(PoolDesc)
 
 # name -> argtypes, exactly as declared in include/dualvar_hip.h
@@ -189,6 +191,12 @@ SELECT_SIGNATURES = {
     'dv_knn_vote': [P, P, I32, I32, I32, P, I32, I32, F, P, I32, P, P],
 }
 
+# name -> argtypes of include/dualvar_pairstat.h (the pair statistics of csrc/pairstat.hip)
+PAIRSTAT_SIGNATURES = {
+    'dv_pairstat_workspace': [I32, I32],
+    'dv_pairstat_accum_f32': [P, I32, I32, I32, P, P, P, P, I64, I32, F, I32, P, P, P, I32, P, I32, P],
+}
+
 _lib = None
 
 
@@ -209,7 +217,7 @@ def load():
     # same HIP runtime (loading ours first binds it to /opt/rocm's copy and every launch then reports "no device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI and this table disagree
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
