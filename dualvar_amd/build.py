@@ -47,7 +47,8 @@ def parse_resources(text):
 
 def build_lib(force=False, verbose=False):
     hipcc = os.environ.get('HIPCC', 'hipcc')
-    hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'conv_common.hpp'), os.path.join(HERE, '..', 'include', 'dualvar_hip.h'),
+    hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'conv_common.hpp'), os.path.join(CSRC, 'ordered_fold.hpp'),
+            os.path.join(HERE, '..', 'include', 'dualvar_hip.h'),
             os.path.join(HERE, '..', 'include', 'dualvar_select.h'), os.path.join(HERE, '..', 'include', 'dualvar_pairstat.h')]
     objs = []
     procs = []

@@ -113,7 +113,8 @@ struct ConvArgs {
   const float *bn_mean, *bn_invstd, *bn_scale, *bn_shift;
   float* bn_sums;
   int bn_ldx, bn_rep, bn_mask;
-  // dv_conv3d_dgrad_bn_ws (conv_tap.hip): per-tile partial sums + tickets of the ORDERED form of that reduce (no float atomics);
+  // dv_conv3d_dgrad_bn_ws (conv_tap.hip): per-tile partial sums + tickets of the ORDERED form of that reduce (no float atomics;
+  // the hand-off is ordered_fold.hpp's);
   // bn_bytes = extent of bn_x for its buffer descriptor
   float* bn_ws;
   int bn_bytes;

@@ -32,6 +32,7 @@
 // assembly with their own counted s_waitcnt so that the compiler's wait-count pass, which cannot see the LDS-DMA weight pieces,
 // does not drain the weight pipeline in front of them.
 #include "conv_common.hpp"
+#include "ordered_fold.hpp"
 
 namespace {
 
@@ -69,28 +70,17 @@ struct TapArgs {
   int in_C, in_relu;
 };
 
-// rows / tickets of the ordered fold (the protocol of elementwise.hip's ordered_fold: sc1 stores -> s_waitcnt vmcnt(0) -> barrier ->
-// one agent-scope ticket -> the last arriver reads with sc1 loads; validated on gfx950, see the comment there)
-constexpr int kBnFoldGroup = 32, kBnRow = 128;                  // tiles per group; floats per row: [sum g | sum g xhat] x 64 columns
+// rows / tickets of the ordered fold (the protocol of ordered_fold.hpp: sc1 stores -> s_waitcnt vmcnt(0) -> barrier -> one
+// agent-scope ticket -> the last arriver reads with sc1 loads; validated on gfx950, guarded there)
+constexpr int kBnRow = 128;                                     // floats per row: [sum g | sum g xhat] x 64 columns
 // Workspace layout: [kBnTickWords ticket words][per column tile: n_mt tile rows, ngrp group rows].  The tickets have a region of
 // their own that NO launch ever stores data into: the workspace is shared by launches of different shapes (and by the passes of
 // a step), whose row regions overlap -- with the tickets behind each column tile's rows (the first version of this round) a
 // launch's partial sums landed on the ticket words of another shape's layout, and from the second pass through a plan on the
 // folds ran on garbage counts (gradients 10 % off; tools/probes/fused_reduce_twice.py, test_repeated_passes_...).
 constexpr int kBnTickWords = 16384;
-__host__ __device__ __forceinline__ int bn_ws_tick_stride(int n_mt) { return (((n_mt + kBnFoldGroup - 1) / kBnFoldGroup) + 1 + 7) & ~7; }
-static inline int64_t bn_ws_floats_per_coltile(int n_mt) {
-  const int ngrp = (n_mt + kBnFoldGroup - 1) / kBnFoldGroup;
-  return (int64_t)(n_mt + ngrp) * kBnRow;
-}
-__device__ __forceinline__ size_t bn_ws_floats_per_coltile_dev(int n_mt) {
-  const int ngrp = (n_mt + kBnFoldGroup - 1) / kBnFoldGroup;
-  return (size_t)(n_mt + ngrp) * kBnRow;
-}
-__device__ __forceinline__ void tap_coherent_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float tap_coherent_load(const float* p) {
-  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// per column tile: fold_ticket_words(n_mt) tickets in the ticket region, fold_rows_total(n_mt) rows (tile rows, group rows) behind it
+__host__ __device__ __forceinline__ int64_t bn_ws_floats_per_coltile(int n_mt) { return fold_rows_total(n_mt) * kBnRow; }
 
 // displacement of tap t (compile-time index, natural order (dh, dw) / dt; 3 x 3 and 3 x 1 x 1 windows, padding 1): a handful of
 // scalar instructions from two kernel arguments -- a table in the argument block was re-loaded (s_load + lgkmcnt(0), which also
@@ -433,7 +423,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 12
   }
   if (bn_on) {
     // ---- this tile's row of partial sums (fixed order: registers, wave halves, waves), then the ordered fold over tiles
-    constexpr int G = kBnFoldGroup;
+    constexpr int G = kFoldGroup;
     static_assert(BN == 64, "a row of partial sums is [sum g | sum g xhat] x 64 columns");
     float* redf = reinterpret_cast<float*>(dsm);                // [NW][2][BN] + the row [2][BN]; one flag word behind it
     __syncthreads();                                            // the weight stages are free
@@ -445,11 +435,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 12
       if (h == 0) { redf[(wave * 2 + 0) * BN + j * 32 + l31] = s1; redf[(wave * 2 + 1) * BN + j * 32 + l31] = s2; }
     }
     __syncthreads();
-    const int n_mt = (a.M + BM - 1) / BM, ngrp = (n_mt + G - 1) / G, grp = tile_m / G;
+    const int n_mt = (a.M + BM - 1) / BM, ngrp = fold_groups(n_mt), grp = tile_m / G;
     const int gsize = min(G, n_mt - grp * G);
-    float* rows = a.bn_ws + kBnTickWords + (size_t)tile_n * bn_ws_floats_per_coltile_dev(n_mt);
+    float* rows = a.bn_ws + kBnTickWords + (size_t)tile_n * (size_t)bn_ws_floats_per_coltile(n_mt);
     float* grows = rows + (size_t)n_mt * kBnRow;
-    unsigned* tick = reinterpret_cast<unsigned*>(a.bn_ws) + (size_t)tile_n * bn_ws_tick_stride(n_mt);      // [ngrp group tickets | 1]
+    unsigned* tick = reinterpret_cast<unsigned*>(a.bn_ws) + (size_t)tile_n * fold_ticket_words(n_mt);      // [ngrp group tickets | 1]
     unsigned* lastf = reinterpret_cast<unsigned*>(redf + (NW * 2 + 2) * BN);
     const int which = tid >> 6, cc = tid & 63;                  // tid < 128: (sum index, column)
     const bool mine = tid < kBnRow;
@@ -457,24 +447,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 12
       float t = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) t += redf[(w * 2 + which) * BN + cc];
-      tap_coherent_store(rows + (size_t)tile_m * kBnRow + tid, t);
+      coherent_store(rows + (size_t)tile_m * kBnRow + tid, t);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this tile's row has reached the coherence point ...
-    __syncthreads();
-    if (tid == 0) *lastf = (atomicAdd(tick + grp, 1u) == (unsigned)gsize - 1u) ? 1u : 0u;       // ... before its ticket is taken
-    __syncthreads();
-    if (!*lastf) return;
-    auto fold = [&](const float* src, int n) -> float {         // rows src[0 .. n) of this thread's word, in row order
-      float t = 0.f;
-      for (int b = 0; b < n; b += G) {
-        float v[G];
-#pragma unroll
-        for (int u = 0; u < G; ++u) v[u] = tap_coherent_load(src + (size_t)min(b + u, n - 1) * kBnRow + tid);
-#pragma unroll
-        for (int u = 0; u < G; ++u) t += (b + u < n) ? v[u] : 0.f;
-      }
-      return t;
-    };
+    if (!took_last_ticket(tick + grp, (unsigned)gsize, lastf)) return;
+    // rows src[0 .. n) of this thread's word, in row order (one lambda for both levels: with fold_in_order called at the two
+    // sites directly eight of this file's ten kernels took one VGPR more)
+    auto fold = [&](const float* src, int n) -> float { return fold_in_order<G>(src + tid, n, kBnRow); };
     auto finish = [&](float t) {                                // += into the caller's sums: [2][bn_cpb], real columns only
       const int c = n0 + cc;
       if (c < a.N) a.bn_sums[(size_t)which * a.bn_cpb + c] += t;
@@ -482,18 +460,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 12
     float t = mine ? fold(rows + (size_t)grp * G * kBnRow, gsize) : 0.f;
     if (ngrp == 1) {
       if (mine) finish(t);
-      if (tid == 0) __hip_atomic_store(tick, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      clear_ticket(tick);
       return;
     }
-    if (mine) tap_coherent_store(grows + (size_t)grp * kBnRow + tid, t);
-    if (tid == 0) __hip_atomic_store(tick + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) *lastf = (atomicAdd(tick + ngrp, 1u) == (unsigned)ngrp - 1u) ? 1u : 0u;
-    __syncthreads();
-    if (!*lastf) return;
+    if (mine) coherent_store(grows + (size_t)grp * kBnRow + tid, t);
+    clear_ticket(tick + grp);
+    if (!took_last_ticket(tick + ngrp, (unsigned)ngrp, lastf)) return;
     if (mine) finish(fold(grows, ngrp));
-    if (tid == 0) __hip_atomic_store(tick + ngrp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    clear_ticket(tick + ngrp);
     return;
   }
   if (flags & DV_STATS) {
@@ -828,7 +802,7 @@ static int tap_bm(const ConvArgs& a, int kind) {
 // floats of dv_conv3d_dgrad_bn_ws's workspace for a launch of `rows` rows and `np` (padded) columns
 int64_t dvt_bn_ws_floats(int64_t rows, int np) {
   const int n_mt = (int)((rows + 127) / 128), ntn = (np + 63) / 64;        // (sized for the 128-row tiles: covers both tile heights)
-  if ((int64_t)ntn * bn_ws_tick_stride(n_mt) > kBnTickWords) return 0;     // (more tickets than the ticket region holds: not fused)
+  if ((int64_t)ntn * fold_ticket_words(n_mt) > kBnTickWords) return 0;     // (more tickets than the ticket region holds: not fused)
   return kBnTickWords + (int64_t)ntn * bn_ws_floats_per_coltile(n_mt);
 }
 

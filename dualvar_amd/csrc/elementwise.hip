@@ -2,6 +2,7 @@
 // apply / backward, MaxPool3d, spatial mean, self-gating scale, optimizer.  NDHWC, 16-byte vector
 // accesses along the channel axis, fp32 math, wavefront(64)-shuffle + LDS reductions.
 #include "common.hpp"
+#include "ordered_fold.hpp"
 #include <cstdlib>
 
 namespace {
@@ -361,56 +362,18 @@ __device__ __forceinline__ void column_reduce(int64_t r_begin, int64_t r_end, in
 }
 
 // Tail of an ordered reduction over the nblk blocks of one item, each of which has stored NO = 2*CP partial sums to
-// ws[bid][NO].  Two levels, so that no single block has to walk hundreds of partial rows: the block that takes the last
-// ticket of its group of kFoldGroup blocks adds the group's rows in block order into a group row; the block that takes the
-// last group ticket adds the group rows in group order and WRITES out[NO].  The hand-off (rows -> ticket -> reader) is the
-// sc1 / s_waitcnt form described below, not agent-scope fences.  Layout of ws: [nblk][NO] rows, [ngrp][NO] group rows,
-// [ngrp + 1] ticket words (zero on entry, zero again on exit; the host re-zeroes them after a failed launch:
-// dualvar_amd/_lib.py register_ticket_workspace).
-constexpr int kFoldGroup = 32;
-static inline int64_t ordered_fold_floats(int nblk, int CP) {
-  const int ngrp = (nblk + kFoldGroup - 1) / kFoldGroup;
-  return (int64_t)(nblk + ngrp) * 2 * CP + ((ngrp + 1 + 7) & ~7);
-}
-// Rows and tickets travel as agent-scope relaxed atomics (stores / loads with sc1: coherent across the XCDs' L2s on their own),
-// ordered by a plain s_waitcnt -- NOT by agent-scope fences: a release fence is a write-back of the whole L2 (buffer_wbl2) and
-// an acquire fence an invalidate, from every one of the thousands of blocks of a launch; measured, they took the reduce
-// launches of the S3D-G step from 1.4 to 4.0 - 7.9 ms.
-// The protocol, spelled out: (1) EVERY store of a handed-off row is an sc1 (write-through, agent-coherent) store; (2) every
-// storing wave drains them with s_waitcnt vmcnt(0), then the workgroup's barrier; (3) ONE lane takes the ticket with an
-// agent-scope atomic add; (4) only the workgroup whose add returned the last ticket reads, after a barrier its ticket lane
-// joins, and EVERY load of the rows is an sc1 load to registers (never cached in the reading CU's L1).  This is the
-// "sc1 stores + drained counter + sc1 loads" hand-off measured valid on gfx950 (MI355X_MICROARCH.md, inter-workgroup
-// visibility, valid forms); it is NOT a HIP memory-model guarantee and relies on stores retiring under vmcnt on this part.
-// Hence the guard: the file refuses to build for any other target (the library's host side refuses to run elsewhere too:
-// dv_check_device).  A port would replace coherent_store / stores_done / coherent_load by plain accesses between
-// __builtin_amdgcn_fence(__ATOMIC_RELEASE / __ATOMIC_ACQUIRE, "agent").
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "ordered_fold's sc1 / s_waitcnt hand-off is validated on gfx950 only (see the comment above)"
-#endif
-__device__ __forceinline__ void coherent_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float coherent_load(const float* p) {
-  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// ws[bid][NO] (coherent_store).  Two levels, so that no single block has to walk hundreds of partial rows: the block that
+// takes the last ticket of its group of kFoldGroup blocks adds the group's rows in block order into a group row; the block
+// that takes the last group ticket adds the group rows in group order and WRITES out[NO].  The hand-off (rows -> ticket ->
+// reader) is the sc1 / s_waitcnt protocol of ordered_fold.hpp, not agent-scope fences.  Layout of ws: [nblk][NO] rows,
+// [ngrp][NO] group rows, [ngrp + 1] ticket words (zero on entry, zero again on exit).
+static inline int64_t ordered_fold_floats(int nblk, int CP) { return fold_rows_total(nblk) * 2 * CP + fold_ticket_words(nblk); }
 
 __device__ __forceinline__ void fold_rows(const float* __restrict__ rows, int n, int NO, int C, int CP, float* __restrict__ dst,
                                           bool coherent_dst) {
-  // all the loads of a batch are in flight together (one trip to the coherence point per kFoldBatch rows, not per row); a
-  // short batch re-reads its last row and adds nothing for it, so the order of the additions is the row order
-  constexpr int kFoldBatch = 32;
   for (int i = threadIdx.x; i < NO; i += blockDim.x) {
     const int c = i < CP ? i : i - CP;
-    float t = 0.f;
-    if (c < C) {
-      for (int b = 0; b < n; b += kFoldBatch) {
-        float v[kFoldBatch];
-#pragma unroll
-        for (int u = 0; u < kFoldBatch; ++u) v[u] = coherent_load(rows + (size_t)min(b + u, n - 1) * NO + i);
-#pragma unroll
-        for (int u = 0; u < kFoldBatch; ++u) t += (b + u < n) ? v[u] : 0.f;
-      }
-    }
+    const float t = c < C ? fold_in_order<32>(rows + i, n, NO) : 0.f;
     if (coherent_dst) coherent_store(dst + i, t);
     else dst[i] = t;
   }
@@ -419,29 +382,21 @@ __device__ __forceinline__ void ordered_fold(float* __restrict__ ws, uint32_t bi
   __shared__ uint32_t last;
   const int NO = 2 * CP;
   constexpr uint32_t gfold = kFoldGroup;
-  const uint32_t ngrp = (nblk + gfold - 1) / gfold, grp = bid / gfold;
+  const uint32_t ngrp = fold_groups((int)nblk), grp = bid / gfold;
   const uint32_t gsize = min(gfold, nblk - grp * gfold);
   float* grows = ws + (size_t)nblk * NO;
   uint32_t* tick = reinterpret_cast<uint32_t*>(grows + (size_t)ngrp * NO);
-  stores_done();                                     // this block's row has reached the coherence point ...
-  __syncthreads();
-  if (threadIdx.x == 0) last = (atomicAdd(tick + grp, 1u) == gsize - 1) ? 1u : 0u;       // ... before its ticket is taken
-  __syncthreads();
-  if (!last) return;
+  if (!took_last_ticket(tick + grp, gsize, &last)) return;
   if (ngrp == 1) {                                   // one group: its last block writes the result (0 + the group row: same bits)
     fold_rows(ws, (int)gsize, NO, C, CP, out, false);
-    if (threadIdx.x == 0) __hip_atomic_store(tick, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    clear_ticket(tick);
     return;
   }
   fold_rows(ws + (size_t)grp * gfold * NO, (int)gsize, NO, C, CP, grows + (size_t)grp * NO, true);
-  if (threadIdx.x == 0) __hip_atomic_store(tick + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  stores_done();
-  __syncthreads();
-  if (threadIdx.x == 0) last = (atomicAdd(tick + ngrp, 1u) == ngrp - 1) ? 1u : 0u;
-  __syncthreads();
-  if (!last) return;
+  clear_ticket(tick + grp);
+  if (!took_last_ticket(tick + ngrp, ngrp, &last)) return;
   fold_rows(grows, (int)ngrp, NO, C, CP, out, false);
-  if (threadIdx.x == 0) __hip_atomic_store(tick + ngrp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  clear_ticket(tick + ngrp);
 }
 
 template <typename T, bool GATE = false>

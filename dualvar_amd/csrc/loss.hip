@@ -3,6 +3,7 @@
 // cross-entropy that also emits the reference-ordered logits, the top-k rank of the positive
 // and the gradient w.r.t. the similarity matrix.  See include/dualvar_hip.h for the citations.
 #include "common.hpp"
+#include "ordered_fold.hpp"
 
 namespace {
 
@@ -219,41 +220,24 @@ __global__ __launch_bounds__(256) void gemm_f32_splitk_kernel(int M, int N, int 
   // Ordered form: the slice's 32x32 partial goes to ws[slice][tile][16][64]; the workgroup that takes the last ticket of its
   // tile adds the slices in order and writes C -- no float atomics, the result does not depend on the arrival order.
   float* part = ws + ((size_t)slice * tiles + tile) * 1024;
-  // (partial tiles and tickets as agent-scope relaxed atomics ordered by s_waitcnt, not by agent-scope fences: see
-  // elementwise.hip, ordered_fold)
+  // (partial tiles and tickets travel by the sc1 / s_waitcnt hand-off of ordered_fold.hpp, not by agent-scope fences)
   if (wave == 0) {
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      __hip_atomic_store(part + r * 64 + lane, ((acc[r] + red[0][r][lane]) + red[1][r][lane]) + red[2][r][lane], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
+      coherent_store(part + r * 64 + lane, ((acc[r] + red[0][r][lane]) + red[1][r][lane]) + red[2][r][lane]);
   }
   uint32_t* ticket = reinterpret_cast<uint32_t*>(ws + (size_t)splits * tiles * 1024) + tile;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) last = (atomicAdd(ticket, 1u) == (uint32_t)splits - 1) ? 1u : 0u;
-  __syncthreads();
-  if (!last) return;
+  if (!took_last_ticket(ticket, (uint32_t)splits, &last)) return;
   for (int i = threadIdx.x; i < 1024; i += 256) {
     const int r = i >> 6, ln = i & 63;
     const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5), col = n0 + (ln & 31);
-    float t = 0.f;
-    const float* src = ws + (size_t)tile * 1024 + i;
-    const size_t pitch = (size_t)tiles * 1024;
-    int sl = 0;
-    for (; sl + 8 <= splits; sl += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = __hip_atomic_load(const_cast<float*>(src) + (size_t)(sl + u) * pitch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t += v[u];
-    }
-    for (; sl < splits; ++sl) t += __hip_atomic_load(const_cast<float*>(src) + (size_t)sl * pitch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float t = fold_in_order<8>(ws + (size_t)tile * 1024 + i, splits, (size_t)tiles * 1024);
     if (row < M && col < N) {
       float* c = C + (int64_t)row * ldc + col;
       *c = accumulate ? *c + alpha * t : alpha * t;
     }
   }
-  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  clear_ticket(ticket);
 }
 
 __global__ void zero_matrix_kernel(float* __restrict__ C, int64_t ldc, int M, int N) {

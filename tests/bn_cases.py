@@ -32,8 +32,9 @@ def ceil_div(a, b):
     return -(-a // b)
 
 
-# the rules above as csrc/elementwise.hip spells them: (text, occurrences).  The case-table test finds each in the source, so
-# a block size, cap or limit that is retuned there has to be retuned in this file's rules (and rows) too.
+# the rules above as csrc/elementwise.hip spells them: (text, occurrences), and for a rule that lives in another file of csrc
+# that file's name.  The case-table test finds each in its source, so a block size, cap or limit that is retuned there has to
+# be retuned in this file's rules (and rows) too.
 QUOTED_RULES = [
     ('constexpr int kThreads = 256;', 1),
     ('static inline int grid_for(int64_t work_items, int max_blocks = 4096) {', 1),
@@ -43,7 +44,7 @@ QUOTED_RULES = [
     ('int grid = grid_for(total, 2048);', 1),                                      # dv_bn_bwd_apply
     ('if (3 * CP * 4 > 60 * 1024) return DV_EUNSUPPORTED;', 1),
     ('const int64_t rpb = (M + blocks - 1) / blocks;', 2),                         # dv_bn_bwd_reduce (and its max-pool twin)
-    ('constexpr int kFoldGroup = 32;', 1),
+    ('constexpr int kFoldGroup = 32;', 1, 'ordered_fold.hpp'),                      # shared with the other ordered folds
     ('for (int cvb = 0; cvb < CV; cvb += kThreads) {', 1),                         # column_reduce
 ]
 
@@ -151,7 +152,8 @@ def reduce_query(M, C_):
 
 
 def workspace_bytes(blocks, C_):
-    """ordered_fold_floats: [blocks][2 CP] rows, [groups][2 CP] group rows, groups + 1 ticket words rounded up to 8"""
+    """ordered_fold_floats (on ordered_fold.hpp's layout functions): [blocks][2 CP] rows, [groups][2 CP] group rows, groups + 1
+    ticket words rounded up to 8"""
     g = ceil_div(blocks, FOLD_GROUP)
     return 4 * ((blocks + g) * 2 * cp8(C_) + ((g + 1 + 7) & ~7))
 

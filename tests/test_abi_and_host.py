@@ -786,13 +786,17 @@ BN_TABLE_ROWS = [
 def test_bn_case_table_blocks_and_coverage():
     """tests/bn_cases.py, the tables tests/test_batchnorm_single_gpu.py runs: every literal of every row against the host
     queries (dv_bn_bwd_blocks, dv_bn_bwd_reduce_workspace) and against the launch rules the table quotes from
-    csrc/elementwise.hip -- each of which is found in the source as quoted -- and the tables as a whole reach every member of
-    bn_cases.REQUIRED and every row listed above.  A retune of dv_bn_bwd_blocks, of the 2048-tile threshold or of a grid cap
+    csrc/elementwise.hip (the fold's group size: csrc/ordered_fold.hpp) -- each of which is found in its source as quoted --
+    and the tables as a whole reach every member of bn_cases.REQUIRED and every row listed above.  A retune of dv_bn_bwd_blocks, of the 2048-tile threshold or of a grid cap
     that moves a row off its edge is named here."""
     from tests import bn_cases as T
-    src = open(os.path.join(ROOT, 'dualvar_amd', 'csrc', 'elementwise.hip')).read()
-    for text, count in T.QUOTED_RULES:
-        assert src.count(text) == count, 'csrc/elementwise.hip no longer reads %r %d time(s): tests/bn_cases.py quotes it' % (text, count)
+    homes = ('elementwise.hip', 'ordered_fold.hpp')
+    src = {f: open(os.path.join(ROOT, 'dualvar_amd', 'csrc', f)).read() for f in homes}
+    for text, count, *home in T.QUOTED_RULES:
+        home = home[0] if home else 'elementwise.hip'
+        for f in homes:                 # as often as quoted in the file the rule lives in, and not in the other
+            want = count if f == home else 0
+            assert src[f].count(text) == want, 'csrc/%s no longer reads %r %d time(s): tests/bn_cases.py quotes it' % (f, text, want)
     assert (T.BLOCK, T.APPLY_CAP, T.BAPPLY_CAP, T.FOLD_GROUP, T.STATS_WIDE_FROM, T.BAPPLY_MAX_C) == (256, 4096, 2048, 32, 2048, 5120)
     moved, seen = [], set()
     for c in T.STATS_CASES:
@@ -985,3 +989,18 @@ def test_every_abi_entry_names_its_strongest_test():
     weak = sorted(n for n, (_, k) in A.ENTRY_COVERAGE.items() if k == A.TORCH_FP32)
     assert not [n for n in weak if n.startswith('dv_bn_') or n in ('dv_addcmul_f32', 'dv_fill_cols_f32')], weak
     assert weak == ['dv_conv3d_dgrad_fp8', 'dv_conv3d_fwd_fp8', 'dv_quantize_fp8'], weak
+
+
+def test_ordered_fold_protocol_has_one_home():
+    """The ticketed hand-off of the ordered reductions (sc1 stores, drained counter, agent-scope ticket, sc1 loads) lies outside
+    the HIP memory model and is guarded for gfx950 in csrc/ordered_fold.hpp; its three users (elementwise.hip, conv_tap.hip,
+    loss.hip) call that header.  So no other source spells an agent-scope atomic of its own, and loss.hip no longer carries
+    a bare drain: a fourth copy of the protocol would fail here."""
+    csrc = os.path.join(ROOT, 'dualvar_amd', 'csrc')
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(('.hip', '.hpp')))
+    assert 'ordered_fold.hpp' in files and len(files) >= 14
+    holders = [f for f in files if '__HIP_MEMORY_SCOPE_AGENT' in open(os.path.join(csrc, f)).read()]
+    assert holders == ['ordered_fold.hpp'], holders
+    loss = open(os.path.join(csrc, 'loss.hip')).read()
+    assert not re.search(r's_waitcnt\s+vmcnt\(0\)"\s*:\s*:\s*:\s*"memory"', loss)
+    assert '#include "ordered_fold.hpp"' in loss
