@@ -114,6 +114,11 @@ def parse_args(argv=None):
     p.add_argument('--variance', action='store_true', help='with --test ... --retrieval: also the inter- / intra-video variance report of the clip features')
     p.add_argument('--var_bins', default=64, type=int)
     p.add_argument('--var_t', default=2.0, type=float)
+    p.add_argument('--tsne', action='store_true', help='with --test ... --retrieval: also the t-SNE map of the clip features')
+    p.add_argument('--tsne_perplexity', default=30, type=int)
+    p.add_argument('--tsne_iter', default=1000, type=int)
+    p.add_argument('--tsne_seed', default=0, type=int)
+    p.add_argument('--tsne_split', default='test', choices=['test', 'train', 'both'])
     p.add_argument('--center_crop', action='store_true')
     p.add_argument('--five_crop', action='store_true')
     p.add_argument('--ten_crop', action='store_true')
@@ -172,6 +177,14 @@ def check_args(args, environ=None):
         refuse('--var_bins must be between 1 and 256 (the pair-statistics kernel keeps at most 256 bins)')
     if not (args.var_t >= 0 and math.isfinite(args.var_t)):
         refuse('--var_t must be finite and not negative')
+    if args.tsne and not (args.test and args.retrieval):
+        refuse('--tsne maps the retrieval clip features: pass --test <checkpoint> --retrieval with it')
+    if args.tsne_perplexity < 2:
+        refuse('--tsne_perplexity must be at least 2')
+    if 3 * args.tsne_perplexity + 1 > 256:
+        refuse('--tsne_perplexity must be at most 85 (the selection kernel keeps at most 256 neighbours, 3 * perplexity + 1 of them are needed)')
+    if args.tsne_iter < 1:
+        refuse('--tsne_iter must be at least 1')
     if args.test:
         if args.retrieval:
             if args.num_seq != 10:
@@ -523,7 +536,7 @@ def test_retrieval(model, epoch, args):
             per_feature = torch.cat(per_feature, dim=0)
             torch.save(per_feature, os.path.join(out_dir, '%s_%s_per_feature.pth.tar' % (args.dataset, split)))
             feats[split] = (feature, label)
-            if args.variance:
+            if args.variance or args.tsne:
                 clips[split] = per_feature
     acc, sim = nn_retrieval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1], ks=(1, 5, 10, 20, 50))
     torch.save(sim, os.path.join(out_dir, '%s_sim.pth.tar' % args.dataset))
@@ -555,7 +568,46 @@ def test_retrieval(model, epoch, args):
                 args.logger.info('\tmean similarity, %s: %s over %d pairs' % (name, show(rep['categories'][name]['mean']), rep['categories'][name]['count']))
             with open(os.path.join(out_dir, '%s_%s_variance.json' % (args.dataset, split)), 'w') as fp:
                 json.dump(rep, fp, indent=1)
+    if args.tsne:
+        for split in (('test', 'train') if args.tsne_split == 'both' else (args.tsne_split,)):
+            write_tsne(clips[split], feats[split][1], split, out_dir, args)
     return acc
+
+
+def write_tsne(per_feature, label, split, out_dir, args):
+    """--tsne: the t-SNE map of one split's clip features -> <dataset>_<split>_tsne.{pth.tar, json, png}; the only writer of
+    these three files"""
+    from dualvar_amd.utils.embed import tsne_eval
+    n = per_feature.shape[0] * per_feature.shape[1]
+    y, trace, rep, k = tsne_eval(per_feature, label, perplexity=args.tsne_perplexity, n_iter=args.tsne_iter, seed=args.tsne_seed)
+    if k < 3 * args.tsne_perplexity:
+        args.logger.info('t-SNE: neighbours per clip reduced from %d to %d, the %s split holds %d clips'
+                         % (3 * args.tsne_perplexity, k, split, n))
+    args.logger.info('t-SNE map of %s %s (%d clips, perplexity=%d, %d iterations): CE = %.4f Z = %.4g'
+                     % (args.dataset, split, n, args.tsne_perplexity, args.tsne_iter, trace['ce'][-1], trace['z'][-1]))
+    args.logger.info('\tpurity video = %.4f purity class = %.4f kNN preservation = %.4f (k=%d)'
+                     % (rep['purity_video'], rep['purity_class'], rep['knn_preservation'], rep['k']))
+    stem = os.path.join(out_dir, '%s_%s_tsne' % (args.dataset, split))
+    torch.save(y, stem + '.pth.tar')
+    with open(stem + '.json', 'w') as fp:
+        json.dump({'perplexity': args.tsne_perplexity, 'n_iter': args.tsne_iter, 'seed': args.tsne_seed, 'neighbours': k, 'n': n,
+                   'trace': trace, 'z': trace['z'][-1], 'report': rep}, fp, indent=1)
+    try:
+        import matplotlib
+        matplotlib.use('Agg')
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return
+    lo, hi = y.min(0).values, y.max(0).values
+    xy = ((y - lo) / (hi - lo).clamp(min=1e-12)).numpy()                    # min-max scaled to [0, 1]^2, as the paper's figure
+    cls = torch.as_tensor(label).cpu().long().repeat_interleave(per_feature.shape[1]).numpy()
+    fig = plt.figure(figsize=(6, 6))
+    plt.scatter(xy[:, 0], xy[:, 1], c=cls, s=3, cmap='nipy_spectral')
+    plt.xlim(-0.02, 1.02)
+    plt.ylim(-0.02, 1.02)
+    plt.axis('off')
+    fig.savefig(stem + '.png', dpi=150, bbox_inches='tight')
+    plt.close(fig)
 
 
 # --------------------------------------------------------------------------------------------------------------- main

@@ -88,7 +88,7 @@ class GemmDesc(C.Structure):
 
 P, I32, I64, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 RETURNS_INT64 = ('dv_conv3d_wgrad_workspace', 'dv_conv3d_dgrad_bn_workspace', 'dv_w3_bytes', 'dv_bn_bwd_reduce_workspace', 'dv_infonce_workspace',
-                 'dv_pairstat_workspace')       # everything else returns int
+                 'dv_pairstat_workspace', 'dv_tsne_repulse_workspace')       # everything else returns int
 CD, PD = C.POINTER(ConvDesc), C.POINTER(PoolDesc)
 
 # name -> argtypes, exactly as declared in include/dualvar_hip.h
@@ -197,6 +197,15 @@ PAIRSTAT_SIGNATURES = {
     'dv_pairstat_accum_f32': [P, I32, I32, I32, P, P, P, P, I64, I32, F, I32, P, P, P, I32, P, I32, P],
 }
 
+# name -> argtypes of include/dualvar_tsne.h (the t-SNE entries of csrc/tsne.hip)
+TSNE_SIGNATURES = {
+    'dv_tsne_perplexity_f32': [P, P, I32, I32, I32, I32, F, P, P, P],
+    'dv_tsne_attract_f32': [P, P, P, I32, I32, I32, P, P, I32, P, P, P, P],
+    'dv_tsne_repulse_workspace': [I32, P],
+    'dv_tsne_repulse_f32': [P, I32, P, P, P, P],
+    'dv_tsne_update_f32': [P, P, P, P, P, P, I64, F, F, F, F, P],
+}
+
 _lib = None
 
 
@@ -217,7 +226,7 @@ def load():
     # same HIP runtime (loading ours first binds it to /opt/rocm's copy and every launch then reports "no device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI and this table disagree
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
