@@ -119,6 +119,12 @@ def parse_args(argv=None):
     p.add_argument('--tsne_iter', default=1000, type=int)
     p.add_argument('--tsne_seed', default=0, type=int)
     p.add_argument('--tsne_split', default='test', choices=['test', 'train', 'both'])
+    p.add_argument('--cluster', action='store_true', help='with --test ... --retrieval: also spherical k-means of the clip features, scored against the classes')
+    p.add_argument('--cluster_k', default=0, type=int, help='clusters (0: as many as the dataset has classes)')
+    p.add_argument('--cluster_iter', default=100, type=int)
+    p.add_argument('--cluster_init', default=10, type=int)
+    p.add_argument('--cluster_seed', default=0, type=int)
+    p.add_argument('--cluster_split', default='test', choices=['test', 'train', 'both'])
     p.add_argument('--center_crop', action='store_true')
     p.add_argument('--five_crop', action='store_true')
     p.add_argument('--ten_crop', action='store_true')
@@ -185,6 +191,14 @@ def check_args(args, environ=None):
         refuse('--tsne_perplexity must be at most 85 (the selection kernel keeps at most 256 neighbours, 3 * perplexity + 1 of them are needed)')
     if args.tsne_iter < 1:
         refuse('--tsne_iter must be at least 1')
+    if args.cluster and not (args.test and args.retrieval):
+        refuse('--cluster clusters the retrieval clip features: pass --test <checkpoint> --retrieval with it')
+    if not 0 <= args.cluster_k <= 4096:
+        refuse('--cluster_k must be between 0 (the class count) and 4096 (the k-means kernels keep at most 4096 clusters)')
+    if args.cluster_iter < 1:
+        refuse('--cluster_iter must be at least 1')
+    if args.cluster_init < 1:
+        refuse('--cluster_init must be at least 1')
     if args.test:
         if args.retrieval:
             if args.num_seq != 10:
@@ -536,7 +550,7 @@ def test_retrieval(model, epoch, args):
             per_feature = torch.cat(per_feature, dim=0)
             torch.save(per_feature, os.path.join(out_dir, '%s_%s_per_feature.pth.tar' % (args.dataset, split)))
             feats[split] = (feature, label)
-            if args.variance or args.tsne:
+            if args.variance or args.tsne or args.cluster:
                 clips[split] = per_feature
     acc, sim = nn_retrieval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1], ks=(1, 5, 10, 20, 50))
     torch.save(sim, os.path.join(out_dir, '%s_sim.pth.tar' % args.dataset))
@@ -571,7 +585,32 @@ def test_retrieval(model, epoch, args):
     if args.tsne:
         for split in (('test', 'train') if args.tsne_split == 'both' else (args.tsne_split,)):
             write_tsne(clips[split], feats[split][1], split, out_dir, args)
+    if args.cluster:
+        for split in (('test', 'train') if args.cluster_split == 'both' else (args.cluster_split,)):
+            write_cluster(clips[split], feats[split][1], split, out_dir, args)
     return acc
+
+
+def write_cluster(per_feature, label, split, out_dir, args):
+    """--cluster: spherical k-means of one split's clip features -> <dataset>_<split>_cluster.{json, pth.tar}; the only writer
+    of these two files"""
+    from dualvar_amd.utils.cluster import cluster_eval
+    n = per_feature.shape[0] * per_feature.shape[1]
+    k = min(args.cluster_k or args.num_class, n)
+    if k < (args.cluster_k or args.num_class):
+        args.logger.info('k-means: clusters reduced from %d to %d, the %s split holds %d clips' % (args.cluster_k or args.num_class, k, split, n))
+    fit, rep = cluster_eval(per_feature, label, k=k, n_class=args.num_class, n_iter=args.cluster_iter, n_init=args.cluster_init,
+                            seed=args.cluster_seed)
+    args.logger.info('k-means of %s %s (%d clips, k=%d, %d restarts, %d iterations, %d empty): NMI = %.4f ARI = %.4f purity = %.4f '
+                     'accuracy = %.4f video consistency = %.4f'
+                     % (args.dataset, split, n, k, args.cluster_init, fit['iterations'], fit['empty'], rep['nmi'], rep['ari'],
+                        rep['purity'], rep['accuracy'], rep['video_consistency']))
+    stem = os.path.join(out_dir, '%s_%s_cluster' % (args.dataset, split))
+    torch.save({'assign': fit['assign'].cpu(), 'centroids': fit['centroids'].cpu()}, stem + '.pth.tar')
+    with open(stem + '.json', 'w') as fp:
+        json.dump({'k': k, 'n_iter': args.cluster_iter, 'n_init': args.cluster_init, 'seed': args.cluster_seed, 'n': n,
+                   'objective': fit['objective'], 'iterations': fit['iterations'], 'restart': fit['restart'], 'empty': fit['empty'],
+                   'init_index': fit['init_index'], 'trace': fit['trace'], 'sizes': fit['sizes'], 'metrics': rep}, fp, indent=1)
 
 
 def write_tsne(per_feature, label, split, out_dir, args):
