@@ -101,5 +101,12 @@ static inline int dv_launch_status() {
   return e == hipSuccess ? 0 : (int)e;
 }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// blocks of 256 threads for a grid-stride kernel over work_items, at least 1 and at most max_blocks
+static inline int grid_for(int64_t work_items, int max_blocks = 4096) {
+  int64_t b = (work_items + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > max_blocks) b = max_blocks;
+  return (int)b;
+}
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

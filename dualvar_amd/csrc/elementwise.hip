@@ -1,6 +1,7 @@
 // Streaming (HBM-bound) kernels of the DualVar hot path on gfx950: ingest, BatchNorm statistics /
-// apply / backward, MaxPool3d, spatial mean, self-gating scale, optimizer.  NDHWC, 16-byte vector
+// apply / backward, MaxPool3d, spatial mean, self-gating scale, weight repacking.  NDHWC, 16-byte vector
 // accesses along the channel axis, fp32 math, wavefront(64)-shuffle + LDS reductions.
+// (Whatever steps a parameter arena -- SGD, Adam, LARS, EMA, the arena cast -- is in optim.hip.)
 #include "common.hpp"
 #include "ordered_fold.hpp"
 #include <cstdlib>
@@ -8,12 +9,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-static inline int grid_for(int64_t work_items, int max_blocks = 4096) {
-  int64_t b = (work_items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  if (b > max_blocks) b = max_blocks;
-  return (int)b;
-}
 
 // ------------------------------------------------------------------ ingest
 template <typename T>
@@ -1580,90 +1575,7 @@ __global__ void mean_kernel(const float* __restrict__ x, int n, float* __restric
   if (threadIdx.x == 0) out[0] = s / (float)n;
 }
 
-// ------------------------------------------------------------------ optimizer / arenas
-template <typename CT>
-__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
-                           float lr, float mu, float wd, float gs, CT* __restrict__ copy) {
-  for (int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    if (i + 4 <= n) {
-      f32x4 pv = *reinterpret_cast<f32x4*>(p + i), gv = *reinterpret_cast<const f32x4*>(g + i),
-            bv = *reinterpret_cast<f32x4*>(buf + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float d = gv[e] * gs + wd * pv[e];
-        bv[e] = mu * bv[e] + d;
-        pv[e] = pv[e] - lr * bv[e];
-      }
-      *reinterpret_cast<f32x4*>(p + i) = pv;
-      *reinterpret_cast<f32x4*>(buf + i) = bv;
-      if (copy)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) copy[i + e] = (CT)pv[e];
-    } else {
-      for (int64_t j = i; j < n; ++j) {
-        float d = g[j] * gs + wd * p[j];
-        buf[j] = mu * buf[j] + d;
-        p[j] -= lr * buf[j];
-        if (copy) copy[j] = (CT)p[j];
-      }
-    }
-  }
-}
-// Adam (torch.optim.Adam's single-tensor form, L2 weight decay coupled into the gradient) in one pass: p, g, m, v in,
-// p, m, v and the compute copy out.  -ffp-contract=off: every operation below rounds once; sqrtf and `/` are hipcc's
-// default correctly rounded pair.  step = lr / bc1 and rsb2 = sqrt(bc2) are wave-uniform.
-__device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v, float b2, float omb1, float omb2, float eps,
-                                          float wd, float gs, float step, float sb2) {
-  const float d = g * gs + wd * p;
-  m = m + omb1 * (d - m);
-  v = b2 * v + (omb2 * d) * d;
-  const float den = sqrtf(v) / sb2 + eps;
-  p = p - step * (m / den);
-  return p;
-}
-template <typename CT>
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            int64_t n, float lr, float omb1, float b2, float omb2, float eps, float wd, float bc1, float bc2,
-                            float gs, CT* __restrict__ copy) {
-  const float step = lr / bc1, sb2 = sqrtf(bc2);
-  for (int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4) {
-    if (i + 4 <= n) {
-      f32x4 pv = *reinterpret_cast<f32x4*>(p + i), gv = *reinterpret_cast<const f32x4*>(g + i),
-            mv = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pv[e], me = mv[e], ve = vv[e];
-        adam_one(pe, gv[e], me, ve, b2, omb1, omb2, eps, wd, gs, step, sb2);
-        pv[e] = pe; mv[e] = me; vv[e] = ve;
-      }
-      *reinterpret_cast<f32x4*>(p + i) = pv;
-      *reinterpret_cast<f32x4*>(m + i) = mv;
-      *reinterpret_cast<f32x4*>(v + i) = vv;
-      if (copy)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) copy[i + e] = (CT)pv[e];
-    } else {
-      for (int64_t j = i; j < n; ++j) {
-        float pe = p[j], me = m[j], ve = v[j];
-        adam_one(pe, g[j], me, ve, b2, omb1, omb2, eps, wd, gs, step, sb2);
-        p[j] = pe; m[j] = me; v[j] = ve;
-        if (copy) copy[j] = (CT)pe;
-      }
-    }
-  }
-}
-template <typename CT>
-__global__ void ema_kernel(float* __restrict__ k, const float* __restrict__ q, int64_t n, float m, CT* __restrict__ copy) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = k[i] * m + q[i] * (1.f - m);
-    k[i] = v;
-    if (copy) copy[i] = (CT)v;
-  }
-}
-template <typename CT>
-__global__ void cast_kernel(const float* __restrict__ s, CT* __restrict__ d, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = (CT)s[i];
-}
+// ------------------------------------------------------------------ weight layout for the data gradient
 // one block per (desc, input channel c): Wd[c][tap][n] = W[n][tap][c]
 template <typename CT>
 __global__ void pack_dgrad_kernel(const float* __restrict__ master, CT* __restrict__ dst,
@@ -2324,51 +2236,6 @@ extern "C" int dv_mean_f32(const float* x, int32_t n, float* out, void* stream) 
   return dv_launch_status();
 }
 
-extern "C" int dv_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, float mu, float wd, float gs,
-                               int32_t copy_dtype, void* p_copy, void* stream) {
-  if (!p || !g || !buf || n <= 0) return DV_EINVAL;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(buf)) return DV_EALIGN;
-  const int grid = grid_for((n + 3) / 4, 2048);
-  if (p_copy && copy_dtype == DV_BF16)
-    hipLaunchKernelGGL((sgd_kernel<bf16_t>), dim3(grid), dim3(kThreads), 0, ST(stream), p, g, buf, n, lr, mu, wd, gs, (bf16_t*)p_copy);
-  else
-    hipLaunchKernelGGL((sgd_kernel<float>), dim3(grid), dim3(kThreads), 0, ST(stream), p, g, buf, n, lr, mu, wd, gs,
-                       (float*)(copy_dtype == DV_F32 ? p_copy : nullptr));
-  return dv_launch_status();
-}
-extern "C" int dv_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float omb1, float b2, float omb2, float eps,
-                       float wd, float bc1, float bc2, float gs, int32_t copy_dtype, void* p_copy, void* stream) {
-  if (!p || !g || !m || !v || n <= 0) return DV_EINVAL;
-  // eps > 0: arena padding has g = v = 0 and must stay 0, not become 0 / 0
-  if (!(eps > 0.f) || !(bc1 > 0.f) || !(bc2 > 0.f) || !(omb1 > 0.f && omb1 <= 1.f) || !(b2 >= 0.f && b2 < 1.f) ||
-      !(omb2 > 0.f && omb2 <= 1.f)) return DV_EINVAL;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return DV_EALIGN;
-  const int grid = grid_for((n + 3) / 4, 2048);
-  if (p_copy && copy_dtype == DV_BF16)
-    hipLaunchKernelGGL((adam_kernel<bf16_t>), dim3(grid), dim3(kThreads), 0, ST(stream), p, g, m, v, n, lr, omb1, b2, omb2, eps, wd, bc1,
-                       bc2, gs, (bf16_t*)p_copy);
-  else
-    hipLaunchKernelGGL((adam_kernel<float>), dim3(grid), dim3(kThreads), 0, ST(stream), p, g, m, v, n, lr, omb1, b2, omb2, eps, wd, bc1,
-                       bc2, gs, (float*)(copy_dtype == DV_F32 ? p_copy : nullptr));
-  return dv_launch_status();
-}
-extern "C" int dv_ema(float* k, const float* q, int64_t n, float m, int32_t copy_dtype, void* k_copy, void* stream) {
-  if (!k || !q || n <= 0) return DV_EINVAL;
-  const int grid = grid_for(n, 2048);
-  if (k_copy && copy_dtype == DV_BF16)
-    hipLaunchKernelGGL((ema_kernel<bf16_t>), dim3(grid), dim3(kThreads), 0, ST(stream), k, q, n, m, (bf16_t*)k_copy);
-  else
-    hipLaunchKernelGGL((ema_kernel<float>), dim3(grid), dim3(kThreads), 0, ST(stream), k, q, n, m,
-                       (float*)(copy_dtype == DV_F32 ? k_copy : nullptr));
-  return dv_launch_status();
-}
-extern "C" int dv_cast_arena(int32_t dtype, const float* src, void* dst, int64_t n, void* stream) {
-  if (!src || !dst || n <= 0) return DV_EINVAL;
-  if (dtype == DV_BF16) hipLaunchKernelGGL((cast_kernel<bf16_t>), dim3(grid_for(n, 2048)), dim3(kThreads), 0, ST(stream), src, (bf16_t*)dst, n);
-  else if (dtype == DV_F32) hipLaunchKernelGGL((cast_kernel<float>), dim3(grid_for(n, 2048)), dim3(kThreads), 0, ST(stream), src, (float*)dst, n);
-  else return DV_EUNSUPPORTED;
-  return dv_launch_status();
-}
 extern "C" int dv_pack_dgrad_weights(int32_t dtype, const float* master, void* dst, const dv_pack_desc* descs,
                                      const int32_t* block_map, int32_t n_blocks, void* stream) {
   if (!master || !dst || !descs || !block_map || n_blocks <= 0) return DV_EINVAL;

@@ -309,6 +309,11 @@ class ParamStore:
         if self.grad is not None:
             self.grad.zero_()
 
+    def compute_copy(self):
+        """the arena a kernel that rewrites the master must also write the cast of the new values to: the compute copy, or None
+        for an fp32 store (its compute copy IS the master)"""
+        return self.cc if self.dtype != DV_F32 else None
+
     def mark_dirty(self, cast_done=False):
         self._dirty = True
         self._cast_done = cast_done

@@ -52,7 +52,7 @@ class _MoCoBase(_Objective):
         bb_q.prepare(dev)
         bb_k.prepare(dev)
         assert qs.total == ks.total, 'query / key arenas must have identical layouts'
-        ops.call('dv_ema', ks.master, qs.master, ks.total, float(self.m), ks.dtype, ks.cc if ks.dtype != ops.DV_F32 else None)
+        ops.call('dv_ema', ks.master, qs.master, ks.total, float(self.m), ks.dtype, ks.compute_copy())
         ks.mark_dirty(cast_done=True)
 
     @torch.no_grad()

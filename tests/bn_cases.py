@@ -37,7 +37,8 @@ def ceil_div(a, b):
 # be retuned in this file's rules (and rows) too.
 QUOTED_RULES = [
     ('constexpr int kThreads = 256;', 1),
-    ('static inline int grid_for(int64_t work_items, int max_blocks = 4096) {', 1),
+    ('static inline int grid_for(int64_t work_items, int max_blocks = 4096) {', 1, 'common.hpp'),   # shared with optim.hip
+    ('int64_t b = (work_items + 255) / 256;', 1, 'common.hpp'),                    # ... in blocks of kThreads
     ('dim3(C), dim3(n_tiles >= 2048 ? 1024 : kThreads)', 2),                       # dv_bn_reduce_stats, dv_bn_stats_finalize
     ('hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 127) / 128), dim3(128)', 1),
     ('hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(grid_for(total)), dim3(kThreads)', 1),

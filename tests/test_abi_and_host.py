@@ -786,11 +786,11 @@ BN_TABLE_ROWS = [
 def test_bn_case_table_blocks_and_coverage():
     """tests/bn_cases.py, the tables tests/test_batchnorm_single_gpu.py runs: every literal of every row against the host
     queries (dv_bn_bwd_blocks, dv_bn_bwd_reduce_workspace) and against the launch rules the table quotes from
-    csrc/elementwise.hip (the fold's group size: csrc/ordered_fold.hpp) -- each of which is found in its source as quoted --
+    csrc/elementwise.hip (the fold's group size: csrc/ordered_fold.hpp; grid_for: csrc/common.hpp) -- each of which is found in its source as quoted --
     and the tables as a whole reach every member of bn_cases.REQUIRED and every row listed above.  A retune of dv_bn_bwd_blocks, of the 2048-tile threshold or of a grid cap
     that moves a row off its edge is named here."""
     from tests import bn_cases as T
-    homes = ('elementwise.hip', 'ordered_fold.hpp')
+    homes = ('elementwise.hip', 'ordered_fold.hpp', 'common.hpp')
     src = {f: open(os.path.join(ROOT, 'dualvar_amd', 'csrc', f)).read() for f in homes}
     for text, count, *home in T.QUOTED_RULES:
         home = home[0] if home else 'elementwise.hip'

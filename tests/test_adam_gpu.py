@@ -1,4 +1,4 @@
-"""dv_adam (csrc/elementwise.hip) and dualvar_amd.optim.Adam against float64.
+"""dv_adam (csrc/optim.hip) and dualvar_amd.optim.Adam against float64.
 
 The entry computes, per element and with ONE fp32 rounding per operation (include/dualvar_hip.h: no FMA contraction, correctly
 rounded sqrtf and division):
@@ -201,14 +201,25 @@ def call_adam(p, g, m, v, n, lr, b1, b2, eps, wd, t, gs, code, cp):
 
 
 # ------------------------------------------------------------------------------------------------------ (A) exact grid
-@pytest.mark.parametrize('copy', ['bf16', 'f32', 'none'])
-@pytest.mark.parametrize('n', NS)
+def copy_buffer(n, copy, dev):
+    """copy case -> (torch dtype or None, DV code, the whole sentinel buffer, the [n + 8] view the entry writes).  'bf16-odd': the
+    view starts one element (2 bytes) past the allocation, so no 8-byte store of four bf16 is possible"""
+    dt = {'bf16': torch.bfloat16, 'bf16-odd': torch.bfloat16, 'f32': torch.float32, 'none': None}[copy]
+    off = 1 if copy == 'bf16-odd' else 0
+    whole = sent((n + 8 + off,), dev, dt or torch.float32)
+    cp = whole[off:]
+    assert cp.data_ptr() % 8 == 2 * off
+    return dt, DV_BF16 if dt == torch.bfloat16 else DV_F32, whole, cp
+
+
+COPY_CASES = [(n, c) for n in NS for c in ('bf16', 'f32', 'none')] + [(n, 'bf16-odd') for n in (5, 1003)]
+
+
+@pytest.mark.parametrize('n,copy', COPY_CASES)
 def test_adam_exact(gpu, n, copy):
     """b1 = 1/2, b2 = 3/4 at t = 1 (bc1 = 1/2, bc2 = 1/4), lr 2^-8, |G| = 2^-3: one step from v = 0 and one from v = G^2, with
     weight decay 1/4 (p = +-1/4, g = +-1/4, grad_scale 1/4) and without (g = +-1/2, p multiples of 1/4), bit for bit"""
     gen = torch.Generator().manual_seed(n)
-    dt = {'bf16': torch.bfloat16, 'f32': torch.float32, 'none': None}[copy]
-    code = DV_BF16 if copy == 'bf16' else DV_F32
     for wd in (0.25, 0.0):
         for v_on in (0, 1):
             sign = (torch.randint(0, 2, (n,), generator=gen) * 2 - 1).double().to(gpu)
@@ -220,7 +231,7 @@ def test_adam_exact(gpu, n, copy):
             v64 = torch.full((n,), 2.0 ** -6 * v_on, dtype=F64, device=gpu)
             eps = 2.0 ** -2 if v_on else 2.0 ** -3                   # den = 2^-1 / 2^-2
             p, g, m, v = arena(p64), arena(g64), arena(m64), arena(v64)
-            cp = sent((n + 8,), gpu, dt or torch.float32)
+            dt, code, whole, cp = copy_buffer(n, copy, gpu)
             call_adam(p, g, m, v, n, 2.0 ** -8, 0.5, 0.75, eps, wd, 1, 0.25, code, cp if dt is not None else None)
             c = Hyper.of_entry(2.0 ** -8, 0.5, 0.75, eps, wd, 0.25, 1)
             assert (c.step, c.sb2) == (2.0 ** -7, 0.5)
@@ -232,6 +243,7 @@ def test_adam_exact(gpu, n, copy):
             assert is_sent(p[n:]) and is_sent(m[n:]) and is_sent(v[n:]) and is_sent(g[n:]), what
             assert torch.equal(g[:n].double(), g64), what + ': the gradient was written'
             check_copy(cp, p, n, dt, 'adam ' + what + ' ' + copy)
+            assert is_sent(whole[:whole.numel() - cp.numel()]), what + ' ' + copy + ': copy written in front of its start'
 
 
 def test_adam_keeps_zero_padding_and_refuses_bad_arguments(gpu):

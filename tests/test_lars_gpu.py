@@ -34,9 +34,12 @@ rounded once.  Every term is >= 0, so a path from a term to the total crosses 1 
       gradients against a per-tensor float64 replay and after a real forward / backward of R(2+1)D (padded weight rows: the norms
       are those of the tensors' real elements); (H) a state_dict taken after two steps continues with the same bits.
 
-  Each case prints (-s) err / bound.  Figures from an MI355X are NOT recorded here yet (no GPU run could be made when this
-  file was written).  A numpy float32 replay of the operation list and of the summation tree, run under this file's own code
-  on the CPU, gives   lars.p 0.996  lars.buf 0.595  lars.q 0.019   and   clf.p 0.998  clf.buf 0.545  clf.q 0.015.
+  Each case prints (-s) err / bound; the largest per quantity measured on an MI355X (all 20 tests pass, in about 6 s):
+      lars.p 0.996  lars.buf 0.595  lars.q 0.019   (dv_lars_norms + dv_lars_step against float64, 3 steps)
+      clf.p  0.998  clf.buf  0.545  clf.q  0.015   (optim.LARS on LinearClassifier arenas)
+      model.q 0.017 (after a real backward of R(2+1)D, fp32 0.013 / bf16 0.017 over 26 weights)   zero.p 0.187
+  A numpy float32 replay of the operation list and of the summation tree, run under this file's own code on the CPU, gives the
+  same lars.* and clf.* figures: every operation rounds as IEEE does.
 """
 import ctypes as C
 import math

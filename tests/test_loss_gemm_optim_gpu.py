@@ -1,5 +1,5 @@
-"""The loss, fp32 GEMM and optimizer entries (csrc/loss.hip; dv_sgd_momentum, dv_ema, dv_cast_arena, dv_mean_f32, dv_colsum_f32
-of csrc/elementwise.hip) against plain float64 references of the same operations, written here from include/dualvar_hip.h.
+"""The loss, fp32 GEMM and optimizer entries (csrc/loss.hip; dv_sgd_momentum, dv_ema, dv_cast_arena of csrc/optim.hip; dv_mean_f32,
+dv_colsum_f32 of csrc/elementwise.hip) against plain float64 references of the same operations, written here from include/dualvar_hip.h.
 
 Every entry is called through the C ABI on explicit tensors.  Inputs sit in buffers whose gaps (pitch padding, the float in
 front of an offset base) hold NaN, outputs in buffers filled with a NaN bit pattern no kernel produces (SENT): a read or a
@@ -965,18 +965,29 @@ def check_copy(copy, p, n, dtype, what):
     assert is_sent(copy[n:]), what + ': copy written past n'
 
 
-@pytest.mark.parametrize('copy', ['bf16', 'f32', 'none'])
-@pytest.mark.parametrize('n', NS)
+def copy_buffer(n, copy, dev):
+    """copy case -> (torch dtype or None, DV code, the whole sentinel buffer, the [n + 8] view the entry writes).  'bf16-odd': the
+    view starts one element (2 bytes) past the allocation, so no 8-byte store of four bf16 is possible"""
+    dt = {'bf16': torch.bfloat16, 'bf16-odd': torch.bfloat16, 'f32': torch.float32, 'none': None}[copy]
+    off = 1 if copy == 'bf16-odd' else 0
+    whole = sent((n + 8 + off,), dev, dt or torch.float32)
+    cp = whole[off:]
+    assert cp.data_ptr() % 8 == 2 * off
+    return dt, DV_BF16 if dt == torch.bfloat16 else DV_F32, whole, cp
+
+
+COPY_CASES = [(n, c) for n in NS for c in ('bf16', 'f32', 'none')] + [(n, 'bf16-odd') for n in (5, 1003)]
+
+
+@pytest.mark.parametrize('n,copy', COPY_CASES)
 def test_sgd_exact(gpu, n, copy):
     """lr 2^-8, mu 1/2, wd 2^-10, grad_scale 1/4, integer p, g, buf: one step with weight decay, three without, bit for bit"""
     gen = torch.Generator().manual_seed(n)
-    dt = {'bf16': torch.bfloat16, 'f32': torch.float32, 'none': None}[copy]
-    code = DV_BF16 if copy == 'bf16' else DV_F32
     for wd, steps in ((2.0 ** -10, 1), (0.0, 3)):
         ri = lambda: torch.randint(-8, 9, (n,), generator=gen).double().to(gpu)  # noqa: E731
         p64, b64 = ri(), ri()
         p, buf = arena(p64), arena(b64)
-        cp = sent((n + 8,), gpu, dt or torch.float32)
+        dt, code, whole, cp = copy_buffer(n, copy, gpu)
         for step in range(steps):
             g64 = ri()
             g = arena(g64)
@@ -986,6 +997,7 @@ def test_sgd_exact(gpu, n, copy):
             same_bits(buf[:n], b64, f'sgd buf n={n} wd={wd} step {step}')
             assert is_sent(p[n:]) and is_sent(buf[n:]) and is_sent(g[n:])
             check_copy(cp, p, n, dt, f'sgd n={n} {copy}')
+            assert is_sent(whole[:whole.numel() - cp.numel()]), f'sgd n={n} {copy}: copy written in front of its start'
 
 
 TIE_BITS = [0x3f808000, 0x3f818000, 0x3f808001, 0x3f807fff, 0x3f817fff, 0x3f818001, 0xbf808000, 0xbf818000, 0x00008000, 0x00018000,
