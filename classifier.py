@@ -125,6 +125,9 @@ def parse_args(argv=None):
     p.add_argument('--cluster_init', default=10, type=int)
     p.add_argument('--cluster_seed', default=0, type=int)
     p.add_argument('--cluster_split', default='test', choices=['test', 'train', 'both'])
+    p.add_argument('--ridge', action='store_true', help='with --test ... --retrieval: also the closed-form ridge probe, fitted on the train clip features and scored on the test clips')
+    p.add_argument('--ridge_lambda', default=[1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1], type=float, nargs='*', help='the grid of lambda (relative to the number of training clips)')
+    p.add_argument('--ridge_holdout', default=5, type=int, help='one training video in this many, per class, is held out to choose lambda')
     p.add_argument('--center_crop', action='store_true')
     p.add_argument('--five_crop', action='store_true')
     p.add_argument('--ten_crop', action='store_true')
@@ -199,6 +202,12 @@ def check_args(args, environ=None):
         refuse('--cluster_iter must be at least 1')
     if args.cluster_init < 1:
         refuse('--cluster_init must be at least 1')
+    if args.ridge and not (args.test and args.retrieval):
+        refuse('--ridge fits on the retrieval clip features: pass --test <checkpoint> --retrieval with it')
+    if not args.ridge_lambda or any(not (v > 0 and math.isfinite(v)) for v in args.ridge_lambda):
+        refuse('--ridge_lambda takes one or more positive finite values')
+    if args.ridge_holdout < 2:
+        refuse('--ridge_holdout must be at least 2')
     if args.test:
         if args.retrieval:
             if args.num_seq != 10:
@@ -550,7 +559,7 @@ def test_retrieval(model, epoch, args):
             per_feature = torch.cat(per_feature, dim=0)
             torch.save(per_feature, os.path.join(out_dir, '%s_%s_per_feature.pth.tar' % (args.dataset, split)))
             feats[split] = (feature, label)
-            if args.variance or args.tsne or args.cluster:
+            if args.variance or args.tsne or args.cluster or args.ridge:
                 clips[split] = per_feature
     acc, sim = nn_retrieval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1], ks=(1, 5, 10, 20, 50))
     torch.save(sim, os.path.join(out_dir, '%s_sim.pth.tar' % args.dataset))
@@ -588,7 +597,27 @@ def test_retrieval(model, epoch, args):
     if args.cluster:
         for split in (('test', 'train') if args.cluster_split == 'both' else (args.cluster_split,)):
             write_cluster(clips[split], feats[split][1], split, out_dir, args)
+    if args.ridge:
+        write_ridge(clips['train'], feats['train'][1], clips['test'], feats['test'][1], out_dir, args)
     return acc
+
+
+def write_ridge(train_clips, train_label, test_clips, test_label, out_dir, args):
+    """--ridge: the closed-form ridge probe, fitted on the train clips and scored on the test clips -> <dataset>_ridge.{json,
+    pth.tar}; the only writer of these two files"""
+    from dualvar_amd.utils.probe import ridge_probe
+    rep = ridge_probe(train_clips, train_label, test_clips, test_label, args.num_class, lambdas=tuple(args.ridge_lambda),
+                      holdout=args.ridge_holdout)
+    for row in rep['sweep']:
+        args.logger.info('ridge probe, lambda = %g: held-out clip Acc@1 = %.4f Acc@5 = %.4f video Acc@1 = %.4f Acc@5 = %.4f'
+                         % (row['lambda'], row['clip_top1'], row['clip_top5'], row['video_top1'], row['video_top5']))
+    args.logger.info('ridge probe on %s (%d train clips, %d videos held out, lambda = %g): clip Acc@1 = %.4f Acc@5 = %.4f '
+                     'video Acc@1 = %.4f Acc@5 = %.4f' % (args.dataset, rep['n_train'], rep['n_held_videos'], rep['lambda'],
+                                                          rep['clip_top1'], rep['clip_top5'], rep['video_top1'], rep['video_top5']))
+    stem = os.path.join(out_dir, '%s_ridge' % args.dataset)
+    torch.save({'W': rep['W'].cpu(), 'lambda': rep['lambda']}, stem + '.pth.tar')
+    with open(stem + '.json', 'w') as fp:
+        json.dump({k: v for k, v in rep.items() if k != 'W'}, fp, indent=1)
 
 
 def write_cluster(per_feature, label, split, out_dir, args):

@@ -16,6 +16,8 @@ DV_LARS_ADAPT, DV_LARS_DECAY = 1, 2
 DV_TOPK_MAX_K = 256          # == DV_TOPK_MAX_K of include/dualvar_select.h: the largest k of dv_topk_merge_f32 / dv_knn_vote
 DV_PAIRSTAT_MAX_BINS = 256    # == DV_PAIRSTAT_MAX_BINS of include/dualvar_pairstat.h: the most histogram bins of dv_pairstat_accum_f32
 DV_KMEANS_MAX_K = 4096       # == DV_KMEANS_MAX_K of include/dualvar_cluster.h: the most clusters of the dv_kmeans_* entries
+DV_RIDGE_MAX_D = 4096       # == DV_RIDGE_MAX_D of include/dualvar_ridge.h: the widest feature row of the dv_ridge_* entries
+DV_RIDGE_MAX_C = 4096       # == DV_RIDGE_MAX_C of include/dualvar_ridge.h: the most classes of the dv_ridge_* entries
 DV_W3 = 128                  # conv fwd / dgrad in DV_F32: weights pre-split in fragment order (dv_pack_w3)
 
 _ERR = {-1: 'DV_EINVAL (inconsistent shapes / unsupported parameter)',
@@ -89,7 +91,8 @@ class GemmDesc(C.Structure):
 
 P, I32, I64, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 RETURNS_INT64 = ('dv_conv3d_wgrad_workspace', 'dv_conv3d_dgrad_bn_workspace', 'dv_w3_bytes', 'dv_bn_bwd_reduce_workspace', 'dv_infonce_workspace',
-                 'dv_pairstat_workspace', 'dv_tsne_repulse_workspace', 'dv_kmeans_update_workspace', 'dv_kmeans_seed_workspace')       # everything else returns int
+                 'dv_pairstat_workspace', 'dv_tsne_repulse_workspace', 'dv_kmeans_update_workspace', 'dv_kmeans_seed_workspace',
+                 'dv_ridge_gram_workspace')       # everything else returns int
 CD, PD = C.POINTER(ConvDesc), C.POINTER(PoolDesc)
 
 # name -> argtypes, exactly as declared in include/dualvar_hip.h
@@ -217,6 +220,13 @@ CLUSTER_SIGNATURES = {
     'dv_kmeans_seed_f32': [P, I32, P, I32, C.c_double, P, P, P, P],
 }
 
+# name -> argtypes of include/dualvar_ridge.h (the ridge-probe entries of csrc/ridge.hip)
+RIDGE_SIGNATURES = {
+    'dv_ridge_gram_workspace': [I32, I32, I32],
+    'dv_ridge_gram_f64': [P, I64, I32, I32, P, I32, P, I64, P, I64, I32, P, P],
+    'dv_ridge_solve_f64': [P, I64, I32, I32, C.c_double, P, I64, I32, P, I64, P, I64, P, P],
+}
+
 _lib = None
 
 
@@ -237,7 +247,7 @@ def load():
     # same HIP runtime (loading ours first binds it to /opt/rocm's copy and every launch then reports "no device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(RIDGE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI and this table disagree
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
