@@ -13,6 +13,8 @@ ABI_VERSION = 2              # == DV_ABI_VERSION of include/dualvar_hip.h (tests
 DV_F32, DV_BF16 = 0, 1
 DV_BIAS, DV_RELU, DV_SIGMOID, DV_ACCUM, DV_STATS, DV_NO_RELU_MASK, DV_MASK_FROM_X = 1, 2, 4, 8, 16, 32, 64
 DV_LARS_ADAPT, DV_LARS_DECAY = 1, 2
+DV_PAIR_DGRAD, DV_PAIR_BN_IN0, DV_PAIR_BN_IN1, DV_PAIR_BN_REDUCE0, DV_PAIR_BN_REDUCE1 = 1, 2, 4, 8, 16      # dv_conv3d_pair_ok's mode bits (include/dualvar_conv_pair.h)
+DV_PAIR_KS = 4               # dv_conv3d_pair_ok's answer for two convs that share a conv_gemm_ks launch (1 / 2: conv_tap's forms)
 DV_TOPK_MAX_K = 256          # == DV_TOPK_MAX_K of include/dualvar_select.h: the largest k of dv_topk_merge_f32 / dv_knn_vote
 DV_PAIRSTAT_MAX_BINS = 256    # == DV_PAIRSTAT_MAX_BINS of include/dualvar_pairstat.h: the most histogram bins of dv_pairstat_accum_f32
 DV_KMEANS_MAX_K = 4096       # == DV_KMEANS_MAX_K of include/dualvar_cluster.h: the most clusters of the dv_kmeans_* entries
@@ -227,6 +229,14 @@ RIDGE_SIGNATURES = {
     'dv_ridge_solve_f64': [P, I64, I32, I32, C.c_double, P, I64, I32, P, I64, P, I64, P, P],
 }
 
+# name -> argtypes of include/dualvar_conv_pair.h (two independent convs in one grid: csrc/conv.hip, csrc/conv_tap.hip)
+PAIR_SIGNATURES = {
+    'dv_conv3d_pair_ok': [CD, CD, I32],
+    'dv_conv3d_fwd_pair': [CD, P, P, P, P, CD, P, P, P, P, P],
+    'dv_conv3d_fwd_bn_in_pair': [CD, P, P, P, P, P, CD, P, P, P, P, P, P],
+    'dv_conv3d_dgrad_pair': [CD, P, P, P, P, CD, P, P, P, P, P, I64, P],
+}
+
 _lib = None
 
 
@@ -247,7 +257,7 @@ def load():
     # same HIP runtime (loading ours first binds it to /opt/rocm's copy and every launch then reports "no device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(RIDGE_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(RIDGE_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI and this table disagree
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int

@@ -51,7 +51,7 @@ def build_lib(force=False, verbose=False):
             os.path.join(HERE, '..', 'include', 'dualvar_hip.h'),
             os.path.join(HERE, '..', 'include', 'dualvar_select.h'), os.path.join(HERE, '..', 'include', 'dualvar_pairstat.h'),
             os.path.join(HERE, '..', 'include', 'dualvar_tsne.h'), os.path.join(HERE, '..', 'include', 'dualvar_cluster.h'),
-            os.path.join(HERE, '..', 'include', 'dualvar_ridge.h')]
+            os.path.join(HERE, '..', 'include', 'dualvar_ridge.h'), os.path.join(HERE, '..', 'include', 'dualvar_conv_pair.h')]
     objs = []
     procs = []
     for src in SOURCES:

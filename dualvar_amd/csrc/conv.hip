@@ -14,6 +14,7 @@
 // MFMA: v_mfma_f32_32x32x16_bf16 (bf16 storage) / v_mfma_f32_32x32x2_f32 (f32 parity mode);
 // both share the 32x32 C/D layout  col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 #include "conv_common.hpp"
+#include "../../include/dualvar_conv_pair.h"
 
 // the LDS-staged input-tile kernels for stride-1 "same" 1x3x3 / 3x1x1 convs and their pixel-pair stem form (conv_tap.hip); the
 // argument is a ConvArgs*.  The three predicates answer route_conv's questions; the launches run what it decided.
@@ -21,6 +22,8 @@ int dvt_conv_tap_kind(const void* conv_args, int mode);
 int dvt_conv_tap_bm(const void* conv_args, int kind);
 int dvt_conv_pp_lines(const void* conv_args, int mode);
 void dvt_conv_tap_launch(const void* conv_args, int mode, int kind, int bm, void* stream);
+int dvt_conv_tap_pair_inst(const void* args0, int kind0, int bm0, const void* args1, int kind1, int bm1, int mode);
+void dvt_conv_tap_launch_pair(const void* args0, const void* args1, int mode, int kind, int bm, void* stream);
 void dvt_conv_pp_launch(const void* conv_args, int G, void* stream);
 int64_t dvt_bn_ws_floats(int64_t rows, int np);
 
@@ -652,8 +655,10 @@ __attribute__((amdgpu_waves_per_eu(conv_waves_per_simd(sizeof(T), GVB, BM, BN)))
 // bit-reproducible), then bias / activation / store / BatchNorm partials as in conv_gemm_kernel.
 // Restricted to what the engine's fp32 mode issues for those layers: pre-split weights (DV_W3), uniform-tap gathers
 // (channel pitch a multiple of 16, <= 32 taps), no parity classes, no fused BatchNorm-backward reduce.
+// The body of one workgroup: block `bid` of the `nblk` blocks of the problem `a` (a grid of its own, or one member's share of
+// conv_gemm_ks_pair_kernel's).  `a` by value: its fields stay the scalar kernel-argument loads of a kernel that takes the block.
 template <int MODE, int BN, int NS>
-__global__ __launch_bounds__(256) void conv_gemm_ks_kernel(ConvArgs a) {
+__device__ __forceinline__ void conv_gemm_ks_body(const ConvArgs a, const int bid, const int nblk) {
   constexpr int BM = 64, NW = 4, TM = 2, TN = BN / 32;
   constexpr int A_BYTES = BM * 64, B_BYTES = BN * 96;          // one K tile: 16 f32 per row of A; hi|mid|lo of both k halves of B
   constexpr int BPC = B_BYTES / 1024;
@@ -670,7 +675,7 @@ __global__ __launch_bounds__(256) void conv_gemm_ks_kernel(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, l31 = lane & 31;
-  const int lbid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int lbid = xcd_remap(bid, nblk);
   const int tile_n = lbid % a.ntn, tile_m = lbid / a.ntn;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const dma_rsrc_t src_dma = dma_make_rsrc(a.src, (unsigned)a.src_bytes), w_dma = dma_make_rsrc(a.w, (unsigned)a.w_bytes);
@@ -834,6 +839,25 @@ __global__ __launch_bounds__(256) void conv_gemm_ks_kernel(ConvArgs a) {
       }
     }
   }
+}
+
+template <int MODE, int BN, int NS>
+__global__ __launch_bounds__(256) void conv_gemm_ks_kernel(ConvArgs a) {
+  conv_gemm_ks_body<MODE, BN, NS>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// Two independent problems of the same instantiation in one grid (the spatial branch convs of the 1 152-row Inception levels:
+// 72 - 216 workgroups each, one per CU): blocks [0, nblk0) are member 0's grid, the others member 1's, as conv_tap_pair_kernel
+// (conv_tap.hip).  The exchange of the partial tiles stays inside a workgroup: nothing crosses members.
+struct KsPair {
+  ConvArgs m[2];
+  int nblk0;
+};
+
+template <int MODE, int BN, int NS>
+__global__ __launch_bounds__(256) void conv_gemm_ks_pair_kernel(KsPair p) {
+  const int b = (int)blockIdx.x, second = b >= p.nblk0 ? 1 : 0;
+  conv_gemm_ks_body<MODE, BN, NS>(p.m[second], second ? b - p.nblk0 : b, second ? (int)gridDim.x - p.nblk0 : p.nblk0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1678,6 +1702,18 @@ static void launch_ks(int bn, ConvArgs& a, hipStream_t s) {
   if (bn == 32) hipLaunchKernelGGL((conv_gemm_ks_kernel<MODE, 32, 4>), dim3(grid), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_gemm_ks_kernel<MODE, 64, 3>), dim3(grid), dim3(256), 0, s, a);
 }
+// two problems with the same column tile (the instantiation follows from it) in one grid
+template <int MODE>
+static void launch_ks_pair(int bn, ConvArgs& a0, ConvArgs& a1, hipStream_t s) {
+  KsPair p;
+  a0.ntn = (a0.NP + bn - 1) / bn;
+  a1.ntn = (a1.NP + bn - 1) / bn;
+  p.m[0] = a0; p.m[1] = a1;
+  p.nblk0 = a0.ntn * ((a0.M + 63) / 64);
+  const int grid = p.nblk0 + a1.ntn * ((a1.M + 63) / 64);
+  if (bn == 32) hipLaunchKernelGGL((conv_gemm_ks_pair_kernel<MODE, 32, 4>), dim3(grid), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((conv_gemm_ks_pair_kernel<MODE, 64, 3>), dim3(grid), dim3(256), 0, s, p);
+}
 
 // the parity classes of a strided data gradient (ConvArgs::cls_on == 1): `a` holds the launch-wide fields; -> number of classes
 static int dgrad_classes(const dv_conv_desc* d, const ConvArgs& a, ConvArgs (&out)[8]) {
@@ -1899,8 +1935,9 @@ extern "C" int dv_conv3d_ksplit_cols(const dv_conv_desc* d, int32_t dgrad) {
   return r.path == ROUTE_KS ? r.ks_cols : 0;
 }
 
-static int fwd_impl(const dv_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
-                    const dv_bn_in* bn_in, void* stream) {
+// a forward call checked, its arguments in `a`, its route in `r`: all of dv_conv3d_fwd / dv_conv3d_fwd_bn_in but the launch
+static int fwd_prepare(const dv_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
+                       const dv_bn_in* bn_in, ConvArgs& a, ConvRoute& r) {
   int rc = check_desc(d);
   if (rc) return rc;
   if (!x || !w || !y) return DV_EINVAL;
@@ -1908,17 +1945,64 @@ static int fwd_impl(const dv_conv_desc* d, const void* x, const void* w, const f
   if ((d->flags & DV_STATS) && !stats) return DV_EINVAL;
   if (!aligned16(w) || !aligned16(y) || (reinterpret_cast<uintptr_t>(x) & 7)) return DV_EALIGN;
   if (bn_in && (!bn_in->scale || !bn_in->shift)) return DV_EINVAL;
-  ConvArgs a;
   if ((rc = conv_args(d, MODE_FWD, a))) return rc;
   a.src = x; a.w = w; a.out = y; a.bias = bias; a.stats = stats;
   if (bn_in) { a.in_scale = bn_in->scale; a.in_shift = bn_in->shift; a.in_C = d->Cin; a.in_relu = (bn_in->flags & DV_RELU) ? 1 : 0; }
-  const ConvRoute r = route_conv(d, MODE_FWD, a);
+  r = route_conv(d, MODE_FWD, a);
   if (r.path == ROUTE_NONE) return DV_EUNSUPPORTED;
   const int gvb = gather_bytes(d->dtype, d->cin_pitch);
   if (gvb == 16 && !aligned16(x)) return DV_EALIGN;
   const int esz = d->dtype == DV_F32 ? 4 : 2;
   if ((d->ldx * esz) % gvb || (a.ldw * esz) % gvb) return DV_EALIGN;
-  return launch_route(d, MODE_FWD, r, a, stream);
+  return DV_OK;
+}
+
+static int fwd_impl(const dv_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
+                    const dv_bn_in* bn_in, void* stream) {
+  ConvArgs a;
+  ConvRoute r;
+  const int rc = fwd_prepare(d, x, w, bias, y, stats, bn_in, a, r);
+  return rc ? rc : launch_route(d, MODE_FWD, r, a, stream);
+}
+
+// ---- two independent convs in one grid ---------------------------------------------------------------------------------------
+// What the two routed calls share a grid on, or 0: the kind (1 spatial / 2 temporal) of the LDS-staged kernel when both select
+// the identical instantiation of it and may share a grid (conv_tap.hip: conv_tap_pair_kernel); DV_PAIR_KS when both run
+// conv_gemm_ks_kernel with the same column tile (which fixes its instantiation; that route never carries a fused reduce, a
+// BatchNorm on load or a parity class).  The query and the three pair entries all ask here.
+static int pair_kind(const ConvRoute& r0, const ConvArgs& a0, const ConvRoute& r1, const ConvArgs& a1, int mode) {
+  if (r0.path == ROUTE_KS && r1.path == ROUTE_KS) return r0.ks_cols == r1.ks_cols ? DV_PAIR_KS : 0;
+  if (r0.path != ROUTE_TAP || r1.path != ROUTE_TAP) return 0;
+  return dvt_conv_tap_pair_inst(&a0, r0.kind, r0.rows, &a1, r1.kind, r1.rows, mode) ? r0.kind : 0;
+}
+
+// both members are checked before anything is launched; a pair that does not qualify runs its two launches in order
+static int launch_pair(const dv_conv_desc* d0, ConvRoute& r0, ConvArgs& a0, const dv_conv_desc* d1, ConvRoute& r1, ConvArgs& a1,
+                       int mode, void* stream) {
+  if (const int kind = pair_kind(r0, a0, r1, a1, mode)) {
+    if (kind != DV_PAIR_KS) dvt_conv_tap_launch_pair(&a0, &a1, mode, kind, r0.rows, stream);
+    else if (mode == MODE_FWD) launch_ks_pair<MODE_FWD>(r0.ks_cols, a0, a1, (hipStream_t)stream);
+    else launch_ks_pair<MODE_DGRAD>(r0.ks_cols, a0, a1, (hipStream_t)stream);
+    return dv_launch_status();
+  }
+  if (r0.path == ROUTE_NONE || r1.path == ROUTE_NONE) return DV_EUNSUPPORTED;
+  const int rc = launch_route(d0, mode, r0, a0, stream);
+  return rc ? rc : launch_route(d1, mode, r1, a1, stream);
+}
+
+extern "C" int dv_conv3d_fwd_bn_in_pair(const dv_conv_desc* d0, const void* x0, const dv_bn_in* bn0, const void* w0, void* y0,
+                                        float* stats0, const dv_conv_desc* d1, const void* x1, const dv_bn_in* bn1, const void* w1,
+                                        void* y1, float* stats1, void* stream) {
+  ConvArgs a0, a1;
+  ConvRoute r0, r1;
+  int rc = fwd_prepare(d0, x0, w0, nullptr, y0, stats0, bn0, a0, r0);
+  if (!rc) rc = fwd_prepare(d1, x1, w1, nullptr, y1, stats1, bn1, a1, r1);
+  return rc ? rc : launch_pair(d0, r0, a0, d1, r1, a1, MODE_FWD, stream);
+}
+
+extern "C" int dv_conv3d_fwd_pair(const dv_conv_desc* d0, const void* x0, const void* w0, void* y0, float* stats0,
+                                  const dv_conv_desc* d1, const void* x1, const void* w1, void* y1, float* stats1, void* stream) {
+  return dv_conv3d_fwd_bn_in_pair(d0, x0, nullptr, w0, y0, stats0, d1, x1, nullptr, w1, y1, stats1, stream);
 }
 
 extern "C" int dv_conv3d_fwd(const dv_conv_desc* d, const void* x, const void* w, const float* bias, void* y,
@@ -2057,8 +2141,9 @@ static void launch_dgrad_bn_tail(const ConvArgs& c, int dtype, hipStream_t s) {
   else hipLaunchKernelGGL((dgrad_bn_tail_kernel<bf16_t>), dim3(grid), dim3(256), 0, s, t);
 }
 
-static int dgrad_impl(const dv_conv_desc* d, const void* dy, const void* wd, void* dx, const dv_bn_reduce* bnr, void* stream,
-                      void* bn_ws = nullptr, int64_t bn_ws_bytes = 0) {
+// a data-gradient call checked and its arguments in `a` (the route is the caller's: the atomic form routes the plain call)
+static int dgrad_prepare(const dv_conv_desc* d, const void* dy, const void* wd, void* dx, const dv_bn_reduce* bnr, void* bn_ws,
+                         int64_t bn_ws_bytes, ConvArgs& a) {
   int rc = check_desc(d);
   if (rc) return rc;
   if (!dy || !wd || !dx) return DV_EINVAL;
@@ -2072,7 +2157,6 @@ static int dgrad_impl(const dv_conv_desc* d, const void* dy, const void* wd, voi
   if (!aligned16(dy) || !aligned16(wd) || !aligned16(dx)) return DV_EALIGN;
   const int esz = d->dtype == DV_F32 ? 4 : 2;
   if ((d->ldx * esz) % 16) return DV_EALIGN;
-  ConvArgs a;
   if ((rc = conv_args(d, MODE_DGRAD, a))) return rc;
   a.src = dy; a.w = wd; a.out = dx;
   if (bnr) {
@@ -2087,6 +2171,14 @@ static int dgrad_impl(const dv_conv_desc* d, const void* dy, const void* wd, voi
       a.bn_bytes = (int)xb;
     }
   }
+  return DV_OK;
+}
+
+static int dgrad_impl(const dv_conv_desc* d, const void* dy, const void* wd, void* dx, const dv_bn_reduce* bnr, void* stream,
+                      void* bn_ws = nullptr, int64_t bn_ws_bytes = 0) {
+  ConvArgs a;
+  int rc = dgrad_prepare(d, dy, wd, dx, bnr, bn_ws, bn_ws_bytes, a);
+  if (rc) return rc;
   if (bnr && !bn_ws) {
     // dv_conv3d_dgrad_bn, the atomic form: the plain data gradient on whatever kernel takes it, then the reduce over what it wrote
     const ConvArgs tail = a;
@@ -2106,6 +2198,36 @@ extern "C" int dv_conv3d_dgrad_bn(const dv_conv_desc* d, const void* dy, const v
                                   void* stream) {
   if (!bn) return DV_EINVAL;
   return dgrad_impl(d, dy, wd, dx, bn, stream);
+}
+
+// bn0 / bn1: a member that carries the ordered fused BatchNorm-backward reduce (dv_conv3d_dgrad_bn_ws with `workspace`), or NULL.
+// Such a member shares no grid: the two calls then run one after the other.
+extern "C" int dv_conv3d_dgrad_pair(const dv_conv_desc* d0, const void* dy0, const void* wd0, void* dx0, const dv_bn_reduce* bn0,
+                                    const dv_conv_desc* d1, const void* dy1, const void* wd1, void* dx1, const dv_bn_reduce* bn1,
+                                    void* workspace, int64_t workspace_bytes, void* stream) {
+  if ((bn0 || bn1) && !workspace) return DV_EINVAL;
+  ConvArgs a0, a1;
+  int rc = dgrad_prepare(d0, dy0, wd0, dx0, bn0, bn0 ? workspace : nullptr, bn0 ? workspace_bytes : 0, a0);
+  if (!rc) rc = dgrad_prepare(d1, dy1, wd1, dx1, bn1, bn1 ? workspace : nullptr, bn1 ? workspace_bytes : 0, a1);
+  if (rc) return rc;
+  ConvRoute r0 = route_conv(d0, MODE_DGRAD, a0), r1 = route_conv(d1, MODE_DGRAD, a1);
+  return launch_pair(d0, r0, a0, d1, r1, a1, MODE_DGRAD, stream);
+}
+
+extern "C" int dv_conv3d_pair_ok(const dv_conv_desc* d0, const dv_conv_desc* d1, int32_t mode) {
+  if (!d0 || !d1 || check_desc(d0) || check_desc(d1)) return 0;
+  if (mode & (DV_PAIR_BN_REDUCE0 | DV_PAIR_BN_REDUCE1)) return 0;
+  const int m = (mode & DV_PAIR_DGRAD) ? MODE_DGRAD : MODE_FWD;
+  if (m == MODE_DGRAD && (mode & (DV_PAIR_BN_IN0 | DV_PAIR_BN_IN1))) return 0;
+  for (const dv_conv_desc* d : {d0, d1})
+    if (m == MODE_DGRAD && (d->st > 2 || d->sh > 2 || d->sw > 2 || d->cin_pitch % 8)) return 0;      // (dv_conv3d_dgrad refuses these)
+  static const float dummy = 0.f;
+  ConvArgs a0, a1;
+  if (conv_args(d0, m, a0) || conv_args(d1, m, a1)) return 0;
+  if (mode & DV_PAIR_BN_IN0) a0.in_scale = &dummy;
+  if (mode & DV_PAIR_BN_IN1) a1.in_scale = &dummy;
+  const ConvRoute r0 = route_conv(d0, m, a0), r1 = route_conv(d1, m, a1);
+  return pair_kind(r0, a0, r1, a1, m);
 }
 
 extern "C" int64_t dv_conv3d_dgrad_bn_workspace(const dv_conv_desc* d) {

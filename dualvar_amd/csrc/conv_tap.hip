@@ -104,8 +104,11 @@ __device__ __forceinline__ void gload16_hi(f32x4& dst, dma_rsrc_t rsrc, unsigned
 // BNL: BatchNorm (+ReLU) of the layer in front applied to the staged slab (coefficients in an LDS table behind the zero slot)
 // BM: rows per tile, 256 (a wave owns 64 rows) or 128 (32): the 128-row form is for launches of less than ~1.5 workgroups per CU
 // in the 256-row form (the 12 544-row levels): twice the workgroups, two or three of them resident per CU instead of one
+// The body of one workgroup: block `bid` of the `nblk` blocks of the problem `a` (a grid of its own -- conv_tap_kernel -- or one
+// member's share of a grid -- conv_tap_pair_kernel).  `a` by value: the fields stay the scalar kernel-argument loads they are in a
+// kernel that takes the block itself (by reference the 256-row temporal forms took two VGPRs more and one pair form spilled).
 template <int KIND, int NTAPS, int BN, int NS, int NU, bool BNL = false, int BM = 256>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 128 ? 4 : 3))) void conv_tap_kernel(TapArgs a) {
+__device__ __forceinline__ void conv_tap_body(const TapArgs a, const int bid, const int nblk) {
   static_assert(!BNL || KIND == 1, "BatchNorm on load: temporal form (rows past the end never share a tile row with valid ones)");
   static_assert(BM == 256 || BM == 128, "tile height");
   constexpr int NW = 4, TM = BM / 128, WR = BM / NW, TN = BN / 32;       // WR: rows of a wave
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 12
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, l31 = lane & 31;
-  const int lbid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int lbid = xcd_remap(bid, nblk);
   const int tile_n = lbid % a.ntn, tile_m = lbid / a.ntn;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const dma_rsrc_t src_rs = dma_make_rsrc(a.src, (unsigned)a.src_bytes), w_rs = dma_make_rsrc(a.w, (unsigned)a.w_bytes);
@@ -524,6 +527,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 12
   }
 }
 
+template <int KIND, int NTAPS, int BN, int NS, int NU, bool BNL = false, int BM = 256>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 128 ? 4 : 3))) void conv_tap_kernel(TapArgs a) {
+  conv_tap_body<KIND, NTAPS, BN, NS, NU, BNL, BM>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// Two independent problems that run the SAME instantiation, in one grid (the two separable branches of an Inception level: the
+// small member -- 98 - 196 workgroups on 256 CUs, almost all latency -- runs in the slack of the large one, which does not fill
+// a resident round either).  Blocks [0, nblk0) are member 0's grid, the others member 1's: each member keeps the tile order
+// (xcd_remap over its own blocks) and the operands it has alone, so every tile computes the bits it computes alone.  The choice
+// is workgroup-uniform; the launch's dynamic LDS is the larger member's (all offsets come from the member's own npos / npp / CP).
+struct TapPair {
+  TapArgs m[2];
+  int nblk0;
+};
+
+template <int KIND, int NTAPS, int BN, int NS, int NU, bool BNL = false, int BM = 256>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BM == 128 ? 4 : 3))) void conv_tap_pair_kernel(TapPair p) {
+  const int b = (int)blockIdx.x, second = b >= p.nblk0 ? 1 : 0;
+  conv_tap_body<KIND, NTAPS, BN, NS, NU, BNL, BM>(p.m[second], second ? b - p.nblk0 : b, second ? (int)gridDim.x - p.nblk0 : p.nblk0);
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------------
 // Pixel-pair stem form (forward): the network's first conv (backbone/s3dg.py:151 Conv_1a.conv1, 1x7x7 / stride 2 on RGB -- here a
@@ -780,9 +804,26 @@ static int tap_kind(const ConvArgs& a, int mode) {
   return 0;
 }
 
+// One launch of the LDS-staged kernel as dvt_conv_tap_launch runs it: the argument block, the instantiation (TAP_*), the grid and
+// the dynamic LDS.  tap_launch_of decides all four; launch_tap_inst runs what it decided, for one problem or for two that share
+// the instantiation (conv_tap_pair_kernel).
+enum { TAP_SP128 = 1, TAP_SP256_NU2, TAP_SP256_NU3, TAP_TM128_BNL, TAP_TM128_K4, TAP_TM128, TAP_TM256_BNL, TAP_TM256_K4, TAP_TM256 };
+struct TapLaunch {
+  TapArgs t;
+  int inst, grid;
+  size_t lds;
+};
+
 template <int KIND, int NTAPS, int NU, bool BNL = false, int BM = 256>
-static void launch_tap(const TapArgs& t, int grid, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL((conv_tap_kernel<KIND, NTAPS, 64, 3, NU, BNL, BM>), dim3(grid), dim3(256), lds, s, t);
+static void launch_tap(const TapLaunch& l, const TapLaunch* l1, hipStream_t s) {
+  if (!l1) {
+    hipLaunchKernelGGL((conv_tap_kernel<KIND, NTAPS, 64, 3, NU, BNL, BM>), dim3(l.grid), dim3(256), l.lds, s, l.t);
+    return;
+  }
+  TapPair p;
+  p.m[0] = l.t; p.m[1] = l1->t; p.nblk0 = l.grid;
+  hipLaunchKernelGGL((conv_tap_pair_kernel<KIND, NTAPS, 64, 3, NU, BNL, BM>), dim3(l.grid + l1->grid), dim3(256),
+                     std::max(l.lds, l1->lds), s, p);
 }
 
 // tile height: 128 rows where the 256-row form would launch fewer than ~1.5 workgroups per CU (the 12 544-row levels: 147 - 245
@@ -829,11 +870,11 @@ void dvt_conv_pp_launch(const void* conv_args, int G, void* stream) {
   hipLaunchKernelGGL((conv_pp_fwd_kernel<2>), dim3(grid), dim3(256), lds, (hipStream_t)stream, t);
 }
 
-// the LDS-staged kernel in form `kind` (dvt_conv_tap_kind) with tiles of bm rows (dvt_conv_tap_bm)
-void dvt_conv_tap_launch(const void* conv_args, int mode, int kind, int bm, void* stream) {
-  const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);
+// the launch of the LDS-staged kernel in form `kind` (dvt_conv_tap_kind) with tiles of bm rows (dvt_conv_tap_bm)
+static TapLaunch tap_launch_of(const ConvArgs& a, int mode, int kind, int bm) {
   const ConvGeom& g = a.g;
-  TapArgs t;
+  TapLaunch l;
+  TapArgs& t = l.t;
   t.src = a.src; t.w = a.w; t.out = a.out; t.stats = a.stats;
   t.M = a.M; t.N = a.N; t.NP = a.NP; t.lds_ = a.lds_; t.ldo = a.ldo; t.ldw = a.ldw;
   t.ntn = (a.NP + 63) / 64;
@@ -853,28 +894,61 @@ void dvt_conv_tap_launch(const void* conv_args, int mode, int kind, int bm, void
   t.bn_cpb = (a.N + 7) & ~7;
   if (a.bn_x == nullptr) { t.bn_ws = nullptr; t.bn_sums = nullptr; t.bn_bytes = 0; }
   t.in_scale = a.in_scale; t.in_shift = a.in_shift; t.in_C = a.in_C; t.in_relu = a.in_relu;
-  const int grid = t.ntn * ((a.M + bm - 1) / bm);
-  hipStream_t s = (hipStream_t)stream;
+  l.grid = t.ntn * ((a.M + bm - 1) / bm);
   if (kind == 1) {
     t.halo = g.ph * g.sW + g.pw;
     t.npos = bm + 2 * t.halo;
     t.npp = t.npos + ((4 - t.npos % 8) + 8) % 8;
-    const size_t lds = 3 * 64 * 96 + (size_t)t.npp * 96 + 64;
-    if (bm == 128) launch_tap<0, 9, 2, false, 128>(t, grid, lds, s);        // (128 + 2 (W + 1) <= 256 positions: two units per thread)
-    else if (2 * t.npos <= 512) launch_tap<0, 9, 2>(t, grid, lds, s);
-    else launch_tap<0, 9, 3>(t, grid, lds, s);
+    l.lds = 3 * 64 * 96 + (size_t)t.npp * 96 + 64;
+    if (bm == 128) l.inst = TAP_SP128;                          // (128 + 2 (W + 1) <= 256 positions: two units per thread)
+    else if (2 * t.npos <= 512) l.inst = TAP_SP256_NU2;
+    else l.inst = TAP_SP256_NU3;
   } else {
     t.halo = 0;
     t.npos = bm;
     t.npp = t.npos + 4;
-    const size_t lds = 3 * 64 * 96 + (size_t)t.npp * 96 + 64;
-    if (bm == 128) {
-      if (a.in_scale != nullptr) launch_tap<1, 3, 1, true, 128>(t, grid, lds + (size_t)g.CP * 8, s);
-      else if (g.kt == 4) launch_tap<1, 4, 1, false, 128>(t, grid, lds, s);
-      else launch_tap<1, 3, 1, false, 128>(t, grid, lds, s);
-    }
-    else if (a.in_scale != nullptr) launch_tap<1, 3, 2, true>(t, grid, lds + (size_t)g.CP * 8, s);
-    else if (g.kt == 4) launch_tap<1, 4, 2>(t, grid, lds, s);
-    else launch_tap<1, 3, 2>(t, grid, lds, s);
+    l.lds = 3 * 64 * 96 + (size_t)t.npp * 96 + 64;
+    if (a.in_scale != nullptr) l.lds += (size_t)g.CP * 8;
+    if (a.in_scale != nullptr) l.inst = bm == 128 ? TAP_TM128_BNL : TAP_TM256_BNL;
+    else if (g.kt == 4) l.inst = bm == 128 ? TAP_TM128_K4 : TAP_TM256_K4;
+    else l.inst = bm == 128 ? TAP_TM128 : TAP_TM256;
   }
+  return l;
+}
+
+// l1: a second problem of the same instantiation for the same grid, or nullptr
+static void launch_tap_inst(const TapLaunch& l, const TapLaunch* l1, hipStream_t s) {
+  switch (l.inst) {
+    case TAP_SP128: launch_tap<0, 9, 2, false, 128>(l, l1, s); break;
+    case TAP_SP256_NU2: launch_tap<0, 9, 2>(l, l1, s); break;
+    case TAP_SP256_NU3: launch_tap<0, 9, 3>(l, l1, s); break;
+    case TAP_TM128_BNL: launch_tap<1, 3, 1, true, 128>(l, l1, s); break;
+    case TAP_TM128_K4: launch_tap<1, 4, 1, false, 128>(l, l1, s); break;
+    case TAP_TM128: launch_tap<1, 3, 1, false, 128>(l, l1, s); break;
+    case TAP_TM256_BNL: launch_tap<1, 3, 2, true>(l, l1, s); break;
+    case TAP_TM256_K4: launch_tap<1, 4, 2>(l, l1, s); break;
+    default: launch_tap<1, 3, 2>(l, l1, s); break;
+  }
+}
+
+void dvt_conv_tap_launch(const void* conv_args, int mode, int kind, int bm, void* stream) {
+  launch_tap_inst(tap_launch_of(*static_cast<const ConvArgs*>(conv_args), mode, kind, bm), nullptr, (hipStream_t)stream);
+}
+
+// Two launches in one grid (conv_tap_pair_kernel).  dvt_conv_tap_pair_inst: the instantiation both would run alone, or 0 where
+// they differ or a member may not share a grid: one that carries the fused BatchNorm-backward reduce (the members would share the
+// ticket workspace) or is a parity class of a strided data gradient.  The launch runs what the query said; conv.hip asks first.
+int dvt_conv_tap_pair_inst(const void* args0, int kind0, int bm0, const void* args1, int kind1, int bm1, int mode) {
+  const ConvArgs& a0 = *static_cast<const ConvArgs*>(args0);
+  const ConvArgs& a1 = *static_cast<const ConvArgs*>(args1);
+  if (!kind0 || kind0 != kind1 || bm0 != bm1) return 0;
+  if (a0.bn_x != nullptr || a1.bn_x != nullptr || a0.cls_on || a1.cls_on) return 0;
+  const int i0 = tap_launch_of(a0, mode, kind0, bm0).inst, i1 = tap_launch_of(a1, mode, kind1, bm1).inst;
+  return i0 == i1 ? i0 : 0;
+}
+
+void dvt_conv_tap_launch_pair(const void* args0, const void* args1, int mode, int kind, int bm, void* stream) {
+  const TapLaunch l0 = tap_launch_of(*static_cast<const ConvArgs*>(args0), mode, kind, bm);
+  const TapLaunch l1 = tap_launch_of(*static_cast<const ConvArgs*>(args1), mode, kind, bm);
+  launch_tap_inst(l0, &l1, (hipStream_t)stream);
 }

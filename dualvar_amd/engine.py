@@ -86,6 +86,10 @@ FUSE_BN_IN = os.environ.get('DUALVAR_FUSE_BN_IN', '1') != '0'         # (A/B swi
 # dy*g + dmean/S where it loads dy (dv_bn_bwd_*_multi_gated: the gated gradient is never written).  4 of the 14 passes over a
 # level's concat buffer and 2 launches per level less, same bits (tests/test_gate_fold_gpu.py).
 FUSE_GATE = os.environ.get('DUALVAR_FUSE_GATE', '1') != '0'        # (A/B switch; tests monkeypatch the module attribute)
+# Two independent convs that run the same instantiation of the LDS-staged kernel or of conv_gemm_ks -- the two separable branches
+# of an Inception level -- share one grid (dv_conv3d_fwd_pair / _fwd_bn_in_pair / _dgrad_pair): the small branch's launch is almost
+# all latency on a third of the chip.  An emit-time pass over the finished launch lists (pair_convs); '0' gives the unpaired lists.
+PAIR_CONVS = os.environ.get('DUALVAR_PAIR_CONVS', '1') != '0'      # (A/B switch; tests monkeypatch the module attribute)
 
 
 class Slot:
@@ -455,11 +459,13 @@ class Comm:
 
 class Launch:
     """One kernel launch of a plan: a bound C-ABI call plus its algorithmic cost (for the roofline report)."""
-    __slots__ = ('name', 'kname', 'fn', 'args', 'bytes', 'flops', 'shape', 'gend')
+    __slots__ = ('name', 'kname', 'fn', 'args', 'bytes', 'flops', 'shape', 'gend', 'pair', 'members')
 
     def __init__(self, name, kname, fn, args, nbytes=0, flops=0, shape=''):
         self.name, self.kname, self.fn, self.args, self.bytes, self.flops, self.shape = name, kname, fn, args, nbytes, flops, shape
         self.gend = 0                # end (element offset) of the highest gradient-arena range this launch writes
+        self.pair = None             # PairMember: this conv launch as one member of a shared grid (pair_convs), if it can be one
+        self.members = ()            # the two launches a paired launch replaces
 
     def __call__(self, stream):
         rc = self.fn(*self.args, stream)
@@ -558,6 +564,73 @@ class PlanGraph:
         for w in self._writers.values():
             for op, name, _ in w:
                 op.acc[name] = op is not w[-1][0]
+
+
+class PairMember:
+    """A conv forward / data-gradient launch as one member of a two-member grid: its arguments as the pair entry takes them, and
+    what it reads and writes (activations: ops.Act; flat buffers: tensors) for the independence check."""
+    __slots__ = ('role', 'desc', 'args', 'reads', 'writes')
+
+    def __init__(self, role, desc, args, reads, writes):
+        self.role, self.desc, self.args, self.reads, self.writes = role, desc, args, reads, [w for w in writes if w is not None]
+
+
+PAIR_ENTRIES = {'fwd': ('dv_conv3d_fwd_pair', 0), 'fwd_bn_in': ('dv_conv3d_fwd_bn_in_pair', L.DV_PAIR_BN_IN0 | L.DV_PAIR_BN_IN1),
+                'dgrad': ('dv_conv3d_dgrad_pair', L.DV_PAIR_DGRAD)}       # role -> (entry, dv_conv3d_pair_ok's mode)
+
+
+def _storage(t):
+    return _bufkey(t) if isinstance(t, ops.Act) else t.untyped_storage().data_ptr()
+
+
+def _written(t):
+    """(allocation, first, end): the channel columns of an activation's rows a conv writes / the elements of a flat buffer"""
+    if isinstance(t, ops.Act):
+        return _bufkey(t), t.off, t.off + t.cpitch
+    return t.untyped_storage().data_ptr(), t.storage_offset(), t.storage_offset() + t.numel()
+
+
+def pair_independent(m0, m1):
+    """Neither member reads an allocation the other writes into (any slice of it: conservative, as PlanGraph counts reads) and
+    they write disjoint ranges -- so `=` and `+=` into one gradient, or a conv that consumes the other's output, never pair."""
+    for a, b in ((m0, m1), (m1, m0)):
+        if any(_storage(w) == _storage(r) for w in a.writes for r in b.reads):
+            return False
+    for w0 in map(_written, m0.writes):
+        for w1 in map(_written, m1.writes):
+            if w0[0] == w1[0] and w0[1] < w1[2] and w1[1] < w0[2]:
+                return False
+    return True
+
+
+def pair_convs(lst, lib, side=()):
+    """The emit-time pass behind PAIR_CONVS: two launches of the same kind (conv_fwd / conv_dgrad) that are next to each other
+    but for launches named in `side` (the side stream's: they keep their order behind the pair), can both be members
+    (Launch.pair), are independent and route to one instantiation (dv_conv3d_pair_ok) become one launch at the earlier one's
+    position.  name stays; kname gets '+pair'; bytes and flops are the members' sums."""
+    out, i = [], 0
+    while i < len(lst):
+        l0 = lst[i]
+        m0 = getattr(l0, 'pair', None)
+        j = i + 1
+        if m0 is not None:
+            while j < len(lst) and lst[j].name in side:
+                j += 1
+        l1 = lst[j] if j < len(lst) else None
+        m1 = getattr(l1, 'pair', None)
+        if (m0 is not None and m1 is not None and l1.name == l0.name and m0.role == m1.role and pair_independent(m0, m1)
+                and int(lib.dv_conv3d_pair_ok(C.byref(m0.desc), C.byref(m1.desc), PAIR_ENTRIES[m0.role][1]))):
+            extra = (0, 0) if m0.role == 'dgrad' else ()          # (no member carries the fused reduce: no workspace)
+            p = Launch(l0.name, l0.kname + '+pair', getattr(lib, PAIR_ENTRIES[m0.role][0]), m0.args + m1.args + extra,
+                       l0.bytes + l1.bytes, l0.flops + l1.flops, l0.shape + ' | ' + l1.shape)
+            p.gend, p.members = max(l0.gend, l1.gend), (l0, l1)
+            out.append(p)
+            out += lst[i + 1:j]
+            i = j + 1
+        else:
+            out.append(l0)
+            i += 1
+    return out
 
 
 class Plan:
@@ -799,6 +872,10 @@ class Plan:
         t_conv = sum(max(l.flops / 1.5e14, l.bytes / 4e12) for l in self.b_list if l.name == 'conv_dgrad')
         t_other = sum(l.bytes / 4e12 for l in self.b_list if l.name != 'conv_dgrad' and l.name not in SIDE_LAUNCHES)
         self.wgrad_early = (t_other >= WGRAD_EARLY_RATIO * t_conv) if WGRAD_EARLY == 'auto' else WGRAD_EARLY == '1'
+        # (after the estimate above, which so sees one launch per conv as it always has)
+        if PAIR_CONVS and self.dtype == DV_F32:
+            self.f_list = pair_convs(self.f_list, self.lib)
+            self.b_list = pair_convs(self.b_list, self.lib, SIDE_LAUNCHES)
 
     # ------------------------------------------------------------------ execution
     def _run(self, lst):
@@ -1000,8 +1077,15 @@ class ConvOp(Op):
             f = [Launch('conv_fwd', _conv_kname(lib, self.d_in, 0, _dt(self.dtype), gv) + '+bn_in', lib.dv_conv3d_fwd_bn_in,
                         (C.byref(self.d_in), m.x.ptr, C.byref(r), self._wf, y.ptr, self.stats.data_ptr() if self.stats is not None else 0),
                         _abytes(x) + wbytes + _abytes(y), flops, shp + ' +bn_in')]
+        stats_ptr = self.stats.data_ptr() if self.stats is not None else 0
         if self.fp8:
             f = self._fp8_forward(shp, flops, wbytes)
+        elif self.bn_in is not None:
+            m = self.bn_in
+            f[0].pair = PairMember('fwd_bn_in', self.d_in, (C.byref(self.d_in), m.x.ptr, C.byref(self._bn_in), self._wf, y.ptr, stats_ptr),
+                                   [m.x, m.scale, m.shift], [y, self.stats])
+        else:
+            f[0].pair = PairMember('fwd', self.d, (C.byref(self.d), x.ptr, self._wf, y.ptr, stats_ptr), [x], [y, self.stats])
         b = []
         if p.with_grad:
             self.d_w = ops.conv_desc(self.dtype, x, y, self.k, self.s, self.p, flags=0)
@@ -1073,6 +1157,8 @@ class ConvOp(Op):
                 else:
                     b.append(Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad, (C.byref(self.d_g), y.grad.ptr, wdp, x.grad.ptr),
                                     _abytes(y) + wbytes + _abytes(x) * (2 if acc else 1), flops, shp))
+                    b[-1].pair = PairMember('dgrad', self.d_g, (C.byref(self.d_g), y.grad.ptr, wdp, x.grad.ptr, 0),
+                                            [y.grad] + ([x.grad] if acc else []), [x.grad])
         return f, b
 
 

@@ -9,7 +9,8 @@ check for a change of the planning code that is meant to change no plan.
     python tools/plan_dump.py --nets s3dg --args --exchange     # the same plans on the multi-rank path (one gloo rank)
 
 Per plan: every entry of the forward and the backward list (name, kernel, shape, bytes, flops, gradient-arena end), per op its
-accumulate flags and the fusions it takes, and the plan's bytes.  Pointers differ from run to run: they are left out, or, with
+accumulate flags and the fusions it takes, and the plan's bytes.  Two convs that share a grid (engine.PAIR_CONVS) are one entry:
+kernel '...+pair', both shapes, the members' bytes and flops summed; the setting no_pair dumps the unpaired lists.  Pointers differ from run to run: they are left out, or, with
 --args, printed as (ordinal of the storage they point into, in order of first appearance in the plan's dump; byte offset)."""
 import argparse
 import bisect
@@ -28,14 +29,15 @@ from dualvar_amd import _lib as L, engine                           # noqa: E402
 from dualvar_amd.backbone.select_backbone import select_backbone    # noqa: E402
 
 NETS = ('s3dg', 's3d', 'r21d', 'r3d', 'r50', 'r2d3d18', 'c3d')
-SWITCHES = ('FUSE_BN_REDUCE', 'FUSE_BN_REDUCE_TAP', 'FUSE_BN_IN', 'FUSE_BN_WGRAD', 'FUSE_GATE')
-DEFAULT = dict(FUSE_BN_REDUCE=False, FUSE_BN_REDUCE_TAP=False, FUSE_BN_IN=True, FUSE_BN_WGRAD=True, FUSE_GATE=True)
+SWITCHES = ('FUSE_BN_REDUCE', 'FUSE_BN_REDUCE_TAP', 'FUSE_BN_IN', 'FUSE_BN_WGRAD', 'FUSE_GATE', 'PAIR_CONVS')
+DEFAULT = dict(FUSE_BN_REDUCE=False, FUSE_BN_REDUCE_TAP=False, FUSE_BN_IN=True, FUSE_BN_WGRAD=True, FUSE_GATE=True, PAIR_CONVS=True)
 SETTINGS = (('default', {}),
             ('reduce', dict(FUSE_BN_REDUCE=True, FUSE_BN_REDUCE_TAP=False)),
             ('reduce_tap', dict(FUSE_BN_REDUCE_TAP=True)),
             ('no_bn_in', dict(FUSE_BN_IN=False)),
             ('no_bn_wgrad', dict(FUSE_BN_WGRAD=False)),
-            ('no_gate', dict(FUSE_GATE=False)))
+            ('no_gate', dict(FUSE_GATE=False)),
+            ('no_pair', dict(PAIR_CONVS=False)))
 MODES = (('train_grad', True, False, True), ('train_nograd', True, False, False), ('eval_map', False, True, False))
 OP_FLAGS = ('bn_fuse', 'bn_fuse_tap', 'bn_apply', 'bn_in', 'fused', 'bn_member')
 ARG_PREFIXES = ('bn_', 'gate_', 'syncbn_')
@@ -115,8 +117,9 @@ def dump_plan(plan, out, args=False):
 
 def counts(plan):
     n = lambda f: sum(1 for op in plan.ops if getattr(op, f, None) not in (None, False))      # noqa: E731
-    return 'bn_in %d  bn_apply %d  gates %d  pools %d  bn_fuse %d  bn_fuse_tap %d' % (
-        n('bn_in'), n('bn_apply'), n('fused'), n('bn_member'), n('bn_fuse'), n('bn_fuse_tap'))
+    pairs = sum(1 for l in plan.f_list + plan.b_list if getattr(l, 'members', ()))
+    return 'bn_in %d  bn_apply %d  gates %d  pools %d  bn_fuse %d  bn_fuse_tap %d  conv pairs %d' % (
+        n('bn_in'), n('bn_apply'), n('fused'), n('bn_member'), n('bn_fuse'), n('bn_fuse_tap'), pairs)
 
 
 def main():
