@@ -2248,6 +2248,8 @@ extern "C" int dv_pack_dgrad_weights(int32_t dtype, const float* master, void* d
 // ------------------------------------------------------------------------------------------
 // fp8 quantisation for the pointwise-conv GEMMs (dv_conv3d_fwd_fp8 / dv_conv3d_dgrad_fp8): per-tensor scaling,
 //   scale = amax / FMAX (448 for e4m3, 57344 for e5m2; 1 when the tensor is all zero),  q = fp8(x / scale)  (RNE, finite).
+// The quotient is a true fp32 division: a reciprocal 1 / scale overflows to +inf once amax < FMAX * 2^-128 (scale an fp32
+// subnormal; bf16 gradients reach that), after which every non-zero element saturated and every zero became 0 * inf = NaN.
 // Two launches and no atomics: block maxima -> every block of the second launch folds them (<= 1024 floats) and converts.
 #include <hip/hip_fp8.h>
 namespace {
@@ -2292,7 +2294,6 @@ __global__ void __launch_bounds__(256) quantize_fp8_kernel(const T* __restrict__
   constexpr float FMAX = FMT == 0 ? 448.f : 57344.f;
   const float amax = s_amax;
   const float scale = amax > 0.f ? amax / FMAX : 1.f;
-  const float inv = 1.f / scale;
   if (blockIdx.x == 0 && threadIdx.x == 0) scale_out[0] = scale;
   const int vpr = C / 16;                                       // 16 fp8 per 16-byte store
   const int64_t total = M * vpr;
@@ -2307,7 +2308,7 @@ __global__ void __launch_bounds__(256) quantize_fp8_kernel(const T* __restrict__
       Pack16<T>::load(x + r * ld + cv * 16 + hv * V, v);
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        const float t = fminf(fmaxf(v[e] * inv, -FMAX), FMAX);
+        const float t = fminf(fmaxf(v[e] / scale, -FMAX), FMAX);
         o.b[hv * V + e] = __hip_cvt_float_to_fp8(t, __HIP_SATFINITE, FMT == 0 ? __HIP_E4M3 : __HIP_E5M2);
       }
     }

@@ -210,7 +210,12 @@ int dv_conv3d_wgrad_bn_in(const dv_conv_desc* d, const void* x_bn, const dv_bn_i
  * operands it runs on v_mfma_f32_32x32x64_f8f6f4 (fp32 accumulate, twice the bf16 rate per clock).  Operands are quantised
  * per TENSOR: dv_quantize_fp8 computes amax, scale = amax / 448 (e4m3; 57344 for e5m2) and q = fp8_rne(x / scale) into a
  * dense [M][ldq] byte tensor (channel pitch a multiple of 16); the GEMMs multiply the fp32 accumulators by the two scales
- * (device scalars: no host round trip).  Forward: x, w e4m3 -> y bf16 (+ DV_STATS partials like dv_conv3d_fwd); data
+ * (device scalars: no host round trip).  To the letter: scale_out = fl32(amax / FMAX), the correctly rounded fp32 quotient
+ * (1 for an all-zero tensor; an fp32 subnormal, still > 0, for amax < FMAX 2^-126), and each byte is the OCP code nearest to
+ * t = fl32(x / scale_out) -- the fp32 QUOTIENT, a true division, not a product with a reciprocal (which overflows for a
+ * subnormal scale) --, ties to the even mantissa, saturating at +-FMAX, the sign of x kept (+-0 -> 0x00 / 0x80).  Against the
+ * rounding of the exact x / scale this differs only where the second rounding matters: x / scale within 2^-24 of a midpoint
+ * between two codes.  The input must be finite: what a NaN or inf element does to amax and to the bytes is not defined.  Forward: x, w e4m3 -> y bf16 (+ DV_STATS partials like dv_conv3d_fwd); data
  * gradient: dy e5m2, w (dgrad layout [Cin][CoutP]) e4m3 -> dx bf16 (DV_ACCUM as dv_conv3d_dgrad).  The weight gradient stays
  * on the bf16 path (dv_conv3d_wgrad on the bf16 tensors): its reduction runs over up to 4e5 rows.
  * `d` describes the bf16 side (dtype DV_BF16, pitches of y / dx in elements); ldx / ldy of the fp8 operand are in BYTES. */

@@ -317,14 +317,14 @@ def members(c):
     return out
 
 
-# Members only a DUALVAR_* switch reaches (read once per process: a child pytest each) and the fp8 pair.  NOT COVERED YET: the
-# table has no rows for them and tests/test_conv_float64_gpu.py starts no child process.  (Said here in words; nothing asserts on it.)
+# Members only a DUALVAR_* switch reaches (read once per process: a child pytest each).  NOT COVERED YET: the table has no rows
+# for them and tests/test_conv_float64_gpu.py starts no child process.  (Said here in words; nothing asserts on it.)  The fp8
+# pair has a table and a float64 file of its own: tests/fp8_cases.py, tests/test_fp8_float64_gpu.py.
 NOT_COVERED_YET = {
     'DUALVAR_CONV_TAP_GRID=1': 'the LDS-staged kernels on small ragged shapes (tools/tap_check.py runs them against torch float64)',
     'DUALVAR_WGRAD_F32S=0|2': 'conv_wgrad_f32s_kernel, the opt-in second fp32 weight-gradient form (conv_experiments.hip)',
     'DUALVAR_F32_EXACT=1': 'the f32-input MFMA kernels (tests/test_ops_gpu.py runs them against torch fp32 in its A/B mode)',
     'DUALVAR_CONV_TAP_BM128': 'the LDS-staged kernel with its 128-row tiles switched off',
-    'fp8': 'dv_conv3d_fwd_fp8 / dv_conv3d_dgrad_fp8 on exact fp8 operands',
     'bf16:G2,G3': 'DV_BF16 rows run G1 (with ties) and Gaussian data only; the multi-plane grids are not bf16 numbers as written',
     'route:NONE': 'refused calls (DV_EUNSUPPORTED) launch nothing; tests/test_abi_and_host.py checks the refusals',
 }

@@ -975,7 +975,7 @@ def test_every_abi_entry_names_its_strongest_test():
     """tests/abi_coverage.py maps every entry of _lib.SIGNATURES to the test file that holds its strongest reference test and
     to the kind of that reference; each file mentions its entry.  (dv_check_device and dv_quantize_fp8_workspace are checked
     here only to be exported with the declared signature; dv_bn_bwd_blocks and dv_bn_bwd_reduce_workspace by the case-table
-    test above.)  No BatchNorm entry is 'torch fp32 only'; what still is -- the fp8 trio -- is the next gap."""
+    test above.)  No entry is 'torch fp32 only' any more: the fp8 trio, the last one, has tests/test_fp8_float64_gpu.py."""
     from dualvar_amd import _lib
     from tests import abi_coverage as A
     assert set(A.ENTRY_COVERAGE) == set(_lib.SIGNATURES), sorted(set(A.ENTRY_COVERAGE) ^ set(_lib.SIGNATURES))
@@ -988,7 +988,7 @@ def test_every_abi_entry_names_its_strongest_test():
         assert re.search(r'\b%s\b' % name, text[fname]), '%s is not mentioned in tests/%s' % (name, fname)
     weak = sorted(n for n, (_, k) in A.ENTRY_COVERAGE.items() if k == A.TORCH_FP32)
     assert not [n for n in weak if n.startswith('dv_bn_') or n in ('dv_addcmul_f32', 'dv_fill_cols_f32')], weak
-    assert weak == ['dv_conv3d_dgrad_fp8', 'dv_conv3d_fwd_fp8', 'dv_quantize_fp8'], weak
+    assert weak == [], weak
 
 
 def test_ordered_fold_protocol_has_one_home():

@@ -52,8 +52,9 @@ Epilogue flags (DV_BIAS, DV_RELU, DV_SIGMOID): bias is G1 data, so relu(conv + b
     tests/test_loss_gemm_optim_gpu.py, and 2u for the addition and the division.
 
 NOT COVERED YET (tests/conv_cases.py: NOT_COVERED_YET says the same to the CPU test): the kernels only a DUALVAR_* switch
-reaches (DUALVAR_F32_EXACT=1, DUALVAR_WGRAD_F32S, DUALVAR_CONV_TAP_GRID=1 small ragged tap shapes, DUALVAR_CONV_TAP_BM128),
-the fp8 pair, and the multi-plane grids G2 / G3 for DV_BF16 (its rows run G1 with ties and Gaussian data).
+reaches (DUALVAR_F32_EXACT=1, DUALVAR_WGRAD_F32S, DUALVAR_CONV_TAP_GRID=1 small ragged tap shapes, DUALVAR_CONV_TAP_BM128)
+and the multi-plane grids G2 / G3 for DV_BF16 (its rows run G1 with ties and Gaussian data).  The fp8 pair (the 24 fp8
+conv_gemm kernels) is covered by tests/test_fp8_float64_gpu.py over tests/fp8_cases.py.
 
 Each case prints (-s) err / bound; the module prints the largest err / bound per quantity and route at the end.
 The measured figures (largest err / bound per quantity and route, the rms figures next to torch fp32's, the mutants) are in
