@@ -128,6 +128,8 @@ def parse_args(argv=None):
     p.add_argument('--ridge', action='store_true', help='with --test ... --retrieval: also the closed-form ridge probe, fitted on the train clip features and scored on the test clips')
     p.add_argument('--ridge_lambda', default=[1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1], type=float, nargs='*', help='the grid of lambda (relative to the number of training clips)')
     p.add_argument('--ridge_holdout', default=5, type=int, help='one training video in this many, per class, is held out to choose lambda')
+    p.add_argument('--spectrum', action='store_true', help='with --test ... --retrieval: also the eigenvalue spectrum of the clip-feature covariance (effective rank, RankMe, alpha, PCA retrieval)')
+    p.add_argument('--spectrum_k', default=[32, 64, 128], type=int, nargs='*', help='the numbers of leading principal components to project on (values above the feature width are clamped)')
     p.add_argument('--center_crop', action='store_true')
     p.add_argument('--five_crop', action='store_true')
     p.add_argument('--ten_crop', action='store_true')
@@ -208,6 +210,10 @@ def check_args(args, environ=None):
         refuse('--ridge_lambda takes one or more positive finite values')
     if args.ridge_holdout < 2:
         refuse('--ridge_holdout must be at least 2')
+    if args.spectrum and not (args.test and args.retrieval):
+        refuse('--spectrum decomposes the covariance of the retrieval clip features: pass --test <checkpoint> --retrieval with it')
+    if not args.spectrum_k or any(k < 1 for k in args.spectrum_k):
+        refuse('--spectrum_k takes one or more component counts of at least 1')
     if args.test:
         if args.retrieval:
             if args.num_seq != 10:
@@ -559,7 +565,7 @@ def test_retrieval(model, epoch, args):
             per_feature = torch.cat(per_feature, dim=0)
             torch.save(per_feature, os.path.join(out_dir, '%s_%s_per_feature.pth.tar' % (args.dataset, split)))
             feats[split] = (feature, label)
-            if args.variance or args.tsne or args.cluster or args.ridge:
+            if args.variance or args.tsne or args.cluster or args.ridge or args.spectrum:
                 clips[split] = per_feature
     acc, sim = nn_retrieval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1], ks=(1, 5, 10, 20, 50))
     torch.save(sim, os.path.join(out_dir, '%s_sim.pth.tar' % args.dataset))
@@ -599,7 +605,52 @@ def test_retrieval(model, epoch, args):
             write_cluster(clips[split], feats[split][1], split, out_dir, args)
     if args.ridge:
         write_ridge(clips['train'], feats['train'][1], clips['test'], feats['test'][1], out_dir, args)
+    if args.spectrum:
+        write_spectrum(clips, feats, out_dir, args)
     return acc
+
+
+def write_spectrum(clips, feats, out_dir, args):
+    """--spectrum: the eigenvalue spectrum of each split's clip-feature covariance -> <dataset>_{test,train}_spectrum.json, and
+    the train fit (mean, leading components, eigenvalues) -> <dataset>_spectrum.pth.tar, with the retrieval repeated on its PCA
+    projections in the train JSON; the only writer of these three files"""
+    from dualvar_amd.utils.spectrum import pca_retrieval, spectrum_eval
+
+    def show(v):                         # a share whose eigenvalue is numerically zero is None
+        return 'n/a' if v is None else '%.4f' % v
+    D = clips['train'].shape[-1]
+    ks = sorted({min(k, D) for k in args.spectrum_k})
+    if any(k > D for k in args.spectrum_k):
+        args.logger.info('spectrum: --spectrum_k %s clamped to the feature width %d: %s'
+                         % (' '.join(str(k) for k in args.spectrum_k), D, ' '.join(str(k) for k in ks)))
+    for split in ('test', 'train'):
+        rep = spectrum_eval(clips[split], feats[split][1], ks=tuple(ks))
+        met, info = rep['metrics'], rep['info']
+        args.logger.info('Spectrum of %s %s (%d clips, D = %d; %d sweeps, %d rotations%s):'
+                         % (args.dataset, split, met['n'], met['D'], info['sweeps'], info['rotations'],
+                            '' if info['converged'] else ', NOT converged'))
+        args.logger.info('\teffective rank = %.2f RankMe = %.2f participation ratio = %.2f numerical rank = %d'
+                         % (met['effective_rank'], met['rankme'], met['participation_ratio'], met['numerical_rank']))
+        args.logger.info('\ttop-1 share = %s alpha = %s (R2 = %s) dims for 90 / 95 / 99 %% = %s'
+                         % (show(met['top1_share']), show(met['alpha']), show(met['alpha_r2']),
+                            ' / '.join(str(v) for v in met['dims_for'].values())))
+        args.logger.info('\tbetween-video share of the first components: %s' % ' '.join(show(v) for v in rep['video_share'][:8]))
+        out = {'metrics': met, 'info': info, 'video_share': rep['video_share'], 'ks': rep['ks'],
+               'eigenvalues': rep['eigenvalues'].cpu().tolist()}
+        if split == 'train':
+            ret_ks = [k for k in rep['ks'] if k % 8 == 0]
+            if len(ret_ks) < len(rep['ks']):
+                args.logger.info('spectrum: PCA retrieval takes component counts that are multiples of 8: %s left out'
+                                 % ' '.join(str(k) for k in rep['ks'] if k % 8))
+            res = pca_retrieval(feats['train'][0], feats['train'][1], feats['test'][0], feats['test'][1], rep['mean'],
+                                rep['components'], rep['eigenvalues'], ret_ks)
+            for k, row in res.items():
+                args.logger.info('\tPCA retrieval, %d components: 1NN acc = %.4f whitened = %.4f' % (k, row['pca'], row['whitened']))
+            out['pca_retrieval'] = {str(k): row for k, row in res.items()}
+            torch.save({'mean': rep['mean'].cpu(), 'components': rep['components'][:rep['ks'][-1]].cpu(),
+                        'eigenvalues': rep['eigenvalues'].cpu()}, os.path.join(out_dir, '%s_spectrum.pth.tar' % args.dataset))
+        with open(os.path.join(out_dir, '%s_%s_spectrum.json' % (args.dataset, split)), 'w') as fp:
+            json.dump(out, fp, indent=1)
 
 
 def write_ridge(train_clips, train_label, test_clips, test_label, out_dir, args):

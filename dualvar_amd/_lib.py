@@ -20,6 +20,8 @@ DV_PAIRSTAT_MAX_BINS = 256    # == DV_PAIRSTAT_MAX_BINS of include/dualvar_pairs
 DV_KMEANS_MAX_K = 4096       # == DV_KMEANS_MAX_K of include/dualvar_cluster.h: the most clusters of the dv_kmeans_* entries
 DV_RIDGE_MAX_D = 4096       # == DV_RIDGE_MAX_D of include/dualvar_ridge.h: the widest feature row of the dv_ridge_* entries
 DV_RIDGE_MAX_C = 4096       # == DV_RIDGE_MAX_C of include/dualvar_ridge.h: the most classes of the dv_ridge_* entries
+DV_SPECTRUM_MAX_D = 4096    # == DV_SPECTRUM_MAX_D of include/dualvar_spectrum.h: the largest matrix order of the dv_spectrum_* entries
+DV_SPECTRUM_MAX_SWEEPS = 64  # == DV_SPECTRUM_MAX_SWEEPS of include/dualvar_spectrum.h: the cap on Jacobi sweeps of utils.spectrum.eigh_jacobi
 DV_W3 = 128                  # conv fwd / dgrad in DV_F32: weights pre-split in fragment order (dv_pack_w3)
 
 _ERR = {-1: 'DV_EINVAL (inconsistent shapes / unsupported parameter)',
@@ -229,6 +231,16 @@ RIDGE_SIGNATURES = {
     'dv_ridge_solve_f64': [P, I64, I32, I32, C.c_double, P, I64, I32, P, I64, P, I64, P, P],
 }
 
+# name -> argtypes of include/dualvar_spectrum.h (the covariance and Jacobi eigensolver entries of csrc/spectrum.hip)
+SPECTRUM_SIGNATURES = {
+    'dv_spectrum_cov_f64': [P, I64, I32, P, I64, P, P],
+    'dv_spectrum_rounds': [I32],
+    'dv_spectrum_pair': [I32, I32, I32, P, P],
+    'dv_spectrum_init_f64': [P, I64, I32, P, I64, P, I64, P, P],
+    'dv_spectrum_rounds_f64': [P, I64, P, I64, I32, I32, I32, P, P, P],
+    'dv_spectrum_values_f64': [P, I64, P, I64, I32, P, P],
+}
+
 # name -> argtypes of include/dualvar_conv_pair.h (two independent convs in one grid: csrc/conv.hip, csrc/conv_tap.hip)
 PAIR_SIGNATURES = {
     'dv_conv3d_pair_ok': [CD, CD, I32],
@@ -257,7 +269,7 @@ def load():
     # same HIP runtime (loading ours first binds it to /opt/rocm's copy and every launch then reports "no device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(RIDGE_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(RIDGE_SIGNATURES.items()) + list(SPECTRUM_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI and this table disagree
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
