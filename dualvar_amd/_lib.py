@@ -249,6 +249,23 @@ PAIR_SIGNATURES = {
     'dv_conv3d_dgrad_pair': [CD, P, P, P, P, CD, P, P, P, P, P, I64, P],
 }
 
+# header under include/ -> its table: the one registry of the bindings (load() binds what it lists; tests/util.py checks each
+# table against its header).  A name belongs to one header.
+HEADERS = {
+    'dualvar_hip.h': SIGNATURES,
+    'dualvar_select.h': SELECT_SIGNATURES,
+    'dualvar_pairstat.h': PAIRSTAT_SIGNATURES,
+    'dualvar_tsne.h': TSNE_SIGNATURES,
+    'dualvar_cluster.h': CLUSTER_SIGNATURES,
+    'dualvar_ridge.h': RIDGE_SIGNATURES,
+    'dualvar_spectrum.h': SPECTRUM_SIGNATURES,
+    'dualvar_conv_pair.h': PAIR_SIGNATURES,
+}
+_names = [n for table in HEADERS.values() for n in table]
+_twice = sorted({n for n in _names if _names.count(n) > 1})
+if _twice:
+    raise ImportError('declared in two tables of _lib.HEADERS: %s' % ', '.join(_twice))
+
 _lib = None
 
 
@@ -269,10 +286,11 @@ def load():
     # same HIP runtime (loading ours first binds it to /opt/rocm's copy and every launch then reports "no device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(PAIRSTAT_SIGNATURES.items()) + list(TSNE_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()) + list(RIDGE_SIGNATURES.items()) + list(SPECTRUM_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
-        fn = getattr(lib, name)          # AttributeError if the ABI and this table disagree
-        fn.argtypes = argtypes
-        fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
+    for table in HEADERS.values():
+        for name, argtypes in table.items():
+            fn = getattr(lib, name)      # AttributeError if the ABI and this table disagree
+            fn.argtypes = argtypes
+            fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
     got = lib.dv_abi_version()
     if got != ABI_VERSION:
         raise DualVarHipError(f'libdualvar_hip.so reports ABI version {got}, this binding was written against {ABI_VERSION}: '

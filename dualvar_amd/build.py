@@ -2,6 +2,7 @@
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the build container; the
 resulting .so travels to the GPU box with the repo snapshot."""
+import glob
 import os
 import subprocess
 import sys
@@ -47,12 +48,7 @@ def parse_resources(text):
 
 def build_lib(force=False, verbose=False):
     hipcc = os.environ.get('HIPCC', 'hipcc')
-    hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'conv_common.hpp'), os.path.join(CSRC, 'ordered_fold.hpp'),
-            os.path.join(HERE, '..', 'include', 'dualvar_hip.h'),
-            os.path.join(HERE, '..', 'include', 'dualvar_select.h'), os.path.join(HERE, '..', 'include', 'dualvar_pairstat.h'),
-            os.path.join(HERE, '..', 'include', 'dualvar_tsne.h'), os.path.join(HERE, '..', 'include', 'dualvar_cluster.h'),
-            os.path.join(HERE, '..', 'include', 'dualvar_ridge.h'), os.path.join(HERE, '..', 'include', 'dualvar_spectrum.h'),
-            os.path.join(HERE, '..', 'include', 'dualvar_conv_pair.h')]
+    hdrs = glob.glob(os.path.join(CSRC, '*.hpp')) + glob.glob(os.path.join(HERE, '..', 'include', '*.h'))   # every source depends on all
     objs = []
     procs = []
     for src in SOURCES:

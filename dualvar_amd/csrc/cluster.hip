@@ -9,8 +9,6 @@
 #include "common.hpp"
 #include "../../include/dualvar_cluster.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 #define KM_PART DV_KMEANS_PART
 #define KM_SORT_ROWS DV_KMEANS_SORT_ROWS
 #define KM_SEED_BLOCK DV_KMEANS_SEED_BLOCK
@@ -19,15 +17,6 @@
 static_assert(KM_SEED_BLOCK == 256, "a thread owns a row of its seed block");
 static_assert(KM_SORT_ROWS % 256 == 0 && KM_SORT_ROWS % 64 == 0, "the sort blocks are walked by 256 threads and by one wavefront");
 static_assert(KM_PART <= 256, "a part's row indices are staged by one pass of the workgroup");
-
-// 256 doubles, one per thread -> their sum in every thread: wave fold, then the four wave totals in ascending order
-__device__ __forceinline__ double km_block_sum_f64(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 // --------------------------------------------------------------------------------------------------------------- assign
 // G lanes per row, 256 / G rows per workgroup
@@ -310,7 +299,7 @@ __global__ void __launch_bounds__(256) kmeans_centroid_kernel(const double* __re
     const double v = sk[d];
     ss += v * v;
   }
-  const double nrm = sqrt(km_block_sum_f64(ss, sh));
+  const double nrm = sqrt(block_sum_f64(ss, sh));
   const bool ok = count > 0 && nrm > 0.0 && nrm < (double)INFINITY;
   for (int d = threadIdx.x; d < D; d += 256) {
     const size_t at = (size_t)k * (size_t)ldc + d;

@@ -95,6 +95,27 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
 }
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// 256 doubles, one per thread -> their sum in every thread: wave fold, then the four wave totals in ascending order.
+// sh: 4 doubles of LDS; the caller synchronises before it reuses them.
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// the opaque stream argument of the C ABI
+#define ST(s) ((hipStream_t)(s))
 
 static inline int dv_launch_status() {
   hipError_t e = hipGetLastError();

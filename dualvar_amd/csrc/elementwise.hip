@@ -1595,7 +1595,6 @@ __global__ void pack_dgrad_kernel(const float* __restrict__ master, CT* __restri
 
 }  // namespace
 
-#define ST(s) ((hipStream_t)(s))
 #define DISPATCH_T(dtype, ...)                                  \
   do {                                                          \
     if ((dtype) == DV_F32) { typedef float T; __VA_ARGS__; }    \

@@ -484,8 +484,6 @@ __global__ void group_mean_bwd_kernel(const float* __restrict__ dy, int R, int G
 
 }  // namespace
 
-#define ST(s) ((hipStream_t)(s))
-
 extern "C" int dv_gemm_f32(int32_t M, int32_t N, int32_t K, const float* A, int64_t sam, int64_t sak, const float* B,
                            int64_t sbk, int64_t sbn, float* C, int64_t ldc, float alpha, int32_t accumulate,
                            void* stream) {

@@ -234,7 +234,6 @@ __global__ __launch_bounds__(kLarsThreads) void lars_step_kernel(float* __restri
 
 }  // namespace
 
-#define ST(s) ((hipStream_t)(s))
 // The compute copy of an entry: a bf16 copy instantiates the kernel with bf16_t, everything else with float, and that
 // copy pointer is null unless the dtype is DV_F32.  LAUNCH names the kernel as K<CT> and the copy as (CT*)cp.
 #define LAUNCH_COPY(copy_dtype, p_copy, LAUNCH)                                                                       \

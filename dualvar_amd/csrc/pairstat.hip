@@ -8,8 +8,6 @@
 #include "common.hpp"
 #include "../../include/dualvar_pairstat.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 #define PS_THREADS 256
 #define PS_TR 64                                // rows of a tile
 #define PS_TC (4 * PS_THREADS)                  // columns of a tile: four per lane
@@ -25,17 +23,6 @@ static inline int64_t pairstat_tiles(int32_t R, int32_t n_cols) { return cdiv64(
 static inline int pairstat_grid(int32_t R, int32_t n_cols) {
   const int64_t tiles = pairstat_tiles(R, n_cols);
   return (int)(tiles < PS_MAX_GRID ? tiles : PS_MAX_GRID);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
 }
 
 __global__ void __launch_bounds__(PS_THREADS) pairstat_zero_kernel(unsigned long long* __restrict__ hist, int ldh, int bins) {

@@ -8,8 +8,6 @@
 #include "common.hpp"
 #include "../../include/dualvar_ridge.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
 #define RG_TILE DV_RIDGE_TILE

@@ -5,8 +5,6 @@
 #include "common.hpp"
 #include "../../include/dualvar_select.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 // The total order "larger value first, then smaller index" as ONE unsigned comparison: the value's bits made monotone
 // (negative: all bits flipped, else the sign bit set) in the high word, ~index in the low word.  v + 0.0f folds -0 into +0.
 // A real candidate (value > -inf) has a high word above 0x007fffff, so key 0 is free to mean "empty slot" and sorts last.

@@ -10,7 +10,6 @@
 #include "common.hpp"
 #include "../../include/dualvar_spectrum.h"
 
-#define ST(s) ((hipStream_t)(s))
 #define SP_BLOCK DV_SPECTRUM_BLOCK
 
 static_assert(SP_BLOCK == 256, "the fold tree below starts at 128");

@@ -9,34 +9,13 @@
 #include "common.hpp"
 #include "../../include/dualvar_tsne.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 #define TS_ROWS DV_TSNE_ROWS
 #define TS_TILE DV_TSNE_TILE
 #define TS_SLOTS (DV_TOPK_MAX_K / 64)           // list slots a lane holds in registers
 #define TS_TARGET_WGS 1024                      // four workgroups per CU
 
 static_assert(TS_ROWS == TS_TILE, "the tile that holds a workgroup's own rows is found as tile == blockIdx.x");
-static_assert(TS_ROWS == 256, "the folds below take four wavefronts");
-
-__device__ __forceinline__ double ts_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float ts_wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// 256 doubles, one per thread -> their sum in thread 0: wave fold, then the four wave totals in ascending order
-__device__ __forceinline__ double ts_block_sum_f64(double v, double* sh) {
-  v = ts_wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
+static_assert(TS_ROWS == 256, "block_sum_f64 folds four wavefronts");
 
 // ---------------------------------------------------------------------------------------------------------- perplexity
 __global__ void __launch_bounds__(64) tsne_perplexity_kernel(const float* __restrict__ top_val, const int* __restrict__ top_idx,
@@ -64,7 +43,7 @@ __global__ void __launch_bounds__(64) tsne_perplexity_kernel(const float* __rest
       ++cnt;
     }
   }
-  m = ts_wave_min(m);
+  m = wave_min(m);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
   float emax = 0.f;
@@ -155,9 +134,9 @@ __global__ void __launch_bounds__(64) tsne_attract_kernel(const float* __restric
       if (pe > 0.f) tsne_edge(y, yix, yiy, f / ldk, pe * inv2n, acc);
     }
   }
-  acc.x = ts_wave_sum_f64(acc.x);
-  acc.y = ts_wave_sum_f64(acc.y);
-  acc.c = ts_wave_sum_f64(acc.c);
+  acc.x = wave_sum_f64(acc.x);
+  acc.y = wave_sum_f64(acc.y);
+  acc.c = wave_sum_f64(acc.c);
   if (lane == 0) {
     fa[2 * (size_t)i] = (float)acc.x;
     fa[2 * (size_t)i + 1] = (float)acc.y;
@@ -171,7 +150,7 @@ __global__ void __launch_bounds__(256) tsne_total_kernel(const T* __restrict__ v
   __shared__ double sh[4];
   double a = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) a += (double)v[i];
-  a = ts_block_sum_f64(a, sh);
+  a = block_sum_f64(a, sh);
   if (threadIdx.x == 0) *out = a;
 }
 
@@ -277,7 +256,7 @@ __global__ void __launch_bounds__(TS_ROWS) tsne_repulse_fold_kernel(const double
     fr[2 * (size_t)i] = (float)sx;
     fr[2 * (size_t)i + 1] = (float)sy;
   }
-  sz = ts_block_sum_f64(sz, sh);
+  sz = block_sum_f64(sz, sh);
   if (threadIdx.x == 0) zblock[blockIdx.x] = sz;
 }
 

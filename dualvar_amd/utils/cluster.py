@@ -10,8 +10,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops
-from . import knn
-from .variance import _normalise
+from . import features as F
 
 
 def _check_fit_args(feat, k, n_iter, n_init, init):
@@ -29,12 +28,6 @@ def _check_fit_args(feat, k, n_iter, n_init, init):
         raise ValueError('feat (and init) must be device tensors (the kernels read the pointers as they are)')
 
 
-def _ws(nbytes, dev, name):
-    if nbytes < 0:
-        L.check(int(nbytes), name)
-    return torch.empty(max(int(nbytes) // 8, 1), dtype=torch.float64, device=dev)
-
-
 class _Fit:
     """the device arrays one fit reuses over its restarts and iterations"""
 
@@ -42,15 +35,15 @@ class _Fit:
         self.z, self.k = z, k
         self.n, self.D = z.shape
         dev, lib = z.device, L.load()
-        self.row_block, _ = knn.blocks(self.n, k, row_block, None)       # 4096 rows by default, as the sibling walks
-        self.sim = torch.empty(self.row_block, k, dtype=torch.float32, device=dev)
+        row_block, _ = F.blocks(self.n, k, row_block, None)              # 4096 rows by default, as the sibling walks
+        self.walk = F.SimilarityWalk(row_block, k, dev)                  # the bank is the centroids: one chunk of k columns
         self.assign = torch.empty(self.n, dtype=torch.int32, device=dev)
         self.best = torch.empty(self.n, dtype=torch.float32, device=dev)
         self.changed = torch.zeros(1, dtype=torch.int64, device=dev)             # the kernel's uint64
         self.counts = torch.empty(k, dtype=torch.int32, device=dev)
         self.within = torch.empty(k, dtype=torch.float64, device=dev)
-        self.update_ws = _ws(lib.dv_kmeans_update_workspace(self.n, self.D, k), dev, 'dv_kmeans_update_workspace')
-        self.seed_ws = _ws(lib.dv_kmeans_seed_workspace(self.n), dev, 'dv_kmeans_seed_workspace')
+        self.update_ws = F.workspace(lib.dv_kmeans_update_workspace(self.n, self.D, k), dev, 'dv_kmeans_update_workspace')
+        self.seed_ws = F.workspace(lib.dv_kmeans_seed_workspace(self.n), dev, 'dv_kmeans_seed_workspace')
         self.col = torch.empty(self.n, dtype=torch.float32, device=dev)
         self.mind = torch.empty(self.n, dtype=torch.float32, device=dev)
         self.pick = torch.empty(1, dtype=torch.int32, device=dev)
@@ -59,13 +52,10 @@ class _Fit:
     def assign_step(self, cent):
         """the arg-max of every row against cent [k, D], one row block of similarities at a time; the rows whose cluster changed
         add up in self.changed"""
-        lib, s, D = L.load(), ops.stream_ptr(), self.D
+        lib, s, sim = L.load(), ops.stream_ptr(), self.walk.sim
         self.changed.zero_()
-        for r0 in range(0, self.n, self.row_block):
-            nr = min(self.row_block, self.n - r0)
-            L.check(lib.dv_gemm_f32(nr, self.k, D, self.z.data_ptr() + 4 * r0 * D, D, 1, cent.data_ptr(), 1, D, self.sim.data_ptr(),
-                                    self.k, 1.0, 0, s), 'dv_gemm_f32')
-            L.check(lib.dv_kmeans_assign_f32(self.sim.data_ptr(), self.k, nr, self.k, self.assign.data_ptr() + 4 * r0,
+        for r0, nr, _, _, _, _ in self.walk(self.z, cent):
+            L.check(lib.dv_kmeans_assign_f32(sim.data_ptr(), self.k, nr, self.k, self.assign.data_ptr() + 4 * r0,
                                              self.best.data_ptr() + 4 * r0, self.changed.data_ptr(), s), 'dv_kmeans_assign_f32')
 
     def update_step(self, cent_in, cent_out):
@@ -133,7 +123,7 @@ def kmeans_fit(feat, k, n_iter=100, n_init=10, seed=0, centre=True, init=None, r
     k, n_iter, n_init = int(k), int(n_iter), int(n_init)
     _check_fit_args(feat, k, n_iter, n_init, init)
     L.require_device()
-    f = _Fit(_normalise(feat, centre), k, row_block)
+    f = _Fit(F.normalise(feat, centre), k, row_block)
     if init is not None:
         res = f.lloyd(init.float().contiguous(), n_iter)
         res.update(init_index=None, restart=0)
@@ -258,15 +248,8 @@ def cluster_eval(per_feature, video_label, k=0, n_class=None, n_iter=100, n_init
     """per_feature [n_video, num_seq, D] (the per-clip features `classifier.py --retrieval` saves), video_label [n_video] ->
     (fit, metrics): kmeans_fit over the n_video * num_seq clips (row = video * num_seq + clip; k = 0: as many clusters as
     classes, n_class or the largest label + 1) and cluster_metrics of its assignment against the classes and the videos"""
-    if per_feature.dim() != 3:
-        raise ValueError('per_feature must be [n_video, num_seq, D], got %s' % (tuple(per_feature.shape),))
-    n_video, num_seq, D = per_feature.shape
-    label = torch.as_tensor(video_label).reshape(-1).cpu().long()
-    if label.numel() != n_video:
-        raise ValueError('video_label must hold one label per video (%d), got %d' % (n_video, label.numel()))
-    n_class = int(n_class) if n_class else int(label.max()) + 1
+    feat, vid, cls, _, _ = F.clip_rows(per_feature, video_label)
+    n_class = int(n_class) if n_class else int(cls.max()) + 1
     k = int(k) if k else n_class
-    fit = kmeans_fit(per_feature.reshape(n_video * num_seq, D), k, n_iter=n_iter, n_init=n_init, seed=seed)
-    vid = torch.arange(n_video).repeat_interleave(num_seq)
-    cls = label.repeat_interleave(num_seq)
+    fit = kmeans_fit(feat, k, n_iter=n_iter, n_init=n_init, seed=seed)
     return fit, cluster_metrics(fit['assign'], cls, vid=vid, n_class=n_class)

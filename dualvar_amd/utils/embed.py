@@ -10,8 +10,8 @@ import torch
 
 from .. import _lib as L
 from .. import ops
+from . import features as F
 from . import knn
-from .retrieval import _centre_normalise
 
 MIN_GAIN = 0.01
 MOMENTUM = (0.5, 0.8)                # during / after the early exaggeration
@@ -63,13 +63,13 @@ def affinities_from_lists(val, idx, perplexity, row0=0):
 
 def tsne_affinities(feat, perplexity):
     """feat [n, D] on the device -> the sparse conditional affinities p_{j|i} over the k = min(3 * perplexity, n - 1) nearest
-    neighbours of the centred, L2-normalised features (as variance._normalise prepares them) with their reverse lists; the
+    neighbours of the centred, L2-normalised features (features.centre_normalise) with their reverse lists; the
     symmetrised P_ij = (p_{j|i} + p_{i|j}) / 2n is never materialised (dv_tsne_attract_f32 sums both lists)."""
     _check_perplexity(perplexity)
     _check_feat(feat)
     n = feat.shape[0]
     k = min(3 * int(perplexity), n - 1)
-    z = _centre_normalise(feat)
+    z = F.centre_normalise(feat)
     val, idx = knn.topk_neighbours(z, z, k + 1)
     aff = affinities_from_lists(val, idx, perplexity)
     aff['k'] = k
@@ -80,11 +80,7 @@ class _Workspace:
     """the device arrays of one embedding: forces, velocity, gains, the repulsion workspace and the trace"""
 
     def __init__(self, n, dev, n_trace):
-        lib = L.load()
-        nbytes = lib.dv_tsne_repulse_workspace(n, None)
-        if nbytes < 0:
-            L.check(int(nbytes), 'dv_tsne_repulse_workspace')
-        self.ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        self.ws = F.workspace(L.load().dv_tsne_repulse_workspace(n, None), dev, 'dv_tsne_repulse_workspace')
         self.fa = torch.empty(n, 2, dtype=torch.float32, device=dev)
         self.fr = torch.empty(n, 2, dtype=torch.float32, device=dev)
         self.ce_row = torch.empty(n, dtype=torch.float32, device=dev)
@@ -187,17 +183,8 @@ def tsne_eval(per_feature, video_label, perplexity=30, n_iter=1000, seed=0, k=10
     """per_feature [n_video, num_seq, D] (the per-clip features `classifier.py --retrieval` saves), video_label [n_video] ->
     (y [n_video * num_seq, 2] on the host, row = video * num_seq + clip; trace; report; the neighbours per row that attract,
     min(3 * perplexity, n - 1))"""
-    if per_feature.dim() != 3:
-        raise ValueError('per_feature must be [n_video, num_seq, D], got %s' % (tuple(per_feature.shape),))
-    n_video, num_seq, D = per_feature.shape
-    n = n_video * num_seq
-    label = torch.as_tensor(video_label).reshape(-1)
-    if label.numel() != n_video:
-        raise ValueError('video_label must hold one label per video (%d), got %d' % (n_video, label.numel()))
-    feat = per_feature.reshape(n, D)
+    feat, vid, cls, _, _ = F.clip_rows(per_feature, video_label)
     aff = tsne_affinities(feat, perplexity)
     y, trace = tsne_embed(feat, perplexity=perplexity, n_iter=n_iter, seed=seed, affinities=aff)
-    vid = torch.arange(n_video).repeat_interleave(num_seq)
-    cls = label.cpu().long().repeat_interleave(num_seq)
     rep = embedding_report(y, vid, cls, aff['idx'], k=k)
     return y.cpu(), trace, rep, aff['k']

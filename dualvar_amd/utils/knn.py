@@ -8,28 +8,12 @@ import torch
 
 from .. import _lib as L
 from .. import ops
-from .retrieval import _centre_normalise
-
-WORKSPACE_BYTES = 256 << 20          # the largest similarity workspace topk_neighbours allocates by default
-_DEFAULT_ROW_BLOCK = 4096
+from . import features as F
 
 
 def _check_k(k):
     if not 1 <= k <= L.DV_TOPK_MAX_K:
         raise ValueError('k = %d: the selection kernel keeps 1 <= k <= %d (DV_TOPK_MAX_K) neighbours per row' % (k, L.DV_TOPK_MAX_K))
-
-
-def blocks(R, N, row_block=None, chunk=None):
-    """(row_block, chunk) of the similarity workspace for R query rows and N bank rows: what the caller forces, clipped to the
-    problem; the defaults keep row_block * chunk * 4 bytes at or below WORKSPACE_BYTES"""
-    row_block = min(R, _DEFAULT_ROW_BLOCK) if row_block is None else int(row_block)
-    if row_block < 1:
-        raise ValueError('row_block must be positive')
-    row_block = min(row_block, R)
-    chunk = max(1, WORKSPACE_BYTES // 4 // row_block) if chunk is None else int(chunk)
-    if chunk < 1:
-        raise ValueError('chunk must be positive')
-    return row_block, min(chunk, N)
 
 
 def topk_neighbours(query, bank, k, chunk=None, row_block=None):
@@ -43,21 +27,15 @@ def topk_neighbours(query, bank, k, chunk=None, row_block=None):
         raise ValueError('topk_neighbours takes device tensors (the kernels read the pointers as they are)')
     L.require_device()
     q, b = query.float().contiguous(), bank.float().contiguous()
-    R, D = q.shape
-    N = b.shape[0]
-    row_block, chunk = blocks(R, N, row_block, chunk)
+    R = q.shape[0]
+    row_block, chunk = F.blocks(R, b.shape[0], row_block, chunk)
     lib, s = L.load(), ops.stream_ptr()
-    ws = torch.empty(row_block, chunk, dtype=torch.float32, device=q.device)
+    walk = F.SimilarityWalk(row_block, chunk, q.device)
     val = torch.empty(R, k, dtype=torch.float32, device=q.device)
     idx = torch.empty(R, k, dtype=torch.int32, device=q.device)
-    for r0 in range(0, R, row_block):
-        nr = min(row_block, R - r0)
-        for c0 in range(0, N, chunk):
-            nc = min(chunk, N - c0)
-            L.check(lib.dv_gemm_f32(nr, nc, D, q.data_ptr() + 4 * r0 * D, D, 1, b.data_ptr() + 4 * c0 * D, 1, D, ws.data_ptr(), chunk,
-                                    1.0, 0, s), 'dv_gemm_f32')
-            L.check(lib.dv_topk_merge_f32(ws.data_ptr(), chunk, nr, nc, c0, k, val.data_ptr() + 4 * r0 * k, idx.data_ptr() + 4 * r0 * k,
-                                          k, int(c0 == 0), s), 'dv_topk_merge_f32')
+    for r0, nr, c0, nc, _, _ in walk(q, b):
+        L.check(lib.dv_topk_merge_f32(walk.sim.data_ptr(), chunk, nr, nc, c0, k, val.data_ptr() + 4 * r0 * k, idx.data_ptr() + 4 * r0 * k,
+                                      k, int(c0 == 0), s), 'dv_topk_merge_f32')
     return val, idx
 
 
@@ -94,7 +72,7 @@ def knn_eval(test_feature, test_label, train_feature, train_label, n_class, k=20
     of the reference's torch.topk definition (a same-label sample among the first k neighbours).  'k' is the number of
     neighbours that voted, min(k, n_train); 'val' / 'idx' are the [n_test, k'] lists, k' = min(max(k, max(ks)), n_train)."""
     L.require_device()
-    te, tr = _centre_normalise(test_feature), _centre_normalise(train_feature)
+    te, tr = F.centre_normalise(test_feature), F.centre_normalise(train_feature)
     n_train = tr.shape[0]
     kk = min(max([k] + list(ks)), n_train)
     k_vote = min(k, n_train)

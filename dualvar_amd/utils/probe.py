@@ -13,6 +13,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops
+from . import features as F
 
 LAMBDAS = (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)
 
@@ -45,7 +46,9 @@ def _check_z(z):
         raise ValueError('z must be [n, D] clip features with 1 <= D <= %d (DV_RIDGE_MAX_D), got %s' % (L.DV_RIDGE_MAX_D, tuple(z.shape)))
 
 
-def _gram(z, label, n_class, G, B, accumulate, ws):
+def ridge_gram(z, label, n_class, G, B, accumulate, ws):
+    """one dv_ridge_gram_f64 launch: z [n, D] fp32, label [n] int32 (-1: the row is left out), G [D + 1, D + 1], B [D + 1, n_class]
+    float64, all contiguous on the device; ws from dv_ridge_gram_workspace(n, D, n_class)"""
     n, D = z.shape
     L.check(L.load().dv_ridge_gram_f64(z.data_ptr(), D, n, D, label.data_ptr(), n_class, G.data_ptr(), D + 1, B.data_ptr(), n_class,
                                        int(accumulate), ws.data_ptr(), ops.stream_ptr()), 'dv_ridge_gram_f64')
@@ -70,17 +73,14 @@ def ridge_systems(z, clip_label, held_rows, n_class=None):
     z = z.to(dev).float().contiguous()
     label = label.to(device=dev, dtype=torch.int32)
     held = held.to(dev)
-    nbytes = L.load().dv_ridge_gram_workspace(n, D, n_class)
-    if nbytes < 0:
-        L.check(int(nbytes), 'dv_ridge_gram_workspace')
-    ws = torch.empty(int(nbytes) // 8, dtype=torch.float64, device=dev)
+    ws = F.workspace(L.load().dv_ridge_gram_workspace(n, D, n_class), dev, 'dv_ridge_gram_workspace')
     G = torch.empty(D + 1, D + 1, dtype=torch.float64, device=dev)
     B = torch.empty(D + 1, n_class, dtype=torch.float64, device=dev)
     minus = torch.full_like(label, -1)
-    _gram(z, torch.where(held, minus, label).contiguous(), n_class, G, B, 0, ws)
+    ridge_gram(z, torch.where(held, minus, label).contiguous(), n_class, G, B, 0, ws)
     G_full, B_full = G.clone(), B.clone()
     if bool(held.any()):
-        _gram(z, torch.where(held, label, minus).contiguous(), n_class, G_full, B_full, 1, ws)
+        ridge_gram(z, torch.where(held, label, minus).contiguous(), n_class, G_full, B_full, 1, ws)
     return G, B, G_full, B_full
 
 
@@ -127,10 +127,7 @@ def ridge_scores(z, W, video_label=None, num_seq=1):
     w32 = W.to(device=dev, dtype=torch.float32).contiguous()
     Cn, V = w32.shape[1], n // num_seq
     logits = torch.empty(n, Cn, dtype=torch.float32, device=dev)
-    d = L.GemmDesc()
-    d.A, d.B, d.C, d.bias = z.data_ptr(), w32.data_ptr(), logits.data_ptr(), w32.data_ptr() + 4 * D * Cn
-    d.sam, d.sak, d.sbk, d.sbn, d.ldc = D, 1, Cn, 1, Cn
-    d.M, d.N, d.K, d.flags, d.alpha = n, Cn, D, L.DV_BIAS, 1.0
+    d = F.gemm_desc(z.data_ptr(), w32.data_ptr(), logits.data_ptr(), n, Cn, D, Cn, 1, bias=w32.data_ptr() + 4 * D * Cn)
     L.check(lib.dv_gemm_f32_ex(C.byref(d), s), 'dv_gemm_f32_ex')
     video = torch.empty(V, Cn, dtype=torch.float32, device=dev)
     L.check(lib.dv_group_mean_f32(logits.data_ptr(), V, num_seq, Cn, video.data_ptr(), s), 'dv_group_mean_f32')
@@ -150,15 +147,6 @@ def ridge_scores(z, W, video_label=None, num_seq=1):
     return out
 
 
-def _normalise(clips):
-    """[V, S, D] -> [V * S, D] fp32 on the device, every clip feature L2-normalised (eps 1e-12), not centred"""
-    x = clips.reshape(-1, clips.shape[-1]).to('cuda').float().contiguous()
-    y, nrm = torch.empty_like(x), torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    L.check(L.load().dv_l2norm_fwd(x.data_ptr(), x.shape[0], x.shape[1], 1e-12, y.data_ptr(), nrm.data_ptr(), ops.stream_ptr()),
-            'dv_l2norm_fwd')
-    return y
-
-
 def ridge_probe(train_clips, train_label, test_clips, test_label, n_class, lambdas=LAMBDAS, holdout=5):
     """train_clips [V, S, D] with train_label [V], test_clips [Vt, St, D] with test_label [Vt] -> the report of the closed-form
     ridge probe: {'lambda' (the one kept), 'sweep' (per lambda: held-out clip / video top-1 / top-5), 'clip_top1', 'clip_top5',
@@ -168,23 +156,23 @@ def ridge_probe(train_clips, train_label, test_clips, test_label, n_class, lambd
     lambda * n_fit on the D feature rows of the diagonal and scored on the held-out videos; the lambda of largest held-out video
     top-1 is kept, the larger among equals; the refit on all training clips uses lambda * n_train.  If no video can be held
     out the sweep is skipped and the single lambda given, or the middle one of the grid, is used."""
-    if train_clips.dim() != 3 or test_clips.dim() != 3 or train_clips.shape[2] != test_clips.shape[2]:
+    train, _, cls, V, S = F.clip_rows(train_clips, train_label)
+    test, _, _, _, St = F.clip_rows(test_clips, test_label)
+    D = train.shape[1]
+    if test.shape[1] != D:
         raise ValueError('train_clips and test_clips must be [V, S, D] with one D, got %s and %s' % (tuple(train_clips.shape), tuple(test_clips.shape)))
     lam = _check_lambdas(lambdas)
-    V, S, D = train_clips.shape
     n_class = int(n_class)
-    tl = torch.as_tensor(train_label).reshape(-1).cpu().long()
-    if tl.numel() != V or torch.as_tensor(test_label).numel() != test_clips.shape[0]:
-        raise ValueError('one label per video is needed')
+    tl = cls[::S]                        # the videos' labels, int64 on the host
     if int(tl.min()) < 0 or int(tl.max()) >= n_class:
         raise ValueError('train labels must lie in [0, n_class)')
     held_video = holdout_mask(tl, holdout)
     L.require_device()
-    z = _normalise(train_clips)
+    z = F.normalise(train)
     n = V * S
     held_rows = held_video.repeat_interleave(S)
     n_held = int(held_rows.sum())
-    G_fit, B_fit, G_full, B_full = ridge_systems(z, tl.repeat_interleave(S), held_rows, n_class=n_class)
+    G_fit, B_fit, G_full, B_full = ridge_systems(z, cls, held_rows, n_class=n_class)
     sweep = []
     if n_held:
         z_held = z[held_rows.to(z.device)].contiguous()
@@ -201,7 +189,7 @@ def ridge_probe(train_clips, train_label, test_clips, test_label, n_class, lambd
     else:
         chosen = lam[0] if len(lam) == 1 else lam[len(lam) // 2]
     W = ridge_solve(G_full, B_full, chosen * n, D)
-    sc = ridge_scores(_normalise(test_clips), W, test_label, test_clips.shape[1])
+    sc = ridge_scores(F.normalise(test), W, test_label, St)
     return {'lambda': chosen, 'sweep': sweep, 'clip_top1': sc['clip_top1'], 'clip_top5': sc['clip_top5'],
             'video_top1': sc['video_top1'], 'video_top5': sc['video_top5'], 'n_train': n, 'n_fit': n - n_held,
             'n_held_videos': int(held_video.sum()), 'n_class': n_class, 'D': D, 'W': W}

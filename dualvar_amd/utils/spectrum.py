@@ -15,7 +15,8 @@ import torch
 
 from .. import _lib as L
 from .. import ops
-from .probe import _normalise
+from . import features as F
+from .probe import ridge_gram
 
 MAX_SWEEPS = L.DV_SPECTRUM_MAX_SWEEPS
 EPS = 2.0 ** -52
@@ -32,15 +33,11 @@ def covariance(z):
     dev = z.device if z.is_cuda else torch.device('cuda')
     z = z.to(dev).float().contiguous()
     n, D = z.shape
-    nbytes = lib.dv_ridge_gram_workspace(n, D, 1)
-    if nbytes < 0:
-        L.check(int(nbytes), 'dv_ridge_gram_workspace')
-    ws = torch.empty(int(nbytes) // 8, dtype=torch.float64, device=dev)
+    ws = F.workspace(lib.dv_ridge_gram_workspace(n, D, 1), dev, 'dv_ridge_gram_workspace')
     label = torch.zeros(n, dtype=torch.int32, device=dev)
     G = torch.empty(D + 1, D + 1, dtype=torch.float64, device=dev)
     B = torch.empty(D + 1, 1, dtype=torch.float64, device=dev)
-    L.check(lib.dv_ridge_gram_f64(z.data_ptr(), D, n, D, label.data_ptr(), 1, G.data_ptr(), D + 1, B.data_ptr(), 1, 0, ws.data_ptr(), s),
-            'dv_ridge_gram_f64')
+    ridge_gram(z, label, 1, G, B, 0, ws)
     cov = torch.empty(D, D, dtype=torch.float64, device=dev)
     mean = torch.empty(D, dtype=torch.float64, device=dev)
     L.check(lib.dv_spectrum_cov_f64(G.data_ptr(), D + 1, D, cov.data_ptr(), D, mean.data_ptr(), s), 'dv_spectrum_cov_f64')
@@ -176,37 +173,29 @@ def pca_project(z, mean, comps, lam, k, whiten=False, eps=1e-12):
     m32 = mean.to(device=dev, dtype=torch.float32).reshape(1, D).contiguous()
     bias = torch.empty(1, k, dtype=torch.float32, device=dev)
     y = torch.empty(n, k, dtype=torch.float32, device=dev)
-    d = L.GemmDesc()
-    d.A, d.B, d.C, d.bias = m32.data_ptr(), c32.data_ptr(), bias.data_ptr(), None
-    d.sam, d.sak, d.sbk, d.sbn, d.ldc = D, 1, 1, D, k
-    d.M, d.N, d.K, d.flags, d.alpha = 1, k, D, 0, -1.0
-    L.check(lib.dv_gemm_f32_ex(C.byref(d), s), 'dv_gemm_f32_ex')
-    d.A, d.C, d.bias = z.data_ptr(), y.data_ptr(), bias.data_ptr()
-    d.M, d.flags, d.alpha = n, L.DV_BIAS, 1.0
-    L.check(lib.dv_gemm_f32_ex(C.byref(d), s), 'dv_gemm_f32_ex')
+    for d in (F.gemm_desc(m32.data_ptr(), c32.data_ptr(), bias.data_ptr(), 1, k, D, 1, D, alpha=-1.0),
+              F.gemm_desc(z.data_ptr(), c32.data_ptr(), y.data_ptr(), n, k, D, 1, D, bias=bias.data_ptr())):
+        L.check(lib.dv_gemm_f32_ex(C.byref(d), s), 'dv_gemm_f32_ex')
     return y
 
 
 def spectrum_eval(clips, video_label=None, ks=(32, 64, 128)):
-    """clips [V, S, D] (a video's clips adjacent), normalised as the ridge probe does (probe._normalise) -> {'metrics'
+    """clips [V, S, D] (a video's clips adjacent), normalised as the ridge probe does (features.normalise, not centred) -> {'metrics'
     (spectrum_metrics), 'info' (eigh_jacobi), 'video_share' [k_max], 'ks' (clamped to D), 'mean' [D], 'components' [D, D],
     'eigenvalues' [D]} (the last three float64 on the device).
     video_share[j] is the share of component j's variance that lies between the video means: the clips are projected on the top
     k_max = max(ks) components, dv_group_mean_f32 averages a video's S clips to M [V, k_max], and the share is
     S sum_v M[v, j]^2 / (n lam_j) with n = V S; None where lam_j is not above the numerical-rank threshold D eps lam_1.
     video_label is not needed (a video is S adjacent rows); it is accepted so that callers can pass what they hold."""
-    if clips.dim() != 3:
-        raise ValueError('clips must be [V, S, D], got %s' % (tuple(clips.shape),))
-    V, S, D = clips.shape
+    feat, _, _, V, S = F.clip_rows(clips, video_label)
+    D = feat.shape[1]
     if not 1 <= D <= L.DV_SPECTRUM_MAX_D:
         raise ValueError('D = %d: the spectrum kernels keep 1 <= D <= %d (DV_SPECTRUM_MAX_D)' % (D, L.DV_SPECTRUM_MAX_D))
-    if video_label is not None and torch.as_tensor(video_label).numel() != V:
-        raise ValueError('video_label must hold one label per video (%d), got %d' % (V, torch.as_tensor(video_label).numel()))
     ks = sorted({min(int(k), D) for k in ks})
     if not ks or ks[0] < 1:
         raise ValueError('every k must be at least 1')
     L.require_device()
-    z = _normalise(clips)
+    z = F.normalise(feat)
     n = V * S
     mean, cov = covariance(z)
     lam, comps, info = eigh_jacobi(cov)
@@ -228,8 +217,7 @@ def pca_retrieval(train_video_feat, train_label, test_video_feat, test_label, me
     existing nn_retrieval (which centres and normalises again and keeps k a multiple of 8)."""
     from .retrieval import nn_retrieval
     out = {}
-    tr = _normalise(train_video_feat.reshape(train_video_feat.shape[0], 1, -1))
-    te = _normalise(test_video_feat.reshape(test_video_feat.shape[0], 1, -1))
+    tr, te = F.normalise(train_video_feat), F.normalise(test_video_feat)
     for k in ks:
         k = int(k)
         if k % 8:

@@ -11,8 +11,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops
-from . import knn
-from .retrieval import _centre_normalise
+from . import features as F
 
 CATEGORIES = ('same_video', 'same_class', 'diff_class')
 
@@ -24,16 +23,6 @@ def _check_bins_t(bins, t):
         raise ValueError('t must be finite and not negative')
 
 
-def _normalise(x, centre):
-    if centre:
-        return _centre_normalise(x)
-    x = x.float().contiguous()
-    y, nrm = torch.empty_like(x), torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    L.check(L.load().dv_l2norm_fwd(x.data_ptr(), x.shape[0], x.shape[1], 1e-12, y.data_ptr(), nrm.data_ptr(), ops.stream_ptr()),
-            'dv_l2norm_fwd')
-    return y
-
-
 def _ids(v, n, dev, what):
     v = torch.as_tensor(v)
     if v.dim() != 1 or v.numel() != n:
@@ -42,29 +31,23 @@ def _ids(v, n, dev, what):
 
 
 class _State:
-    """the state of dv_pairstat_accum_f32 on the device and the similarity workspace the walk reuses"""
+    """the state of dv_pairstat_accum_f32 on the device"""
 
     def __init__(self, dev, bins, t, row_block, chunk):
-        self.bins, self.t, self.row_block, self.chunk = bins, float(t), row_block, chunk
+        self.bins, self.t = bins, float(t)
         self.sums = torch.empty(3, 4, dtype=torch.float64, device=dev)
         self.ext = torch.empty(3, 2, dtype=torch.float32, device=dev)
         self.hist = torch.empty(3, bins + 1, dtype=torch.int64, device=dev)      # the kernel's uint64; counts stay below 2^63
-        self.sim = torch.empty(row_block, chunk, dtype=torch.float32, device=dev)
-        nbytes = L.load().dv_pairstat_workspace(row_block, chunk)                # the grid grows with the block: the largest one
-        if nbytes < 0:
-            L.check(int(nbytes), 'dv_pairstat_workspace')
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        # the grid grows with the block: the largest one
+        self.ws = F.workspace(L.load().dv_pairstat_workspace(row_block, chunk), dev, 'dv_pairstat_workspace')
         self.first = 1
 
-    def block(self, q, b, q_ids, b_ids, r0, nr, c0, nc, diag, mult):
-        """similarity of q[r0:r0+nr] . b[c0:c0+nc]^T into the workspace, then its pairs into the state"""
-        lib, s, D = L.load(), ops.stream_ptr(), q.shape[1]
-        L.check(lib.dv_gemm_f32(nr, nc, D, q.data_ptr() + 4 * r0 * D, D, 1, b.data_ptr() + 4 * c0 * D, 1, D, self.sim.data_ptr(),
-                                self.chunk, 1.0, 0, s), 'dv_gemm_f32')
-        L.check(lib.dv_pairstat_accum_f32(self.sim.data_ptr(), self.chunk, nr, nc, q_ids[0].data_ptr() + 4 * r0,
-                                          q_ids[1].data_ptr() + 4 * r0, b_ids[0].data_ptr() + 4 * c0, b_ids[1].data_ptr() + 4 * c0,
-                                          diag, mult, self.t, self.bins, self.sums.data_ptr(), self.ext.data_ptr(),
-                                          self.hist.data_ptr(), self.bins + 1, self.ws.data_ptr(), self.first, s),
+    def accumulate(self, sim, ld, q_ids, b_ids, r0, nr, c0, nc, diag, mult):
+        """the pairs of the [nr, nc] similarity block `sim` (pitch ld; rows from r0, columns from c0) into the state"""
+        L.check(L.load().dv_pairstat_accum_f32(sim.data_ptr(), ld, nr, nc, q_ids[0].data_ptr() + 4 * r0, q_ids[1].data_ptr() + 4 * r0,
+                                               b_ids[0].data_ptr() + 4 * c0, b_ids[1].data_ptr() + 4 * c0, diag, mult, self.t,
+                                               self.bins, self.sums.data_ptr(), self.ext.data_ptr(), self.hist.data_ptr(),
+                                               self.bins + 1, self.ws.data_ptr(), self.first, ops.stream_ptr()),
                 'dv_pairstat_accum_f32')
         self.first = 0
 
@@ -84,27 +67,20 @@ def pair_statistics(feat, vid, cls, bins=64, t=2.0, centre=True, symmetric=True,
     hist [3, bins + 1] i64) on the host: the state of dv_pairstat_accum_f32 over the n (n - 1) ordered pairs i != j of the
     normalised features (centred first as retrieval does when `centre`), categories 0 / 1 / 2 as in CATEGORIES.
 
-    The walk is that of knn.topk_neighbours: row blocks of `row_block`, column chunks of `chunk`, one reused workspace within
-    knn.WORKSPACE_BYTES.  symmetric=True visits, per row block [r0, r0 + nr), only the columns from r0 on and cuts the chunks at
-    r0 + nr, so the block grid is aligned to the diagonal: the square [r0, r0 + nr)^2 holds both orders of its pairs and is
-    counted once (mult = 1, self pairs on its diagonal skipped), every block to its right lies strictly above the diagonal and is
-    counted twice (mult = 2).  No block straddles the diagonal raggedly, so no mirror block is ever needed."""
+    The walk is features.SimilarityWalk, as knn.topk_neighbours: row blocks of `row_block`, column chunks of `chunk`, one reused
+    workspace within features.WORKSPACE_BYTES.  symmetric=True takes the spans of features.block_spans aligned to the diagonal:
+    a square on it counts once (mult = 1, the self pairs on its diagonal skipped), a block to its right twice (mult = 2)."""
     bins = int(bins)
     _check_bins_t(bins, t)
     _prepare(feat, 'feat')
     L.require_device()
     n = feat.shape[0]
     ids = (_ids(vid, n, feat.device, 'vid'), _ids(cls, n, feat.device, 'cls'))
-    z = _normalise(feat, centre)
-    row_block, chunk = knn.blocks(n, n, row_block, chunk)
-    st = _State(z.device, bins, t, row_block, chunk)
-    for r0 in range(0, n, row_block):
-        nr = min(row_block, n - r0)
-        # (first column, end, mult) of the column ranges this row block visits
-        spans = [(r0, r0 + nr, 1), (r0 + nr, n, 2)] if symmetric else [(0, n, 1)]
-        for lo, hi, mult in spans:
-            for c0 in range(lo, hi, chunk):
-                st.block(z, z, ids, ids, r0, nr, c0, min(chunk, hi - c0), r0 - c0, mult)
+    z = F.normalise(feat, centre)
+    row_block, chunk = F.blocks(n, n, row_block, chunk)
+    st, walk = _State(z.device, bins, t, row_block, chunk), F.SimilarityWalk(row_block, chunk, z.device)
+    for span in walk(z, z, symmetric):
+        st.accumulate(walk.sim, chunk, ids, ids, *span)
     return st.result()
 
 
@@ -121,14 +97,12 @@ def pair_statistics_cross(q, q_vid, q_cls, bank, bank_vid, bank_cls, bins=64, t=
     R, N = q.shape[0], bank.shape[0]
     q_ids = (_ids(q_vid, R, q.device, 'q_vid'), _ids(q_cls, R, q.device, 'q_cls'))
     b_ids = (_ids(bank_vid, N, q.device, 'bank_vid'), _ids(bank_cls, N, q.device, 'bank_cls'))
-    zq, zb = _normalise(q, centre), _normalise(bank, centre)
-    row_block, chunk = knn.blocks(R, N, row_block, chunk)
-    st = _State(zq.device, bins, t, row_block, chunk)
+    zq, zb = F.normalise(q, centre), F.normalise(bank, centre)
+    row_block, chunk = F.blocks(R, N, row_block, chunk)
+    st, walk = _State(zq.device, bins, t, row_block, chunk), F.SimilarityWalk(row_block, chunk, zq.device)
     no_self = -(1 << 40)                 # no (r, j) has j == r + diag
-    for r0 in range(0, R, row_block):
-        nr = min(row_block, R - r0)
-        for c0 in range(0, N, chunk):
-            st.block(zq, zb, q_ids, b_ids, r0, nr, c0, min(chunk, N - c0), no_self, 1)
+    for r0, nr, c0, nc, _, mult in walk(zq, zb):
+        st.accumulate(walk.sim, chunk, q_ids, b_ids, r0, nr, c0, nc, no_self, mult)
     return st.result()
 
 
@@ -174,13 +148,6 @@ def report_from_state(sums, ext, hist, bins, t):
 def variance_eval(per_feature, video_label, bins=64, t=2.0):
     """per_feature [n_video, num_seq, D] (the per-clip features `classifier.py --retrieval` saves), video_label [n_video] ->
     the report of report_from_state over all ordered pairs of the n_video * num_seq clips: vid = the video's row, cls = its label"""
-    if per_feature.dim() != 3:
-        raise ValueError('per_feature must be [n_video, num_seq, D], got %s' % (tuple(per_feature.shape),))
-    n_video, num_seq, D = per_feature.shape
-    label = torch.as_tensor(video_label).reshape(-1)
-    if label.numel() != n_video:
-        raise ValueError('video_label must hold one label per video (%d), got %d' % (n_video, label.numel()))
-    vid = torch.arange(n_video, dtype=torch.int32).repeat_interleave(num_seq)
-    cls = label.to(torch.int32).cpu().repeat_interleave(num_seq)
-    state = pair_statistics(per_feature.reshape(n_video * num_seq, D), vid, cls, bins=bins, t=t)
+    feat, vid, cls, _, _ = F.clip_rows(per_feature, video_label)
+    state = pair_statistics(feat, vid, cls, bins=bins, t=t)
     return report_from_state(*state, bins, t)

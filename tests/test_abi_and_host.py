@@ -10,32 +10,30 @@ import numpy as np
 import pytest
 import torch
 
+from tests.util import check_header_binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_functions():
-    src = open(os.path.join(ROOT, 'include', 'dualvar_hip.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    out = {}
-    for m in re.finditer(r'\b(?:int|int64_t)\s+(dv_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
-        args = [a.strip() for a in m.group(2).split(',') if a.strip() and a.strip() != 'void']
-        out[m.group(1)] = args
-    return out
 
 
 def test_library_exports_every_declared_symbol():
     from dualvar_amd import _lib
     lib = _lib.load()
-    decl = _header_functions()
-    assert len(decl) >= 35
-    for name, args in decl.items():
-        assert hasattr(lib, name), f'{name} declared in dualvar_hip.h but not exported'
-        assert name in _lib.SIGNATURES, f'{name} missing from the ctypes table'
-        assert len(_lib.SIGNATURES[name]) == len(args), (name, len(_lib.SIGNATURES[name]), args)
-    assert set(_lib.SIGNATURES) == set(decl)
-    hdr = open(os.path.join(ROOT, 'include', 'dualvar_hip.h')).read()
+    hdr, decl = check_header_binding('dualvar_hip.h')
+    assert len(decl) >= 35 and _lib.HEADERS['dualvar_hip.h'] is _lib.SIGNATURES
     declared = int(re.search(r'#define\s+DV_ABI_VERSION\s+(\d+)', hdr).group(1))
     assert lib.dv_abi_version() == declared == _lib.ABI_VERSION >= 2
+
+
+def test_binding_tables_are_disjoint_and_cover_every_header():
+    """_lib.HEADERS lists exactly the headers of include/, and no entry is declared in two of its tables (each header's own
+    test file checks its table against the header with tests/util.py check_header_binding)"""
+    from dualvar_amd import _lib
+    assert set(_lib.HEADERS) == {f for f in os.listdir(os.path.join(ROOT, 'include')) if f.endswith('.h')}
+    tables = list(_lib.HEADERS.items())
+    for i, (ha, a) in enumerate(tables):
+        for hb, b in tables[i + 1:]:
+            assert not set(a) & set(b), (ha, hb, sorted(set(a) & set(b)))
+    assert sum(len(t) for _, t in tables) == len({n for _, t in tables for n in t})
 
 
 def test_no_kernel_of_the_library_spills():

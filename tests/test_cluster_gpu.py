@@ -300,10 +300,10 @@ def fit_data(gpu):
     """the six groups of cluster_reference.fit_fixture, prepared on the device as kmeans_fit prepares them, and the float64
     reference's run from one point of each group on exactly those rows (computed once, left unchanged)"""
     if not CACHE:
-        from dualvar_amd.utils.retrieval import _centre_normalise
+        from dualvar_amd.utils.features import centre_normalise
         x, cls = R.fit_fixture()
         feat = torch.from_numpy(x).to(gpu)
-        z = _centre_normalise(feat)
+        z = centre_normalise(feat)
         z64 = z.double().cpu().numpy()
         assign, cent, trace = R.lloyd_ref(z64, z64[::50])
         assert (assign == cls).all()

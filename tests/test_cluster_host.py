@@ -21,6 +21,7 @@ import torch
 
 from tests import abi_coverage as A
 from tests import cluster_reference as R
+from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EALIGN = -1, -2
@@ -38,34 +39,15 @@ CLUSTER_COVERAGE = {
 }
 
 
-def _header_functions():
-    hdr = open(os.path.join(ROOT, 'include', 'dualvar_cluster.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    out = {}
-    for m in re.finditer(r'\b(?:int|int64_t)\s+(dv_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
-        out[m.group(1)] = (m.group(0).split()[0], [a.strip() for a in m.group(2).split(',') if a.strip() and a.strip() != 'void'])
-    return hdr, out
-
-
 def lib():
     from dualvar_amd import _lib
     return _lib.load()
 
 
 def test_cluster_header_table_and_library_agree():
-    import ctypes
     from dualvar_amd import _lib, build
-    hdr, decl = _header_functions()
+    hdr, decl = check_header_binding('dualvar_cluster.h')
     assert set(decl) == set(_lib.CLUSTER_SIGNATURES) == set(CLUSTER_COVERAGE) and len(decl) == 6
-    others = set(_lib.SIGNATURES) | set(_lib.SELECT_SIGNATURES) | set(_lib.PAIRSTAT_SIGNATURES) | set(_lib.TSNE_SIGNATURES)
-    assert not set(_lib.CLUSTER_SIGNATURES) & others
-    handle = lib()
-    for name, (ret, args) in decl.items():
-        assert len(_lib.CLUSTER_SIGNATURES[name]) == len(args), (name, args)
-        fn = getattr(handle, name)
-        assert fn.argtypes == _lib.CLUSTER_SIGNATURES[name]
-        assert fn.restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
-        assert (name in _lib.RETURNS_INT64) == (ret == 'int64_t')
     assert 'cluster.hip' in build.SOURCES
     for macro, want in (('DV_KMEANS_MAX_K', R.MAX_K), ('DV_KMEANS_PART', R.PART), ('DV_KMEANS_SORT_ROWS', R.SORT_ROWS),
                         ('DV_KMEANS_SEED_BLOCK', R.SEED_BLOCK)):

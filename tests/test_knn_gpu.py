@@ -342,7 +342,7 @@ def test_vote_gaussian_bounds(gpu):
 def test_topk_neighbours_grid_exact(gpu, R, N, k):
     """features are multiples of 1/4 in [-2, 2], D = 128: every dot product is a multiple of 1/16 below 512, exact in fp32 in any
     order, so every chunking equals float64 bit for bit, ties included"""
-    from dualvar_amd.utils import knn
+    from dualvar_amd.utils import features, knn
     D = 128
     q64, b64 = grid_rows(R + N, R, D).double(), grid_rows(R * N + 1, N, D).double()
     assert float((q64.abs() @ b64.abs().t()).max()) < 512
@@ -366,19 +366,19 @@ def test_topk_neighbours_grid_exact(gpu, R, N, k):
         torch.cuda.synchronize()
         grown = torch.cuda.max_memory_allocated() - before
         outputs = 2 * R * k * 4
-        assert grown < R * N * 4 and grown <= knn.WORKSPACE_BYTES + outputs, grown     # here: a [3, 64] workspace and the lists
+        assert grown < R * N * 4 and grown <= features.WORKSPACE_BYTES + outputs, grown     # here: a [3, 64] workspace and the lists
         assert torch.equal(idx, ref_i.to(gpu))
 
 
 # ------------------------------------------------------------------- 7. topk_neighbours end to end, Gaussian, interval check
 def test_topk_neighbours_gaussian_interval(gpu):
-    from dualvar_amd.utils import knn
+    from dualvar_amd.utils import features, knn
     R, N, D, k = 130, 5000, 512, 200
     gen = torch.Generator().manual_seed(7)
     q, b = unit_gauss(gen, R, D).to(gpu), unit_gauss(gen, N, D).to(gpu)
     s64 = q.double() @ b.double().t()
     bound = gemm_bound(q.double(), b.double(), 1.0, gemm_chain(R, N, D))     # the defaults form one [R, N] product here
-    assert knn.blocks(R, N) == (R, N)
+    assert features.blocks(R, N) == (R, N)
     val, idx = knn.topk_neighbours(q, b, k)
     li = idx.long()
     assert bool((idx >= 0).all()) and bool((idx < N).all())
@@ -398,12 +398,12 @@ def test_topk_neighbours_gaussian_interval(gpu):
 # ------------------------------------------------------------------------- 8. knn_eval against the tested retrieval path
 def knn_eval_case(gpu):
     if 'eval' not in CACHE:
-        from dualvar_amd.utils.retrieval import _centre_normalise
+        from dualvar_amd.utils.features import centre_normalise
         n_test, n_train, D, C = 130, 1000, 512, 10
         gen = torch.Generator().manual_seed(2024)
         te, tr = torch.randn((n_test, D), generator=gen).to(gpu), torch.randn((n_train, D), generator=gen).to(gpu)
         tel, trl = torch.randint(0, C, (n_test,), generator=gen), torch.randint(0, C, (n_train,), generator=gen)
-        CACHE['eval'] = (te, tel, tr, trl, C, _centre_normalise(te).double(), _centre_normalise(tr).double())
+        CACHE['eval'] = (te, tel, tr, trl, C, centre_normalise(te).double(), centre_normalise(tr).double())
     return CACHE['eval']
 
 
@@ -488,8 +488,8 @@ def test_knn_eval_against_retrieval_and_float64(gpu):
     with pytest.raises(ValueError, match='DV_TOPK_MAX_K'):
         knn.knn_eval(te, tel, tr, trl, C, k=1500)
     n_small = 150
-    from dualvar_amd.utils.retrieval import _centre_normalise
-    trn_s = _centre_normalise(tr[:n_small]).double()
+    from dualvar_amd.utils.features import centre_normalise
+    trn_s = centre_normalise(tr[:n_small]).double()
     ref_s = eval_ref64(ten, trn_s, tel, trl[:n_small], C, 1500, 0.07, ks, gpu)
     res_s = knn.knn_eval(te, tel, tr[:n_small], trl[:n_small], C, k=1500, T=0.07, ks=ks)
     acc_s, _ = nn_retrieval(te, tel, tr[:n_small], trl[:n_small], ks=ks)

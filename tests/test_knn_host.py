@@ -11,6 +11,7 @@ import sys
 import pytest
 
 from tests import abi_coverage as A
+from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
@@ -38,29 +39,13 @@ SELECT_COVERAGE = {
 }
 
 
-def _select_header_functions():
-    src = open(os.path.join(ROOT, 'include', 'dualvar_select.h')).read()
-    hdr = src
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    out = {}
-    for m in re.finditer(r'\b(?:int|int64_t)\s+(dv_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
-        out[m.group(1)] = [a.strip() for a in m.group(2).split(',') if a.strip() and a.strip() != 'void']
-    return hdr, out
-
-
 def test_select_header_table_and_library_agree():
     """include/dualvar_select.h, its ctypes table _lib.SELECT_SIGNATURES and the library's exports name the same entries with the
-    same argument counts (what test_library_exports_every_declared_symbol does for dualvar_hip.h / SIGNATURES); the two tables
-    are disjoint, and every entry here is called by the float64 tests of tests/test_knn_gpu.py"""
+    same argument counts and types (tests/util.py check_header_binding, as for every header; tests/test_abi_and_host.py keeps
+    the tables disjoint), and every entry here is called by the float64 tests of tests/test_knn_gpu.py"""
     from dualvar_amd import _lib, build
-    hdr, decl = _select_header_functions()
+    hdr, decl = check_header_binding('dualvar_select.h')
     assert set(decl) == set(_lib.SELECT_SIGNATURES) == set(SELECT_COVERAGE)
-    assert not set(_lib.SELECT_SIGNATURES) & set(_lib.SIGNATURES)
-    lib = _lib.load()
-    for name, args in decl.items():
-        assert len(_lib.SELECT_SIGNATURES[name]) == len(args), (name, args)
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.SELECT_SIGNATURES[name] and fn.restype is not None
     assert int(re.search(r'#define\s+DV_TOPK_MAX_K\s+(\d+)', hdr).group(1)) == _lib.DV_TOPK_MAX_K == 256
     assert 'select.hip' in build.SOURCES
     for name, (fname, kind) in SELECT_COVERAGE.items():
@@ -139,17 +124,3 @@ def test_topk_neighbours_refuses_a_large_k_before_the_device(monkeypatch):
         knn.topk_neighbours(q, b, 5)
     with pytest.raises(ValueError, match='device tensors'):
         knn.knn_classify(torch.zeros(2, 5), torch.zeros(2, 5, dtype=torch.int32), torch.zeros(5, dtype=torch.int32), 3)
-    assert knn.WORKSPACE_BYTES == 256 << 20
-
-
-def test_default_blocks_keep_the_workspace_bounded():
-    from dualvar_amd.utils import knn
-    for R, N in ((3, 30), (3783, 9537), (19900, 240000), (1, 10 ** 8), (10 ** 6, 7)):       # UCF101, Kinetics-400, extremes
-        rb, ch = knn.blocks(R, N)
-        assert 1 <= rb <= R and 1 <= ch <= N and rb * ch * 4 <= knn.WORKSPACE_BYTES, (R, N, rb, ch)
-        assert rb * ch * 4 < R * N * 4 or R * N * 4 <= knn.WORKSPACE_BYTES                 # never the full matrix beyond the bound
-    assert knn.blocks(3783, 9537) == (3783, 9537)                                          # UCF101: one product, 144 MB
-    assert knn.blocks(130, 1000, row_block=64, chunk=257) == (64, 257) and knn.blocks(5, 300, 1000, 1000) == (5, 300)
-    for bad in ((0, None), (None, 0), (-1, 5)):
-        with pytest.raises(ValueError):
-            knn.blocks(10, 10, *bad)

@@ -226,8 +226,9 @@ def fixture():
 
 def gpu_rows(clips):
     """the rows as the library normalises them, in float64: both sides then solve the same system"""
-    from dualvar_amd.utils import probe as PR
-    return PR._normalise(torch.as_tensor(clips)).double().cpu().numpy()
+    from dualvar_amd.utils import features as F
+    clips = torch.as_tensor(clips)
+    return F.normalise(clips.reshape(-1, clips.shape[-1])).double().cpu().numpy()
 
 
 @pytest.mark.parametrize('n_train', [40, 60])

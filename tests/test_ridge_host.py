@@ -20,6 +20,7 @@ import torch
 
 from tests import abi_coverage as A
 from tests import ridge_reference as R
+from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EALIGN = -1, -2
@@ -34,39 +35,15 @@ RIDGE_COVERAGE = {
 }
 
 
-def _header_functions():
-    hdr = open(os.path.join(ROOT, 'include', 'dualvar_ridge.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    out = {}
-    for m in re.finditer(r'\b(?:int|int64_t)\s+(dv_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
-        out[m.group(1)] = (m.group(0).split()[0], [a.strip() for a in m.group(2).split(',') if a.strip() and a.strip() != 'void'])
-    return hdr, out
-
-
 def lib():
     from dualvar_amd import _lib
     return _lib.load()
 
 
 def test_ridge_header_table_and_library_agree():
-    import ctypes
     from dualvar_amd import _lib, build
-    hdr, decl = _header_functions()
+    hdr, decl = check_header_binding('dualvar_ridge.h')
     assert set(decl) == set(_lib.RIDGE_SIGNATURES) == set(RIDGE_COVERAGE) and len(decl) == 3
-    others = (set(_lib.SIGNATURES) | set(_lib.SELECT_SIGNATURES) | set(_lib.PAIRSTAT_SIGNATURES) | set(_lib.TSNE_SIGNATURES) |
-              set(_lib.CLUSTER_SIGNATURES))
-    assert not set(_lib.RIDGE_SIGNATURES) & others
-    handle = lib()
-    for name, (ret, args) in decl.items():
-        assert len(_lib.RIDGE_SIGNATURES[name]) == len(args), (name, args)
-        for typ, arg in zip(_lib.RIDGE_SIGNATURES[name], args):
-            want = (ctypes.c_void_p if '*' in arg else ctypes.c_int64 if arg.startswith('int64_t') else
-                    ctypes.c_double if arg.startswith('double') else ctypes.c_int32)
-            assert typ is want, (name, arg)
-        fn = getattr(handle, name)
-        assert fn.argtypes == _lib.RIDGE_SIGNATURES[name]
-        assert fn.restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
-        assert (name in _lib.RETURNS_INT64) == (ret == 'int64_t')
     assert 'ridge.hip' in build.SOURCES
     for macro, want in (('DV_RIDGE_MAX_D', R.MAX_D), ('DV_RIDGE_MAX_C', R.MAX_C), ('DV_RIDGE_SLAB', R.SLAB),
                         ('DV_RIDGE_MAX_SLABS', R.MAX_SLABS), ('DV_RIDGE_TILE', R.TILE)):

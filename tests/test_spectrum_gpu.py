@@ -233,11 +233,11 @@ def test_rounds_clear_stat_only_from_round_zero(gpu):
 @pytest.fixture(scope='module')
 def planted(gpu):
     """the fixture, its rows as the library normalises them (both sides then decompose the same numbers), and spectrum_eval"""
-    from dualvar_amd.utils import probe as PR
+    from dualvar_amd.utils import features as F
     from dualvar_amd.utils import spectrum as SP
     clips, label = R.spectrum_fixture()
     clips = torch.from_numpy(clips)
-    z = PR._normalise(clips).double().cpu().numpy()
+    z = F.normalise(clips.reshape(-1, clips.shape[-1])).double().cpu().numpy()
     rep = SP.spectrum_eval(clips.to(gpu), torch.from_numpy(label), ks=(4, 8))
     return clips, label, z, rep
 

@@ -16,6 +16,7 @@ import torch
 
 from tests import abi_coverage as A
 from tests import tsne_reference as R
+from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EALIGN = -1, -2
@@ -33,28 +34,10 @@ TSNE_COVERAGE = {
 }
 
 
-def _header_functions():
-    hdr = open(os.path.join(ROOT, 'include', 'dualvar_tsne.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    out = {}
-    for m in re.finditer(r'\b(?:int|int64_t)\s+(dv_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
-        out[m.group(1)] = (m.group(0).split()[0], [a.strip() for a in m.group(2).split(',') if a.strip() and a.strip() != 'void'])
-    return hdr, out
-
-
 def test_tsne_header_table_and_library_agree():
-    import ctypes
     from dualvar_amd import _lib, build
-    hdr, decl = _header_functions()
+    hdr, decl = check_header_binding('dualvar_tsne.h')
     assert set(decl) == set(_lib.TSNE_SIGNATURES) == set(TSNE_COVERAGE) and len(decl) == 5
-    assert not set(_lib.TSNE_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.SELECT_SIGNATURES) | set(_lib.PAIRSTAT_SIGNATURES))
-    lib = _lib.load()
-    for name, (ret, args) in decl.items():
-        assert len(_lib.TSNE_SIGNATURES[name]) == len(args), (name, args)
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.TSNE_SIGNATURES[name]
-        assert fn.restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
-        assert (name in _lib.RETURNS_INT64) == (ret == 'int64_t')
     assert 'tsne.hip' in build.SOURCES
     for macro, want in (('DV_TSNE_BETA_START', R.BETA_START), ('DV_TSNE_MAX_STEPS', R.MAX_STEPS), ('DV_TSNE_ENTROPY_TOL', R.ENTROPY_TOL)):
         assert float(re.search(r'#define\s+%s\s+([0-9.e+-]+)' % macro, hdr).group(1)) == want, macro

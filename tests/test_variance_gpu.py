@@ -435,11 +435,12 @@ def check_against_float64(state, ref, t, bins, what):
 def test_pair_statistics_against_float64(gpu, centre):
     """row_block = 48, chunk = 40 on n = 130: three row blocks (the last ragged, 34 rows), every diagonal square cut into two
     column chunks, blocks to its right of 40 columns and a ragged last one"""
+    from dualvar_amd.utils import features as F
     from dualvar_amd.utils import variance as V
     feat, label, vid, cls = clip_case(gpu)
     x = feat.reshape(130, 64)
     t, bins = 2.0, 64
-    z = V._normalise(x, centre)
+    z = F.normalise(x, centre)
     z64 = x.double() - x.double().mean(0) if centre else x.double()
     z64 = z64 / z64.norm(dim=1, keepdim=True)
     assert float((z.double() - z64).abs().max()) < 1e-5                     # the library's rows ARE the normalised features
@@ -458,6 +459,7 @@ def test_pair_statistics_against_float64(gpu, centre):
 
 
 def test_pair_statistics_cross(gpu):
+    from dualvar_amd.utils import features as F
     from dualvar_amd.utils import variance as V
     feat, label, vid, cls = clip_case(gpu)
     bank = feat.reshape(130, 64)
@@ -466,7 +468,7 @@ def test_pair_statistics_cross(gpu):
     q_vid = torch.tensor([0, 1, 2] * 10, dtype=torch.int32)                # three of the bank's videos: all categories occur
     q_cls = (q_vid % 4).int()
     t, bins = 2.0, 64
-    zq, zb = V._normalise(q, True).double().cpu(), V._normalise(bank, True).double().cpu()
+    zq, zb = F.normalise(q, True).double().cpu(), F.normalise(bank, True).double().cpu()
     ref = pairs_ref64(zq, zb, (q_vid, q_cls, vid, cls), NO_SELF, t, bins)
     assert sum(ref['n']) == 30 * 130 and ref['n'][0] == 30 * 10 and min(ref['n']) > 0
     for rb, ch in ((7, 33), (None, None)):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests import abi_coverage as A
+from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EALIGN = -1, -2
@@ -39,30 +40,12 @@ PAIRSTAT_COVERAGE = {
 }
 
 
-def _header_functions():
-    hdr = open(os.path.join(ROOT, 'include', 'dualvar_pairstat.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    out = {}
-    for m in re.finditer(r'\b(?:int|int64_t)\s+(dv_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
-        out[m.group(1)] = (m.group(0).split()[0], [a.strip() for a in m.group(2).split(',') if a.strip() and a.strip() != 'void'])
-    return hdr, out
-
-
 def test_pairstat_header_table_and_library_agree():
     """include/dualvar_pairstat.h, _lib.PAIRSTAT_SIGNATURES, the library's exports and PAIRSTAT_COVERAGE name the same entries with
-    the same argument counts and return widths; the table is disjoint from the two others; the ledger's files call each entry"""
-    import ctypes
+    the same argument counts, types and return widths (tests/util.py check_header_binding); the ledger's files call each entry"""
     from dualvar_amd import _lib, build
-    hdr, decl = _header_functions()
+    hdr, decl = check_header_binding('dualvar_pairstat.h')
     assert set(decl) == set(_lib.PAIRSTAT_SIGNATURES) == set(PAIRSTAT_COVERAGE) == {'dv_pairstat_workspace', 'dv_pairstat_accum_f32'}
-    assert not set(_lib.PAIRSTAT_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.SELECT_SIGNATURES))
-    lib = _lib.load()
-    for name, (ret, args) in decl.items():
-        assert len(_lib.PAIRSTAT_SIGNATURES[name]) == len(args), (name, args)
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.PAIRSTAT_SIGNATURES[name]
-        assert fn.restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
-        assert (name in _lib.RETURNS_INT64) == (ret == 'int64_t')
     assert int(re.search(r'#define\s+DV_PAIRSTAT_MAX_BINS\s+(\d+)', hdr).group(1)) == _lib.DV_PAIRSTAT_MAX_BINS == 256
     assert 'pairstat.hip' in build.SOURCES
     for name, (fname, kind) in PAIRSTAT_COVERAGE.items():

@@ -1,11 +1,56 @@
 """Shared test helpers (not the product)."""
+import ctypes
 import os
+import re
 
 import numpy as np
 import torch
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 CLIP = dict(T=8, H=112, W=112)
+
+
+def header_functions(header):
+    """include/<header> -> (its text, {entry: (return type, [argument declarations])}) of the dv_* entries it declares"""
+    hdr = open(os.path.join(ROOT, 'include', header)).read()
+    src = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    out = {}
+    for m in re.finditer(r'\b(?:int|int64_t)\s+(dv_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
+        out[m.group(1)] = (m.group(0).split()[0], [a.strip() for a in m.group(2).split(',') if a.strip() and a.strip() != 'void'])
+    return hdr, out
+
+
+def _ctype_matches(typ, arg):
+    """the ctypes type of a table against one argument declaration of the header"""
+    if '*' in arg:
+        return typ is ctypes.c_void_p or issubclass(typ, ctypes._Pointer)
+    for word, want in (('int64_t', ctypes.c_int64), ('double', ctypes.c_double), ('float', ctypes.c_float)):
+        if arg.startswith(word):
+            return typ is want
+    return typ is ctypes.c_int32
+
+
+def check_header_binding(header):
+    """include/<header>, its table in _lib.HEADERS and the loaded library agree: the same entries, each exported, with the same
+    argument count and, per argument, the ctypes type its declaration asks for (a pointer: c_void_p or a POINTER type; int64_t,
+    double, float: their ctypes; any other integer: c_int32); argtypes and restype are bound as the table and the declared
+    return type say, and RETURNS_INT64 lists exactly the int64_t entries.  -> (the header's text, its declarations)"""
+    from dualvar_amd import _lib
+    table = _lib.HEADERS[header]
+    hdr, decl = header_functions(header)
+    assert set(decl) == set(table), (header, sorted(set(decl) ^ set(table)))
+    lib = _lib.load()
+    for name, (ret, args) in decl.items():
+        assert hasattr(lib, name), '%s declared in %s but not exported' % (name, header)
+        assert len(table[name]) == len(args), (name, len(table[name]), args)
+        for typ, arg in zip(table[name], args):
+            assert _ctype_matches(typ, arg), (name, arg, typ)
+        fn = getattr(lib, name)
+        assert fn.argtypes == table[name], name
+        assert fn.restype is (ctypes.c_int64 if ret == 'int64_t' else ctypes.c_int), name
+        assert (name in _lib.RETURNS_INT64) == (ret == 'int64_t'), name
+    return hdr, decl
 
 
 def gold(name):
