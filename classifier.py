@@ -130,6 +130,10 @@ def parse_args(argv=None):
     p.add_argument('--ridge_holdout', default=5, type=int, help='one training video in this many, per class, is held out to choose lambda')
     p.add_argument('--spectrum', action='store_true', help='with --test ... --retrieval: also the eigenvalue spectrum of the clip-feature covariance (effective rank, RankMe, alpha, PCA retrieval)')
     p.add_argument('--spectrum_k', default=[32, 64, 128], type=int, nargs='*', help='the numbers of leading principal components to project on (values above the feature width are clamped)')
+    p.add_argument('--map', action='store_true', help='with --test ... --retrieval: also mean average precision, precision@k, recall@k, R-precision and MRR over the full ranking')
+    p.add_argument('--map_k', default=[1, 5, 10, 20, 50], type=int, nargs='+', help='the cut-offs k of precision@k / recall@k / success@k (at most 16)')
+    p.add_argument('--map_level', default='video', choices=['video', 'clip', 'both'], help='rank test videos against train videos (mean features), test clips against train clips, or both')
+    p.add_argument('--map_within', action='store_true', help='with --map: also the test clips among themselves, the clips of their own video left out')
     p.add_argument('--center_crop', action='store_true')
     p.add_argument('--five_crop', action='store_true')
     p.add_argument('--ten_crop', action='store_true')
@@ -214,6 +218,14 @@ def check_args(args, environ=None):
         refuse('--spectrum decomposes the covariance of the retrieval clip features: pass --test <checkpoint> --retrieval with it')
     if not args.spectrum_k or any(k < 1 for k in args.spectrum_k):
         refuse('--spectrum_k takes one or more component counts of at least 1')
+    if args.map and not (args.test and args.retrieval):
+        refuse('--map ranks the retrieval features: pass --test <checkpoint> --retrieval with it')
+    if not 1 <= len(args.map_k) <= 16 or any(k < 1 for k in args.map_k):
+        refuse('--map_k takes one to 16 cut-offs of at least 1')
+    if args.map_within and not args.map:
+        refuse('--map_within adds to the --map report: pass --map with it')
+    if args.map_level != 'video' and not args.map:
+        refuse('--map_level chooses the features of the --map report: pass --map with it')
     if args.test:
         if args.retrieval:
             if args.num_seq != 10:
@@ -565,7 +577,7 @@ def test_retrieval(model, epoch, args):
             per_feature = torch.cat(per_feature, dim=0)
             torch.save(per_feature, os.path.join(out_dir, '%s_%s_per_feature.pth.tar' % (args.dataset, split)))
             feats[split] = (feature, label)
-            if args.variance or args.tsne or args.cluster or args.ridge or args.spectrum:
+            if args.variance or args.tsne or args.cluster or args.ridge or args.spectrum or args.map:
                 clips[split] = per_feature
     acc, sim = nn_retrieval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1], ks=(1, 5, 10, 20, 50))
     torch.save(sim, os.path.join(out_dir, '%s_sim.pth.tar' % args.dataset))
@@ -607,7 +619,47 @@ def test_retrieval(model, epoch, args):
         write_ridge(clips['train'], feats['train'][1], clips['test'], feats['test'][1], out_dir, args)
     if args.spectrum:
         write_spectrum(clips, feats, out_dir, args)
+    if args.map:
+        write_map(clips, feats, out_dir, args)
     return acc
+
+
+def write_map(clips, feats, out_dir, args):
+    """--map: mean average precision and the other full-ranking figures per level -> <dataset>_map.json (the reports) and
+    <dataset>_map.pth.tar (per level: ap, pos_cnt, first_rank of every query); the only writer of these two files"""
+    from dualvar_amd.utils.features import clip_rows
+    from dualvar_amd.utils.rankeval import ranking_eval, ranking_eval_within
+
+    def show(v):                         # a figure without queries is None
+        return 'n/a' if v is None else '%.4f' % v
+    ks = sorted(set(args.map_k))
+    runs = []
+    if args.map_level in ('video', 'both'):
+        runs.append(('video', lambda: ranking_eval(feats['test'][0], feats['test'][1], feats['train'][0], feats['train'][1],
+                                                   args.num_class, ks=ks)))
+    if args.map_level in ('clip', 'both'):
+        def clip_level():
+            te, _, te_cls, _, _ = clip_rows(clips['test'], feats['test'][1])
+            tr, _, tr_cls, _, _ = clip_rows(clips['train'], feats['train'][1])
+            return ranking_eval(te, te_cls, tr, tr_cls, args.num_class, ks=ks)
+        runs.append(('clip', clip_level))
+    if args.map_within:
+        runs.append(('within', lambda: ranking_eval_within(clips['test'], feats['test'][1], args.num_class, ks=ks)))
+    reports, tensors = {}, {}
+    for level, run in runs:
+        rep, state = run()
+        reports[level] = rep
+        tensors[level] = {name: state[name].cpu() for name in ('ap', 'pos_cnt', 'first_rank')}
+        args.logger.info('Ranking report on %s, %s level (%d queries, %d without a positive, bank of %d):'
+                         % (args.dataset, level, rep['n_query'], rep['n_skipped'], rep['n_bank']))
+        args.logger.info('\tmAP = %s macro mAP = %s MRR = %s R-precision = %s'
+                         % tuple(show(rep[name]) for name in ('mAP', 'mAP_macro', 'MRR', 'R_precision')))
+        for k in ks:
+            args.logger.info('\tP@%d = %s recall@%d = %s success@%d = %s'
+                             % (k, show(rep['precision_at'][k]), k, show(rep['recall_at'][k]), k, show(rep['success_at'][k])))
+    with open(os.path.join(out_dir, '%s_map.json' % args.dataset), 'w') as fp:
+        json.dump(reports, fp, indent=1)
+    torch.save(tensors, os.path.join(out_dir, '%s_map.pth.tar' % args.dataset))
 
 
 def write_spectrum(clips, feats, out_dir, args):

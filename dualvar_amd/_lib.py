@@ -22,6 +22,7 @@ DV_RIDGE_MAX_D = 4096       # == DV_RIDGE_MAX_D of include/dualvar_ridge.h: the 
 DV_RIDGE_MAX_C = 4096       # == DV_RIDGE_MAX_C of include/dualvar_ridge.h: the most classes of the dv_ridge_* entries
 DV_SPECTRUM_MAX_D = 4096    # == DV_SPECTRUM_MAX_D of include/dualvar_spectrum.h: the largest matrix order of the dv_spectrum_* entries
 DV_SPECTRUM_MAX_SWEEPS = 64  # == DV_SPECTRUM_MAX_SWEEPS of include/dualvar_spectrum.h: the cap on Jacobi sweeps of utils.spectrum.eigh_jacobi
+DV_RANKEVAL_MAX_POS = 4096   # == DV_RANKEVAL_MAX_POS of include/dualvar_rankeval.h: the longest list of positives per query of the dv_rankeval_* entries
 DV_W3 = 128                  # conv fwd / dgrad in DV_F32: weights pre-split in fragment order (dv_pack_w3)
 
 _ERR = {-1: 'DV_EINVAL (inconsistent shapes / unsupported parameter)',
@@ -241,6 +242,14 @@ SPECTRUM_SIGNATURES = {
     'dv_spectrum_values_f64': [P, I64, P, I64, I32, P, P],
 }
 
+# name -> argtypes of include/dualvar_rankeval.h (the full-ranking retrieval figures of csrc/rankeval.hip)
+RANKEVAL_SIGNATURES = {
+    'dv_rankeval_gather_f32': [P, I32, I32, I32, I32, P, P, P, P, I32, I64, P, P, I32, P, I32, P],
+    'dv_rankeval_sort': [P, P, I32, P, I32, P],
+    'dv_rankeval_count_f32': [P, I32, I32, I32, I32, P, P, I32, I64, P, P, I32, P, P, I32, I32, P],
+    'dv_rankeval_finish': [P, I32, P, I32, I32, P, I32, P, P, P, P, P, P, P],
+}
+
 # name -> argtypes of include/dualvar_conv_pair.h (two independent convs in one grid: csrc/conv.hip, csrc/conv_tap.hip)
 PAIR_SIGNATURES = {
     'dv_conv3d_pair_ok': [CD, CD, I32],
@@ -259,6 +268,7 @@ HEADERS = {
     'dualvar_cluster.h': CLUSTER_SIGNATURES,
     'dualvar_ridge.h': RIDGE_SIGNATURES,
     'dualvar_spectrum.h': SPECTRUM_SIGNATURES,
+    'dualvar_rankeval.h': RANKEVAL_SIGNATURES,
     'dualvar_conv_pair.h': PAIR_SIGNATURES,
 }
 _names = [n for table in HEADERS.values() for n in table]
