@@ -755,7 +755,7 @@ class Plan:
         grad, f32 = self.with_grad and self.training, self.dtype == DV_F32
         if grad and FUSE_BN_REDUCE:
             for m, cop in self._bn_reduce_candidates(g):     # the atomic form (dv_conv3d_dgrad_bn)
-                cop.bn_fuse, m.reduce_fused = m, True
+                cop.take_bn_reduce(m)
         if self.training and FUSE_BN_IN and f32:
             self._fuse_bn_in(g)
         self.bn_fuse_ws = None
@@ -786,7 +786,7 @@ class Plan:
         """conv -> BatchNorm(+ReLU) -> conv chains: when the second conv is the only writer of the gradient of the BatchNorm's
         output, its data gradient IS dL/dy of that BatchNorm, complete after one launch -- the BatchNorm backward's reduce
         (sum g, sum g*xhat) can run in that launch's epilogue instead of re-reading dL/dy in a pass of its own.
-        -> (member, consuming ConvOp), lazily: a conv that has taken one member is not offered another."""
+        -> (member, consuming ConvOp); whether that conv's data gradient can carry the reduce is the conv's to say."""
         for m in self._bn_members():
             y = m.y
             if y.grad is None or not m.plain() or m.fused_pool is not None:
@@ -795,7 +795,7 @@ class Plan:
             if len(w) != 1 or not isinstance(w[0][0], ConvOp):
                 continue
             cop, _, a = w[0]
-            if cop.fp8 or a.buf is not y.buf or a.off != y.off or a.C != y.C or a.rows != y.rows or cop.bn_fuse is not None:
+            if a.buf is not y.buf or a.off != y.off or a.C != y.C or a.rows != y.rows:
                 continue
             yield m, cop
 
@@ -803,17 +803,8 @@ class Plan:
         """the ordered form on the LDS-staged input-tile kernel (dv_conv3d_dgrad_bn_ws)"""
         need_ws = 0
         for m, cop in self._bn_reduce_candidates(g):
-            if m.x.ld * 4 * (m.x.rows - 1) >= (1 << 31):
-                continue
-            _, wdflag = self.store.w_dgrad(cop.slot, strided=False)
-            if not wdflag or max(cop.s) > 1 or cop.slot.cout_pitch * cop.k[0] * cop.k[1] * cop.k[2] < FUSE_BN_REDUCE_TAP_MIN_K:
-                continue                 # (short K loops: the epilogue's read of the BatchNorm input is not hidden)
-            d3 = ops.conv_desc(cop.dtype, cop.x, cop.y, cop.k, cop.s, cop.p, flags=wdflag)
-            nb = int(self.lib.dv_conv3d_dgrad_bn_workspace(C.byref(d3)))
-            if nb <= 0:
-                continue
-            cop.bn_fuse, cop.bn_fuse_tap, m.reduce_fused = m, True, True
-            need_ws = max(need_ws, nb)
+            if m.x.ld * 4 * (m.x.rows - 1) < (1 << 31):
+                need_ws = max(need_ws, cop.take_bn_reduce(m, ordered=True))
         if need_ws:
             # one workspace for all of them (they run one after the other on the main stream; the ticket words are zero
             # between launches, and after a failed launch: _lib.register_ticket_workspace)
@@ -825,27 +816,18 @@ class Plan:
             y, cop = m.y, g.sole_reader(m.y)
             if not m.plain() or m.fused_pool is not None or m.conv_bias is not None or not isinstance(cop, ConvOp):
                 continue
-            if (cop.fp8 or cop.bn_in is not None or cop.x.buf is not y.buf or cop.x.off != y.off or cop.x.C != y.C
-                    or m.x.cpitch != cop.slot.cin_pitch or m.x.rows != y.rows or m.x.C != y.C):
-                continue
-            d = ops.conv_desc(cop.dtype, m.x, cop.y, cop.k, cop.s, cop.p, flags=cop.d.flags)
-            if not int(self.lib.dv_conv3d_bn_in_ok(C.byref(d))) or ops.tile_rows(d) != cop.tile_rows:
-                continue
-            cop.bn_in, m.fused_conv = m, cop
+            if cop.x.buf is y.buf and cop.x.off == y.off and cop.x.C == y.C and m.x.rows == y.rows and m.x.C == y.C:
+                cop.take_bn_in(m)
 
     def _fuse_bn_wgrad(self):
         """BatchNorm-backward apply inside the weight gradient of the producing conv, when that conv's input needs no gradient:
         the weight gradient is the only reader of dL/d(conv output) then"""
         for m in self._bn_members(lone=True):
             cop = m.conv
-            if (not isinstance(cop, ConvOp) or cop.need_dx or cop.fp8 or cop.bn_apply is not None or not m.plain()
-                    or m.x.buf is not cop.y.buf or m.x.off != cop.y.off or m.x.C != cop.y.C or m.x.grad is None
-                    or m.y.grad is None or m.x.ld != m.y.grad.ld):
+            if (not isinstance(cop, ConvOp) or cop.need_dx or not m.plain() or m.x.buf is not cop.y.buf or m.x.off != cop.y.off
+                    or m.x.C != cop.y.C or m.x.grad is None or m.y.grad is None or m.x.ld != m.y.grad.ld):
                 continue
-            d = ops.conv_desc(cop.dtype, cop.x, cop.y, cop.k, cop.s, cop.p, flags=0)
-            if d.ldy != m.y.grad.ld or not self.lib.dv_conv3d_wgrad_bn_ok(C.byref(d)):
-                continue
-            cop.bn_apply, m.apply_fused = m, True
+            cop.take_bn_apply(m)
 
     def _emit(self):
         # scratch of the deterministic weight gradients (row-split partial tiles): ONE buffer per plan, sized for the
@@ -853,7 +835,7 @@ class Plan:
         # reduce, so they can share it
         self.wgrad_ws = None
         if self.with_grad:
-            need = max([o.wgrad_workspace_bytes() for o in self.ops if isinstance(o, ConvOp)] + [0])
+            need = max([ops.wgrad_workspace_bytes(o.d_w) for o in self.ops if isinstance(o, ConvOp)] + [0])
             if need:
                 self.wgrad_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 self.bytes += need
@@ -1022,7 +1004,11 @@ def _abytes(a, c=None):
 
 
 class ConvOp(Op):
-    """conv (bias-free, BN partial statistics in the epilogue) with wgrad + dgrad."""
+    """conv (bias-free, BN partial statistics in the epilogue) with wgrad + dgrad.
+
+    Each direction has ONE descriptor, the one its launch carries: d_in / d_w / dgrad_desc(), all built by _desc.
+    A fusion of Plan.finalize asks take_bn_in / take_bn_apply / take_bn_reduce; each queries the library with the
+    descriptor the launch will then carry, so what was asked and what is launched cannot part."""
 
     def __init__(self, plan, slot, x, k, s, p, out, stats, fp8=False):
         super().__init__(plan)
@@ -1034,7 +1020,7 @@ class ConvOp(Op):
         assert x.cpitch == slot.cin_pitch, (x.cpitch, slot.cin_pitch)
         stats = stats and plan.training              # eval-mode BatchNorm needs no batch statistics
         self._wf, wflag = plan.store.w_fwd(slot)
-        self.d = ops.conv_desc(self.dtype, x, self.y, k, s, p, flags=(DV_STATS if stats else 0) | wflag)
+        self.d = self._desc(x, (DV_STATS if stats else 0) | wflag)
         self.tiles = ops.stat_tiles(self.d)
         self.tile_rows = ops.tile_rows(self.d)
         self.stats = plan.f32(2, slot.Cout, self.tiles) if stats else None
@@ -1045,6 +1031,13 @@ class ConvOp(Op):
         self.bn_fuse_tap = False     # ... in the ordered form of the LDS-staged kernel (dv_conv3d_dgrad_bn_ws)
         self.bn_apply = None         # BNMember (of this conv's output) whose backward apply this conv's weight gradient carries
         self.bn_in = None            # BNMember (of this conv's INPUT) applied on load: x is never materialised (FUSE_BN_IN)
+        # the descriptors the three directions launch with.  d_in, the forward's, and d_w, the weight gradient's (no flags: its
+        # operands are activations), are on the input actually read: x, or the input of the BatchNorm applied on load
+        # (take_bn_in); d_g, the data gradient's, is fixed by dgrad_desc()
+        self.d_in, self.d_w, self.d_g, self._wd = self.d, self._desc(x, 0), None, None
+        if fp8:                      # the quantised copy of x is dense: pitch = channel pitch (dv_conv3d_fwd_fp8)
+            self.d_in = self._desc(x, self.d.flags)
+            self.d_in.ldx = x.cpitch
 
     def inputs(self):
         return [self.x]
@@ -1052,163 +1045,167 @@ class ConvOp(Op):
     def grad_targets(self):
         return [('x', self.x)] if self.need_dx else []
 
-    def wgrad_workspace_bytes(self):
-        d = ops.conv_desc(self.dtype, self.x, self.y, self.k, self.s, self.p, flags=0)
-        return ops.wgrad_workspace_bytes(d)
+    def _desc(self, x, flags):
+        """this conv on input x (self.x, or the input of a BatchNorm applied on load): the one builder of its descriptors"""
+        return ops.conv_desc(self.dtype, x, self.y, self.k, self.s, self.p, flags=flags)
+
+    def dgrad_desc(self):
+        """of the data gradient, with its accumulate flag and the weight form it takes (self._wd).  Fixed at the first call:
+        not before PlanGraph.set_accumulate_flags, nor before an atomic reduce is taken (take_bn_reduce)."""
+        if self.d_g is None:
+            st, sl, acc = self.plan.store, self.slot, DV_ACCUM if self.acc['x'] else 0
+            self._wd, wdflag = st.w_dgrad(sl, strided=max(self.s) > 1)
+            if max(self.s) > 1 and (self.bn_fuse is None or self.bn_fuse_tap):
+                # a strided data gradient takes the pre-split weights only where every parity class of it runs on the
+                # LDS-staged input-tile kernel (the 7x1x1 / stride-2 stem conv: dv_conv3d_tap_kind says so)
+                wdp3, wdflag3 = st.w_dgrad(sl, strided=False)
+                if wdflag3 and int(self.plan.lib.dv_conv3d_tap_kind(C.byref(self._desc(self.x, acc | wdflag3)), 1)):
+                    self._wd, wdflag = wdp3, wdflag3
+            self.d_g = self._desc(self.x, acc | wdflag)
+            if self.fp8:             # the quantised copy of dL/dy is dense (dv_conv3d_dgrad_fp8; bf16 has no pre-split weights)
+                self.d_g.ldy = self.y.cpitch
+        return self.d_g
+
+    def take_bn_in(self, m):
+        """Plan.finalize: apply BatchNorm member m, whose output x is, on load in the forward and the weight gradient"""
+        d = self._desc(m.x, self.d.flags)
+        if not (self.fp8 or self.bn_in is not None or m.x.cpitch != self.slot.cin_pitch
+                or not int(self.plan.lib.dv_conv3d_bn_in_ok(C.byref(d))) or ops.tile_rows(d) != self.tile_rows):
+            self.bn_in, m.fused_conv, self.d_in, self.d_w = m, self, d, self._desc(m.x, 0)
+
+    def take_bn_apply(self, m):
+        """Plan.finalize: form the backward apply of member m, the BatchNorm of this conv's output, inside the weight gradient
+        (never beside a BatchNorm on load: that weight gradient has an entry of its own)"""
+        d = self.d_w
+        if not (self.fp8 or self.bn_apply is not None or self.bn_in is not None or d.ldy != m.y.grad.ld
+                or not self.plan.lib.dv_conv3d_wgrad_bn_ok(C.byref(d))):
+            self.bn_apply, m.apply_fused = m, True
+
+    def take_bn_reduce(self, m, ordered=False):
+        """Plan.finalize: carry the backward reduce of member m, whose output x is, in the data gradient's epilogue.  ordered: in
+        the form of the LDS-staged input-tile kernel only -> the bytes of workspace that takes (0: not taken).
+        dv_conv3d_dgrad_bn_workspace answers 0 for DV_ACCUM (the form does not add to dx): m's sole gradient writer never
+        accumulates (PlanGraph.set_accumulate_flags), and the query sees the launch's own flag."""
+        if self.fp8 or self.bn_fuse is not None or (ordered and max(self.s) > 1):
+            return 0
+        nb = 0
+        if ordered:
+            d = self.dgrad_desc()
+            # (not behind a short K loop: the epilogue's read of the BatchNorm input is not hidden there)
+            if d.flags & L.DV_W3 and self.slot.cout_pitch * self.k[0] * self.k[1] * self.k[2] >= FUSE_BN_REDUCE_TAP_MIN_K:
+                nb = int(self.plan.lib.dv_conv3d_dgrad_bn_workspace(C.byref(d)))
+            if nb <= 0:
+                return 0
+        assert ordered or self.d_g is None      # (dgrad_desc's weight choice looks at bn_fuse)
+        self.bn_fuse, self.bn_fuse_tap, m.reduce_fused = m, ordered, True
+        return nb
 
     def launches(self):
-        p, st, lib, sl, x, y = self.plan, self.plan.store, self.plan.lib, self.slot, self.x, self.y
-        es = ops.ESIZE[self.dtype]
-        taps = self.k[0] * self.k[1] * self.k[2]
-        kdim = self.alg_k if self.alg_k is not None else taps * sl.Cin
-        flops = 2 * y.rows * sl.Cout * kdim
-        wbytes = sl.Cout * kdim * es
+        return self.fwd_launches(), (self.wgrad_launches() + self.dgrad_launches() if self.plan.with_grad else [])
+
+    def _cost(self):
+        """-> (algorithmic K, flops, weight bytes, gather width, shape label): the same for the three directions"""
+        sl = self.slot
+        kdim = self.alg_k if self.alg_k is not None else self.k[0] * self.k[1] * self.k[2] * sl.Cin
         gv = 8 if (self.dtype == DV_BF16 and sl.cin_pitch % 8) else 16
-        kf = _conv_kname(lib, self.d, 0, _dt(self.dtype), gv)
-        shp = 'M%d Cin%d Cout%d k%s s%s' % (y.rows, sl.Cin, sl.Cout, 'x'.join(map(str, self.k)), 'x'.join(map(str, self.s)))
-        f = [Launch('conv_fwd', kf, lib.dv_conv3d_fwd,
-                    (C.byref(self.d), x.ptr, self._wf, 0, y.ptr, self.stats.data_ptr() if self.stats is not None else 0),
-                    _abytes(x) + wbytes + _abytes(y), flops, shp)]
-        if self.bn_in is not None:
-            m = self.bn_in
-            r = self._bn_in = L.BnIn()
-            r.scale, r.shift, r.flags = m.scale.data_ptr(), m.shift.data_ptr(), (DV_RELU if m.relu else 0)
-            self.d_in = ops.conv_desc(self.dtype, m.x, y, self.k, self.s, self.p, flags=self.d.flags)
-            f = [Launch('conv_fwd', _conv_kname(lib, self.d_in, 0, _dt(self.dtype), gv) + '+bn_in', lib.dv_conv3d_fwd_bn_in,
-                        (C.byref(self.d_in), m.x.ptr, C.byref(r), self._wf, y.ptr, self.stats.data_ptr() if self.stats is not None else 0),
-                        _abytes(x) + wbytes + _abytes(y), flops, shp + ' +bn_in')]
-        stats_ptr = self.stats.data_ptr() if self.stats is not None else 0
-        if self.fp8:
-            f = self._fp8_forward(shp, flops, wbytes)
-        elif self.bn_in is not None:
-            m = self.bn_in
-            f[0].pair = PairMember('fwd_bn_in', self.d_in, (C.byref(self.d_in), m.x.ptr, C.byref(self._bn_in), self._wf, y.ptr, stats_ptr),
-                                   [m.x, m.scale, m.shift], [y, self.stats])
-        else:
-            f[0].pair = PairMember('fwd', self.d, (C.byref(self.d), x.ptr, self._wf, y.ptr, stats_ptr), [x], [y, self.stats])
-        b = []
-        if p.with_grad:
-            self.d_w = ops.conv_desc(self.dtype, x, y, self.k, self.s, self.p, flags=0)
-            tr, tc, tsp = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-            L.check(lib.dv_conv3d_wgrad_tile(C.byref(self.d_w), C.byref(tr), C.byref(tc), C.byref(tsp)), 'dv_conv3d_wgrad_tile')
-            tile = '%d,%d' % (tr.value, tc.value)
-            ws = p.wgrad_ws
-            if self.bn_apply is not None:
-                m = self.bn_apply
-                gs, bs = st.slot(m.bn.weight), st.slot(m.bn.bias)
-                r = self._bn_bwd = L.BnBwd()
-                r.x, r.ldx = y.ptr, y.ld
-                r.mean, r.invstd, r.scale, r.shift = (t.data_ptr() for t in (m.mean, m.invstd, m.scale, m.shift))
-                r.gamma, r.dgamma, r.dbeta = st.w_master(gs), st.w_grad(gs), st.w_grad(bs)
-                r.sums, r.n_rep, r.flags = p.zero_ptr(m.sums_off), BN_REPLICAS, (0 if m.relu else DV_NO_RELU_MASK)
-                r.inv_count, r.dparam_scale = 1.0 / (m.M * p.comm.world), 1.0 / p.comm.world
-                b.append(Launch('conv_wgrad', 'conv_wgrad<%s,%d,%s>+bn_bwd_apply' % (_dt(self.dtype), gv, tile), lib.dv_conv3d_wgrad_bn,
-                                (C.byref(self.d_w), x.ptr, m.y.grad.ptr, st.w_grad(sl), ws.data_ptr() if ws is not None else 0,
-                                 ws.numel() if ws is not None else 0, C.byref(r)),
-                                _abytes(x) + 2 * _abytes(y) + sl.Cout * kdim * 4, flops, shp + ' +bn_bwd_apply'))
-                b[-1].gend = max(sl.off + sl.size, _gend(gs, bs))
-            elif self.bn_in is not None:
-                m = self.bn_in
-                self.d_w_in = ops.conv_desc(self.dtype, m.x, y, self.k, self.s, self.p, flags=0)
-                b.append(Launch('conv_wgrad', 'conv_wgrad<%s,%d,%s>+bn_in' % (_dt(self.dtype), gv, tile), lib.dv_conv3d_wgrad_bn_in,
-                                (C.byref(self.d_w_in), m.x.ptr, C.byref(self._bn_in), y.grad.ptr, st.w_grad(sl),
-                                 ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0),
-                                _abytes(x) + _abytes(y) + sl.Cout * kdim * 4, flops, shp + ' +bn_in'))
-                b[-1].gend = sl.off + sl.size
-            else:
-                b.append(Launch('conv_wgrad', 'conv_wgrad<%s,%d,%s>' % (_dt(self.dtype), gv, tile), lib.dv_conv3d_wgrad,
-                                (C.byref(self.d_w), x.ptr, y.grad.ptr, st.w_grad(sl), ws.data_ptr() if ws is not None else 0,
-                                 ws.numel() if ws is not None else 0),
-                                _abytes(x) + _abytes(y) + sl.Cout * kdim * 4, flops, shp))
-                b[-1].gend = sl.off + sl.size
-            if self.zero_pad_taps is not None:
-                rows, pitch, c0, nc = self.zero_pad_taps
-                b.append(Launch('stem_pad_taps', 'fill_cols', lib.dv_fill_cols_f32, (st.w_grad(sl), rows, pitch, c0, nc, 0.0)))
-                b[-1].gend = sl.off + sl.size
-            if self.need_dx and self.fp8:
-                b += self._fp8_dgrad(shp, flops, wbytes)
-            elif self.need_dx:
-                acc = bool(self.acc.get('x'))
-                wdp, wdflag = st.w_dgrad(sl, strided=max(self.s) > 1)
-                if max(self.s) > 1 and (self.bn_fuse is None or self.bn_fuse_tap):
-                    # a strided data gradient takes the pre-split weights only where every parity class of it runs on the
-                    # LDS-staged input-tile kernel (the 7x1x1 / stride-2 stem conv: dv_conv3d_tap_kind says so)
-                    wdp3, wdflag3 = st.w_dgrad(sl, strided=False)
-                    if wdflag3:
-                        d3 = ops.conv_desc(self.dtype, x, y, self.k, self.s, self.p, flags=(DV_ACCUM if acc else 0) | wdflag3)
-                        if int(lib.dv_conv3d_tap_kind(C.byref(d3), 1)):
-                            wdp, wdflag = wdp3, wdflag3
-                self.d_g = ops.conv_desc(self.dtype, x, y, self.k, self.s, self.p, flags=(DV_ACCUM if acc else 0) | wdflag)
-                kd = _conv_kname(lib, self.d_g, 1, _dt(self.dtype))
-                if self.bn_fuse is not None:
-                    m = self.bn_fuse
-                    r = self._bn_reduce = L.BnReduce()
-                    r.x, r.ldx = m.x.ptr, m.x.ld
-                    r.mean, r.invstd, r.scale, r.shift = (t.data_ptr() for t in (m.mean, m.invstd, m.scale, m.shift))
-                    r.sums, r.n_rep, r.flags = p.zero_ptr(m.sums_off), BN_REPLICAS, (0 if m.relu else DV_NO_RELU_MASK)
-                    if self.bn_fuse_tap:
-                        ws = p.bn_fuse_ws
-                        b.append(Launch('conv_dgrad', kd + '+bn_reduce', lib.dv_conv3d_dgrad_bn_ws,
-                                        (C.byref(self.d_g), y.grad.ptr, wdp, x.grad.ptr, C.byref(r), ws.data_ptr(), ws.numel() * 4),
-                                        _abytes(y) + wbytes + _abytes(x) * 2, flops, shp + ' +bn_reduce'))
-                    else:
-                        b.append(Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad_bn, (C.byref(self.d_g), y.grad.ptr, wdp, x.grad.ptr, C.byref(r)),
-                                        _abytes(y) + wbytes + _abytes(x) * 2, flops, shp + ' +bn_reduce'))
-                else:
-                    b.append(Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad, (C.byref(self.d_g), y.grad.ptr, wdp, x.grad.ptr),
-                                    _abytes(y) + wbytes + _abytes(x) * (2 if acc else 1), flops, shp))
-                    b[-1].pair = PairMember('dgrad', self.d_g, (C.byref(self.d_g), y.grad.ptr, wdp, x.grad.ptr, 0),
-                                            [y.grad] + ([x.grad] if acc else []), [x.grad])
-        return f, b
+        shp = 'M%d Cin%d Cout%d k%s s%s' % (self.y.rows, sl.Cin, sl.Cout, 'x'.join(map(str, self.k)), 'x'.join(map(str, self.s)))
+        return kdim, 2 * self.y.rows * sl.Cout * kdim, sl.Cout * kdim * ops.ESIZE[self.dtype], gv, shp
 
-
-def _fp8_methods():
-    """fp8 pointwise path of ConvOp (compute mode 'fp8pw'; include/dualvar_hip.h: dv_conv3d_fwd_fp8 / dv_conv3d_dgrad_fp8)"""
-    def _ws(self):
+    def _quantize(self, a, fmt, shp):
+        """-> (dense fp8 copy of activation a, its scale, the launch that fills them): in front of an fp8 conv (mode 'fp8pw')"""
         p = self.plan
         if p._fp8_ws is None:
             p._fp8_ws = p.f32(p.lib.dv_quantize_fp8_workspace() // 4)
-        return p._fp8_ws
+        q, sc = torch.empty(a.rows, a.cpitch, dtype=torch.uint8, device=p.device), p.f32(1)
+        p.bytes += q.numel()
+        return q, sc, Launch('quantize_fp8', 'quantize_fp8<%s>' % ('e5m2' if fmt else 'e4m3'), p.lib.dv_quantize_fp8,
+                             (DV_BF16, a.ptr, a.rows, a.cpitch, a.ld, fmt, q.data_ptr(), a.cpitch, sc.data_ptr(), p._fp8_ws.data_ptr()),
+                             2 * _abytes(a) + q.numel(), 0, shp)
 
-    def _fp8_forward(self, shp, flops, wbytes):
-        p, st, lib, sl, x, y = self.plan, self.plan.store, self.plan.lib, self.slot, self.x, self.y
-        w8, sw, _, _ = st.fp8_weights(sl)
-        self.x8 = torch.empty(x.rows, x.cpitch, dtype=torch.uint8, device=p.device)
-        self.sx = p.f32(1)
-        p.bytes += self.x8.numel()
-        ws = _ws(self)
-        self.d8 = ops.conv_desc(DV_BF16, x, y, self.k, self.s, self.p, flags=self.d.flags)
-        self.d8.ldx = x.cpitch
-        tile = _tile_shape(lib, self.d, 0)
-        return [Launch('quantize_fp8', 'quantize_fp8<e4m3>', lib.dv_quantize_fp8,
-                       (DV_BF16, x.ptr, x.rows, x.cpitch, x.ld, 0, self.x8.data_ptr(), x.cpitch, self.sx.data_ptr(), ws.data_ptr()),
-                       2 * _abytes(x) + x.rows * x.cpitch, 0, shp),
-                Launch('conv_fwd', 'conv_gemm<fp8,FWD,16,%d,%d>' % tile, lib.dv_conv3d_fwd_fp8,
-                       (C.byref(self.d8), self.x8.data_ptr(), w8.data_ptr(), self.sx.data_ptr(), sw.data_ptr(), y.ptr,
-                        self.stats.data_ptr() if self.stats is not None else 0),
-                       x.rows * x.cpitch + wbytes // 2 + _abytes(y), flops, shp)]
+    def fwd_launches(self):
+        """plain / with the BatchNorm of the input applied on load / fp8 behind the quantisation of x"""
+        lib, x, y, d = self.plan.lib, self.x, self.y, self.d_in
+        _, flops, wbytes, gv, shp = self._cost()
+        stats = self.stats.data_ptr() if self.stats is not None else 0
+        if self.fp8:
+            w8, sw, _, _ = self.plan.store.fp8_weights(self.slot)
+            self.x8, self.sx, ql = self._quantize(x, 0, shp)
+            return [ql, Launch('conv_fwd', 'conv_gemm<fp8,FWD,16,%d,%d>' % _tile_shape(lib, d, 0), lib.dv_conv3d_fwd_fp8,
+                               (C.byref(d), self.x8.data_ptr(), w8.data_ptr(), self.sx.data_ptr(), sw.data_ptr(), y.ptr, stats),
+                               self.x8.numel() + wbytes // 2 + _abytes(y), flops, shp)]
+        kf, nbytes = _conv_kname(lib, d, 0, _dt(self.dtype), gv), _abytes(x) + wbytes + _abytes(y)
+        if self.bn_in is not None:
+            m = self.bn_in
+            args = (C.byref(d), m.x.ptr, C.byref(ops.bn_in_desc(m.scale, m.shift, m.relu)), self._wf, y.ptr, stats)
+            l = Launch('conv_fwd', kf + '+bn_in', lib.dv_conv3d_fwd_bn_in, args, nbytes, flops, shp + ' +bn_in')
+            l.pair = PairMember('fwd_bn_in', d, args, [m.x, m.scale, m.shift], [y, self.stats])
+        else:
+            l = Launch('conv_fwd', kf, lib.dv_conv3d_fwd, (C.byref(d), x.ptr, self._wf, 0, y.ptr, stats), nbytes, flops, shp)
+            l.pair = PairMember('fwd', d, (C.byref(d), x.ptr, self._wf, y.ptr, stats), [x], [y, self.stats])
+        return [l]
 
-    def _fp8_dgrad(self, shp, flops, wbytes):
-        p, st, lib, sl, x, y = self.plan, self.plan.store, self.plan.lib, self.slot, self.x, self.y
-        _, _, wd8, swd = st.fp8_weights(sl)
-        self.dy8 = torch.empty(y.rows, y.cpitch, dtype=torch.uint8, device=p.device)
-        self.sdy = p.f32(1)
-        p.bytes += self.dy8.numel()
-        ws = _ws(self)
-        acc = bool(self.acc.get('x'))
-        self.d8g = ops.conv_desc(DV_BF16, x, y, self.k, self.s, self.p, flags=DV_ACCUM if acc else 0)
-        self.d8g.ldy = y.cpitch
-        g = y.grad
-        return [Launch('quantize_fp8', 'quantize_fp8<e5m2>', lib.dv_quantize_fp8,
-                       (DV_BF16, g.ptr, g.rows, g.cpitch, g.ld, 1, self.dy8.data_ptr(), y.cpitch, self.sdy.data_ptr(), ws.data_ptr()),
-                       2 * _abytes(y) + y.rows * y.cpitch, 0, shp),
-                Launch('conv_dgrad', 'conv_gemm<fp8,DGRAD,16,%d,%d>' % _tile_shape(lib, self.d8g, 1), lib.dv_conv3d_dgrad_fp8,
-                       (C.byref(self.d8g), self.dy8.data_ptr(), wd8.data_ptr(), self.sdy.data_ptr(), swd.data_ptr(), x.grad.ptr),
-                       y.rows * y.cpitch + wbytes // 2 + _abytes(x) * (2 if acc else 1), flops, shp)]
-    return _fp8_forward, _fp8_dgrad
+    def wgrad_launches(self):
+        """plain / forming the backward apply of the output's BatchNorm / on load; then the stem's pad-tap clear"""
+        p, st, lib, sl, x, y, d = self.plan, self.plan.store, self.plan.lib, self.slot, self.x, self.y, self.d_w
+        kdim, flops, _, gv, shp = self._cost()
+        tr, tc, tsp = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        L.check(lib.dv_conv3d_wgrad_tile(C.byref(d), C.byref(tr), C.byref(tc), C.byref(tsp)), 'dv_conv3d_wgrad_tile')
+        kw = 'conv_wgrad<%s,%d,%d,%d>' % (_dt(self.dtype), gv, tr.value, tc.value)
+        ws = (p.wgrad_ws.data_ptr(), p.wgrad_ws.numel()) if p.wgrad_ws is not None else (0, 0)
+        dw, nbytes, gend = st.w_grad(sl), _abytes(x) + _abytes(y) + sl.Cout * kdim * 4, sl.off + sl.size
+        if self.bn_apply is not None:
+            m = self.bn_apply
+            gs, bs = st.slot(m.bn.weight), st.slot(m.bn.bias)
+            r = L.BnBwd()
+            r.x, r.ldx = y.ptr, y.ld
+            r.mean, r.invstd, r.scale, r.shift = (t.data_ptr() for t in (m.mean, m.invstd, m.scale, m.shift))
+            r.gamma, r.dgamma, r.dbeta = st.w_master(gs), st.w_grad(gs), st.w_grad(bs)
+            r.sums, r.n_rep, r.flags = p.zero_ptr(m.sums_off), BN_REPLICAS, (0 if m.relu else DV_NO_RELU_MASK)
+            r.inv_count, r.dparam_scale = 1.0 / (m.M * p.comm.world), 1.0 / p.comm.world
+            b = [Launch('conv_wgrad', kw + '+bn_bwd_apply', lib.dv_conv3d_wgrad_bn, (C.byref(d), x.ptr, m.y.grad.ptr, dw) + ws + (C.byref(r),),
+                        nbytes + _abytes(y), flops, shp + ' +bn_bwd_apply')]
+            b[0].gend = _gend(gs, bs)    # (it writes the BatchNorm's parameter gradients too)
+        elif self.bn_in is not None:
+            m = self.bn_in
+            b = [Launch('conv_wgrad', kw + '+bn_in', lib.dv_conv3d_wgrad_bn_in,
+                        (C.byref(d), m.x.ptr, C.byref(ops.bn_in_desc(m.scale, m.shift, m.relu)), y.grad.ptr, dw) + ws,
+                        nbytes, flops, shp + ' +bn_in')]
+        else:
+            b = [Launch('conv_wgrad', kw, lib.dv_conv3d_wgrad, (C.byref(d), x.ptr, y.grad.ptr, dw) + ws, nbytes, flops, shp)]
+        if self.zero_pad_taps is not None:
+            rows, pitch, c0, nc = self.zero_pad_taps
+            b.append(Launch('stem_pad_taps', 'fill_cols', lib.dv_fill_cols_f32, (dw, rows, pitch, c0, nc, 0.0)))
+        for l in b:
+            l.gend = max(l.gend, gend)
+        return b
 
-
-ConvOp._fp8_forward, ConvOp._fp8_dgrad = _fp8_methods()
+    def dgrad_launches(self):
+        """plain / with a BatchNorm-backward reduce in the epilogue, atomic or ordered / fp8 behind the quantisation of dL/dy"""
+        if not self.need_dx:
+            return []
+        p, lib, x, y, d = self.plan, self.plan.lib, self.x, self.y, self.dgrad_desc()
+        _, flops, wbytes, _, shp = self._cost()
+        dxbytes = _abytes(x) * (2 if d.flags & DV_ACCUM or self.bn_fuse is not None else 1)      # (the reduce re-reads its tile)
+        if self.fp8:
+            _, _, wd8, swd = p.store.fp8_weights(self.slot)
+            self.dy8, self.sdy, ql = self._quantize(y.grad, 1, shp)
+            return [ql, Launch('conv_dgrad', 'conv_gemm<fp8,DGRAD,16,%d,%d>' % _tile_shape(lib, d, 1), lib.dv_conv3d_dgrad_fp8,
+                               (C.byref(d), self.dy8.data_ptr(), wd8.data_ptr(), self.sdy.data_ptr(), swd.data_ptr(), x.grad.ptr),
+                               self.dy8.numel() + wbytes // 2 + dxbytes, flops, shp)]
+        kd, args = _conv_kname(lib, d, 1, _dt(self.dtype)), (C.byref(d), y.grad.ptr, self._wd, x.grad.ptr)
+        nbytes = _abytes(y) + wbytes + dxbytes
+        if self.bn_fuse is None:
+            l = Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad, args, nbytes, flops, shp)
+            l.pair = PairMember('dgrad', d, args + (0,), [y.grad] + ([x.grad] if d.flags & DV_ACCUM else []), [x.grad])
+            return [l]
+        m = self.bn_fuse
+        r = ops.bn_reduce_desc(m.x, m.mean, m.invstd, m.scale, m.shift, p.zero_ptr(m.sums_off), BN_REPLICAS,
+                               0 if m.relu else DV_NO_RELU_MASK)
+        if self.bn_fuse_tap:
+            ws = p.bn_fuse_ws
+            return [Launch('conv_dgrad', kd + '+bn_reduce', lib.dv_conv3d_dgrad_bn_ws, args + (C.byref(r), ws.data_ptr(), ws.numel() * 4),
+                           nbytes, flops, shp + ' +bn_reduce')]
+        return [Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad_bn, args + (C.byref(r),), nbytes, flops, shp + ' +bn_reduce')]
 
 
 BN_PHASES = ('stats', 'apply', 'red', 'bapply')     # forward statistics and apply, backward reduce and apply: dv_bn_item's blk_*

@@ -61,7 +61,7 @@ def new_act(N, T, H, W, C_, dtype, device, cpitch=None, zero=False):
 
 
 def _p(t):
-    return 0 if t is None else (t.ptr if isinstance(t, Act) else t.data_ptr())
+    return 0 if t is None else t if isinstance(t, int) else (t.ptr if isinstance(t, Act) else t.data_ptr())
 
 
 def conv_desc(dtype, x, y, k, s, p, flags=0):

@@ -327,10 +327,9 @@ class Audit:
 
     # ------------------------------------------------------------------------------------------------------ conv
     def shim(self, op):
-        d = _copy(op.d_in if op.bn_in is not None else op.d)
-        fwd = CT.query_fwd(d)
-        dg = CT.query_dgrad(_copy(op.d_g)) if getattr(op, 'd_g', None) is not None else None
-        wg = CT.query_wgrad(_copy(op.d_w)) if getattr(op, 'd_w', None) is not None else None
+        fwd = CT.query_fwd(_copy(op.d_in))
+        dg = CT.query_dgrad(_copy(op.dgrad_desc())) if op.need_dx else None
+        wg = CT.query_wgrad(_copy(op.d_w)) if self.plan.with_grad else None
         return Shim(self.plan.dtype, fwd, dg, wg)
 
     def conv_bound(self, sh, mode, S, cnt, ref, prop=None):

@@ -5,7 +5,7 @@ check for a change of the planning code that is meant to change no plan.
 
     python tools/plan_dump.py > dump.txt              # the whole matrix (several minutes)
     python tools/plan_dump.py --nets s3dg --anchors   # one net, with the per-plan fusion counts on stderr
-    python tools/plan_dump.py --nets s3dg --args      # with the arguments of the BatchNorm / gate / SyncBatchNorm launches
+    python tools/plan_dump.py --nets s3dg --args      # with the arguments of the BatchNorm / gate / SyncBatchNorm / conv launches
     python tools/plan_dump.py --nets s3dg --args --exchange     # the same plans on the multi-rank path (one gloo rank)
 
 Per plan: every entry of the forward and the backward list (name, kernel, shape, bytes, flops, gradient-arena end), per op its
@@ -40,7 +40,7 @@ SETTINGS = (('default', {}),
             ('no_pair', dict(PAIR_CONVS=False)))
 MODES = (('train_grad', True, False, True), ('train_nograd', True, False, False), ('eval_map', False, True, False))
 OP_FLAGS = ('bn_fuse', 'bn_fuse_tap', 'bn_apply', 'bn_in', 'fused', 'bn_member')
-ARG_PREFIXES = ('bn_', 'gate_', 'syncbn_')
+ARG_PREFIXES = ('bn_', 'gate_', 'syncbn_', 'conv_', 'stem_', 'quantize_')
 # the entries that take a device table of dv_bn_item: position of the pointer (the number of items follows it)
 ITEM_TABLES = dict(dv_bn_stats_multi=0, dv_bn_finalize_multi=0, dv_bn_apply_multi=1, dv_bn_bwd_reduce_multi=1,
                    dv_bn_bwd_apply_multi=1, dv_bn_bwd_reduce_multi_gated=1, dv_bn_bwd_apply_multi_gated=1, dv_gate_mean_bn=1,
