@@ -16,20 +16,13 @@ The launch rules, as csrc/elementwise.hip has them:
 from collections import namedtuple
 
 from dualvar_amd import _lib as L
+from tests.checks import ceil_div, cp8
 
 STATS_WIDE_FROM = 2048          # n_tiles from which the statistics launch runs 1024 threads
 APPLY_CAP, BAPPLY_CAP = 4096, 2048
 BLOCK = 256
 FOLD_GROUP = 32
 BAPPLY_MAX_C = 5120
-
-
-def cp8(c):
-    return (c + 7) & ~7
-
-
-def ceil_div(a, b):
-    return -(-a // b)
 
 
 # the rules above as csrc/elementwise.hip spells them: (text, occurrences), and for a rule that lives in another file of csrc

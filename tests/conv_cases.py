@@ -19,6 +19,8 @@ No torch and no GPU in this file: ctypes and the library's host code only.
 import ctypes as C
 from collections import namedtuple
 
+from tests.checks import cp8
+
 F32, BF16 = 0, 1
 DV_BIAS, DV_RELU, DV_SIGMOID, DV_ACCUM, DV_STATS, DV_W3 = 1, 2, 4, 8, 16, 128
 
@@ -26,10 +28,6 @@ Fwd = namedtuple('Fwd', 'path bm bn kind tap_rows ks rows tiles')
 Dgrad = namedtuple('Dgrad', 'path bm bn kind tap_rows ks w3')
 Wgrad = namedtuple('Wgrad', 'rows cols splits workspace bn_ok')
 Case = namedtuple('Case', 'name N Cin T H W Cout k s p dtype w3 cinp data fwd dgrad wgrad bn_in dgrad_bn_ws')
-
-
-def cp8(c):
-    return (c + 7) & ~7
 
 
 def out_dims(c):

@@ -20,10 +20,10 @@ the plan's own markers: fused_conv / bn_in (BatchNorm on load), fused_pool, gate
 as shipped), fp8 convs, world > 1 exchanges and an unfused gate's in-place backward raise NotImplementedError.
 
 Bounds (u = 2^-24; bf16 store: half a bf16 ulp of |ref| + b, i.e. 2^-8 (|ref| + b)):
-  conv y / dx / dw      gauss_bound of tests/test_conv_float64_gpu.py on the float64 S = sum|terms| and cnt, with the route the
+  conv y / dx / dw      gauss_bound of tests/conv_reference.py on the float64 S = sum|terms| and cnt, with the route the
                         library reports for the op's own descriptor (K-split fold, slab additions, split3 / split3w drop terms)
-  DV_STATS partials     the expressions of _stats_check (same file, restated in stats_partials below)
-  BatchNorm             check_finalized / check_apply / check_reduce / check_bwd_apply of tests/test_batchnorm_multi_gpu.py
+  DV_STATS partials     the expressions of _stats_check (tests/test_conv_float64_gpu.py, restated in stats_partials below)
+  BatchNorm             check_finalized / check_apply / check_reduce / check_bwd_apply of tests/bn_support.py
                         (restated: they take that file's Member objects), eval coefficients as test_eval_chain_against_float64
   pool                  values exact, the stored tap points at an element equal to the maximum; dx: (windows - 1) u sum|gy|
   gate, mean            run_means_and_gates of tests/test_pool_gate_float64_gpu.py; the FC: any order of the K + 1 additions,
@@ -52,16 +52,42 @@ from dualvar_amd.backbone.base import IngestOp
 from dualvar_amd.engine import BNGroupOp, ConvOp, GateGroupOp, MeanOp, PlanGraph, PoolOp, _bufkey
 from tests import bn_cases
 from tests import conv_cases as CT
-from tests.test_batchnorm_multi_gpu import BF16_U, U, bwd_reduce_chain, ceil_div, column_chain, cp8, m2_bound, stats_chain, vec
-from tests.test_conv_float64_gpu import e_exp, gamma, gauss_bound, ref_dgrad, ref_fwd, ref_wgrad
-from tests.test_pool_gate_float64_gpu import ref_pool_bwd, ref_pool_fwd
+from tests.chains import bwd_reduce_chain, column_chain, e_exp, gamma, m2_bound, stats_chain
+from tests.checks import BF16_U, F64, U, ceil_div, cp8, vec
+from tests.conv_reference import gauss_bound, ref_dgrad, ref_fwd, ref_wgrad
+from tests.pool_reference import ref_pool_bwd, ref_pool_fwd
 
-F64 = torch.float64
 MASK_CAP = 1e-4
 Row = namedtuple('Row', 'op kind qty how ratio ok info')
 Shim = namedtuple('Shim', 'dtype fwd dgrad wgrad')           # what gauss_bound reads of a conv_cases.Case
 PoolShim = namedtuple('PoolShim', 'N T H W C k s p')         # what ref_pool_fwd / ref_pool_bwd read of a pool_cases.PoolCase
 RATIOS = {}                                                  # (op kind, quantity, dtype) -> largest err / bound of the process
+# the cases of tests/test_plan_audit_gpu.py and _host.py: net -> (T, H = W) of the SMALL cases
+SMALL = {'s3dg': (8, 64), 'r21d': (1, 32), 'r3d': (1, 32), 'r50': (1, 48), 's3d': (8, 64), 'r2d3d18': (1, 48), 'c3d': (8, 32)}
+NETS = tuple(SMALL)
+# net -> N of the LARGE (8 x 112 x 112, fp32) cases and the counts the plan must hold there
+LARGE = {'s3dg': (8, dict(bn_in=1, bn_wgrad=1, pool=2, gate=9, pair_fwd_sp=1, pair_fwd_tm=1, pair_dgrad=1, pair_ks=20)),
+         'r21d': (3, dict(bn_in=1, bn_wgrad=1, pool=0, gate=0, pair_fwd_sp=0, pair_fwd_tm=0, pair_dgrad=0, pair_ks=0))}
+
+
+def fusion_counts(plan):
+    """how many of each fusion and pairing a plan holds"""
+    c = dict(bn_in=0, bn_wgrad=0, pool=0, gate=0, pair_fwd_sp=0, pair_fwd_tm=0, pair_dgrad=0, pair_ks=0)
+    for op in plan.ops:
+        if isinstance(op, ConvOp):
+            c['bn_in'] += op.bn_in is not None
+            c['bn_wgrad'] += op.bn_apply is not None
+        elif isinstance(op, PoolOp):
+            c['pool'] += op.bn_member is not None
+        elif isinstance(op, GateGroupOp):
+            c['gate'] += bool(op.fused)
+    for l in plan.f_list + plan.b_list:
+        if getattr(l, 'members', ()):
+            key = ('pair_ks' if 'conv_gemm_ks' in l.kname else 'pair_dgrad' if l.name == 'conv_dgrad'
+                   else 'pair_fwd_sp' if ',sp,' in l.kname else 'pair_fwd_tm' if ',tm,' in l.kname else None)
+            assert key is not None, l.kname
+            c[key] += 1
+    return c
 
 
 def capture(model):
@@ -152,7 +178,7 @@ class Audit:
         x = self.act(m.x)
         sc, sh = self.load(m.scale)[:m.C], self.load(m.shift)[:m.C]
         y = x * sc + sh
-        b = 3 * U * ((x * sc).abs() + sh.abs())              # check_apply, tests/test_batchnorm_multi_gpu.py:424-427
+        b = 3 * U * ((x * sc).abs() + sh.abs())              # check_apply, tests/bn_support.py
         if m.relu:
             y = y.clamp_min(0)
         if self.su:
@@ -256,7 +282,7 @@ class Audit:
         p[2] += 1
         if self.mode == 'audit':
             own = bound + self.su * (ref.abs() + bound)      # the writer's own result, rounded to storage (bf16: the `+=` forms
-            if p[0] is None:                                 # round(round(new) + old), tests/test_conv_float64_gpu.py:598-601)
+            if p[0] is None:                                 # round(round(new) + old): test_conv_dgrad's accumulate case)
                 p[0], p[1] = ref, own
             else:
                 tot, b = p[0] + ref, p[1] + own
@@ -370,7 +396,7 @@ class Audit:
             self.stats_partials(op, sh.fwd)
 
     def stats_partials(self, op, route):
-        """the DV_STATS partials against float64 of the values AS STORED: _stats_check, tests/test_conv_float64_gpu.py:493-526"""
+        """the DV_STATS partials against float64 of the values AS STORED: _stats_check, tests/test_conv_float64_gpu.py"""
         y = self.act(op.y)
         dev = y.device
         M, Co = op.y.rows, op.y.C
@@ -428,7 +454,7 @@ class Audit:
             da = dy.abs() if bdy is None else dy.abs() + bdy
             S = ref_wgrad(xa, da, op.k, op.s, op.p)
             cnt = ref_wgrad((xa != 0).double(), (da != 0).double(), op.k, op.s, op.p)
-            b = self.conv_bound(sh, 'wgrad', S, cnt, ref) + U * (ref + old).abs()     # tests/test_conv_float64_gpu.py:622
+            b = self.conv_bound(sh, 'wgrad', S, cnt, ref) + U * (ref + old).abs()     # test_conv_wgrad, tests/test_conv_float64_gpu.py
             if bx is not None:
                 b = b + ref_wgrad(bx, dy.abs(), op.k, op.s, op.p)
             if bdy is not None:
@@ -479,7 +505,7 @@ class Audit:
             if m.relu:
                 ref = ref.clamp_min(0)
             terms = (x * sc).abs() + sh.abs() + (res.abs() if res is not None else 0)
-            b = 3 * U * terms                                  # check_apply, tests/test_batchnorm_multi_gpu.py:416-428
+            b = 3 * U * terms                                  # check_apply, tests/bn_support.py
             if self.su:
                 b = b * (1 + BF16_U) + BF16_U * ref.abs()
             snap = self.snaps.get(id(self.gate_of(m.y)))
@@ -500,7 +526,7 @@ class Audit:
 
     def bn_stats(self, op, m, tag, info):
         """mean / invstd / scale / shift / running statistics from the stored partials: stats_reference and check_finalized,
-        tests/test_batchnorm_multi_gpu.py:350-394"""
+        check_finalized and stats_reference, tests/bn_support.py"""
         bn, Cn, M = m.bn, m.C, m.M
         gam, bet = self.vecp(bn.weight), self.vecp(bn.bias)
         eps = float(torch.tensor(float(bn.eps), dtype=torch.float32))     # (the C ABI takes eps and momentum as fp32 numbers)
@@ -554,7 +580,7 @@ class Audit:
         rm_ref = (1 - mom) * rm0 + mom * mean
         brm = 4 * U * ((1 - mom) * rm0.abs() + mom * mean.abs()) + mom * dmean
         if m.conv_bias is not None:              # running_mean += momentum * b, one addcmul behind the finalize: its three roundings
-            cb = self.vecp(m.conv_bias)          # (dadd, tests/test_batchnorm_single_gpu.py:544)
+            cb = self.vecp(m.conv_bias)          # (dadd of test_eval_chain_against_float64, tests/test_batchnorm_single_gpu.py)
             brm = brm + 3 * U * (rm_ref.abs() + brm + (mom * cb).abs())
             rm_ref = rm_ref + mom * cb
         rv_ref = (1 - mom) * rv0 + mom * unb
@@ -563,7 +589,7 @@ class Audit:
         self.check(op, tag + 'running_var', lambda: (bn.running_var, rv_ref, brv), info)
 
     def bn_eval(self, op, m, tag, info):
-        """eval coefficients and the conv-bias fold: test_eval_chain_against_float64, tests/test_batchnorm_single_gpu.py:528-545"""
+        """eval coefficients and the conv-bias fold: test_eval_chain_against_float64, tests/test_batchnorm_single_gpu.py"""
         bn, Cn = m.bn, m.C
         g64, b64 = self.vecp(bn.weight), self.vecp(bn.bias)
         rm, rv = bn.running_mean.double(), bn.running_var.double()
@@ -616,7 +642,7 @@ class Audit:
             x = self.act(m.x).reshape(M, Cn)
             dy = self.act(m.y.grad).reshape(M, Cn)
             bdy = torch.zeros_like(dy)
-            if gop is not None:                  # dy g + dmean / S on load: gate_bwd_apply, tests/test_pool_gate_float64_gpu.py:694-696
+            if gop is not None:                  # dy g + dmean / S on load: gate_bwd_apply, tests/test_pool_gate_float64_gpu.py
                 off, S_ = m.gate[1], gop.cat.S
                 rows = torch.arange(M, device=dy.device) // S_
                 t1 = dy * self.load(gop.g)[:, off:off + Cn][rows]
@@ -654,11 +680,11 @@ class Audit:
                 nblk = int(plan.lib.dv_bn_bwd_blocks(M, Cn))
                 chain = bwd_reduce_chain(M, Cn, plan.dtype, nblk)
                 sums = plan.zero_arena[m.sums_off:m.sums_off + 2 * m.CP].view(2, m.CP)
-                # check_reduce, tests/test_batchnorm_multi_gpu.py:445-456
+                # check_reduce, tests/bn_support.py
                 self.check(op, tag + 'sum_g', lambda: (sums[0, :Cn], sg, chain * U * g.abs().sum(0) + bdy.sum(0) + ud))
                 self.check(op, tag + 'sum_gx', lambda: (sums[1, :Cn], sgx, (chain + 3) * U * (g * xhat).abs().sum(0) + (bdy * xhat.abs()).sum(0) + udx))
                 sgk, sgxk = sums[0, :Cn].double(), sums[1, :Cn].double()
-            # check_bwd_apply, tests/test_batchnorm_multi_gpu.py:470-516, with the sums as stored
+            # check_bwd_apply, tests/bn_support.py, with the sums as stored
             ic = 1.0 / M
             k1 = gam * inv
             k2 = -k1 * inv * sgxk * ic
@@ -761,7 +787,7 @@ class Audit:
 
     # ------------------------------------------------------------------------------------------------------ gate, mean
     def mean_chain(self, N, S, Cn):
-        """column_chain of dv_spatial_mean / dv_gate_bwd_reduce: run_means_and_gates, tests/test_pool_gate_float64_gpu.py:645-648"""
+        """column_chain of dv_spatial_mean / dv_gate_bwd_reduce: run_means_and_gates, tests/test_pool_gate_float64_gpu.py"""
         dt = self.plan.dtype
         CV, chunks = cp8(Cn) // vec(dt), int(self.plan.lib.dv_spatial_chunks(dt, N, S, Cn))
         ccv = ceil_div(CV, chunks)
@@ -800,7 +826,7 @@ class Audit:
             dpre = gamma(w + 1) * (a.abs() @ W.abs().t() + bias.abs())
             sg = torch.sigmoid(pre)
             gref[:, off:off + w] = sg
-            gb[:, off:off + w] = sg * (e_exp(pre) * (1 - sg) + 2 * U) + dpre / 4     # check_desc_result, test_loss_gemm_optim_gpu.py:345
+            gb[:, off:off + w] = sg * (e_exp(pre) * (1 - sg) + 2 * U) + dpre / 4     # check_desc_result, test_loss_gemm_optim_gpu.py
         def t_g():
             if self.mode == 'free':
                 self.load(op.g).copy_(gref)
@@ -846,7 +872,7 @@ class Audit:
             if self.mode == 'free':
                 self.load(op.dpre).copy_(dpre)
                 return None
-            return op.dpre, dpre, (Lc + 1 + 3) * U * prod.abs().sum(1) * (1 - g).abs()   # gate_bwd_reduce, test_pool_gate_float64_gpu.py:681
+            return op.dpre, dpre, (Lc + 1 + 3) * U * prod.abs().sum(1) * (1 - g).abs()   # gate_bwd_reduce, test_pool_gate_float64_gpu.py
         self.check(op, 'dpre', t_dpre)
         dk = self.load(op.dpre)
         dm, dmb = torch.zeros_like(dk), torch.zeros_like(dk)
@@ -882,7 +908,7 @@ class Audit:
             if self.mode == 'free':
                 ga[b0.off:b0.off + Ct] += dk.sum(0)
                 return None
-            # dv_colsum_f32, tests/test_loss_gemm_optim_gpu.py:928
+            # test_colsum_f32, tests/test_loss_gemm_optim_gpu.py
             return ga[b0.off:b0.off + Ct], ob + dk.sum(0), (ceil_div(N, 32) + 2 + 8 + 1) * U * (ob.abs() + dk.abs().sum(0))
         self.check(op, 'db', t_db, binfo)
         self.note(op, 'gated_grad', 'composite via ' + self.label(bn_op))
@@ -911,7 +937,7 @@ class Audit:
             return
         dout = self.dout.double() if self.mode == 'free' else op.dout.double()
         t2 = (dout / x.S)[:, None, :].expand(x.N, x.S, x.C).reshape(x.N, x.T, x.H, x.W, x.C)
-        self.emitg(op, 'x', x, t2, 2 * U * t2.abs())          # spatial_mean_bwd, tests/test_pool_gate_float64_gpu.py:701
+        self.emitg(op, 'x', x, t2, 2 * U * t2.abs())          # spatial_mean_bwd, tests/test_pool_gate_float64_gpu.py
 
 
 def report():

@@ -8,6 +8,7 @@ from collections import namedtuple
 
 from dualvar_amd import _lib as L
 from dualvar_amd._lib import DV_BF16, DV_F32
+from tests.checks import cp8
 
 GATHER, QUAD, TILE = 0, 1, 2
 K333, S1, P1 = (3, 3, 3), (1, 1, 1), (1, 1, 1)
@@ -80,10 +81,6 @@ WRAP_POOLS = {
     'bn_apply_maxpool': _pc('wrap_bnp_311', 1, 2097152 // 4 + 5, 2, 2, 8, (3, 1, 1), S1, (1, 0, 0)),
     'bn_bwd_apply_maxpool': _pc('wrap_bnpb_133', 1, 2200, 8, 15, 8, (1, 3, 3), (1, 2, 2), (0, 1, 1), _G, _Q),
 }
-
-
-def cp8(c):
-    return (c + 7) & ~7
 
 
 def out_dims(c):

@@ -5,23 +5,21 @@ tests/test_ridge_host.py checks it against np.linalg.lstsq on the stacked system
 import numpy as np
 import torch
 
+from tests.checks import ceil_div
+
 MAX_D, MAX_C, SLAB, MAX_SLABS, TILE = 4096, 4096, 512, 8, 64
 LAMBDAS = (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)
 U32 = 2.0 ** -24
 
 
-def cdiv(a, b):
-    return -(-a // b)
-
-
 def slab_cut(n):
     """-> (rows per slab, slabs)"""
-    rows = cdiv(cdiv(n, SLAB), MAX_SLABS) * SLAB
-    return rows, cdiv(n, rows)
+    rows = ceil_div(ceil_div(n, SLAB), MAX_SLABS) * SLAB
+    return rows, ceil_div(n, rows)
 
 
 def gram_workspace_bytes(n, D, C):
-    Da, T = D + 1, cdiv(D + 1, TILE)
+    Da, T = D + 1, ceil_div(D + 1, TILE)
     return 8 * slab_cut(n)[1] * (T * (T + 1) // 2 * TILE * TILE + C * Da)
 
 
@@ -107,8 +105,8 @@ def scores_ref(z, W, video_label, S):
 
 
 def gemm_chain_tile4(K):
-    """the longest chain of fp32 additions of dv_gemm_f32_ex's four-wave kernel (gemm_chain of test_loss_gemm_optim_gpu.py)"""
-    return 16 * cdiv(cdiv(K, 16), 4) + 3
+    """the longest chain of fp32 additions of dv_gemm_f32_ex's four-wave kernel (gemm_chain of tests/chains.py)"""
+    return 16 * ceil_div(ceil_div(K, 16), 4) + 3
 
 
 def score_bound(z, W, S):

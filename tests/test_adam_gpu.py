@@ -40,6 +40,8 @@ Two kinds of data, as in tests/test_loss_gemm_optim_gpu.py:
                                                   a numpy float32 replay of the same operation list gives the same three figures)
       clf.p  0.994  clf.m  0.910  clf.v  0.792   (optim.Adam on LinearClassifier arenas against torch.optim.Adam in float64)
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -48,81 +50,16 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import ops  # noqa: E402
 from dualvar_amd._lib import DV_BF16, DV_F32  # noqa: E402
+from tests import checks  # noqa: E402
+from tests.checks import F64, U, Ratios, f32, is_sent, report_fixture, sent  # noqa: E402
+from tests.optim_support import _classifier, _fill_grads, arena, check_copy, copy_buffer, rnd  # noqa: E402
 
-U = 2.0 ** -24
-SENT_BITS = 0x7fb12345            # a NaN no kernel produces
-F64 = torch.float64
-RATIO = {}
+RATIO = Ratios()
+within = RATIO.within
+_report = report_fixture(RATIO, 20)
+# bit for bit against float64: the reference must be an fp32 number; + 0.0 on both sides only folds -0 into +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in=torch.float32, signed_zeros=False)
 NS = [1, 3, 4, 5, 1003, 2 ** 20 + 3, 2 ** 21 + 4099]       # the last: 2048 blocks x 256 threads x 4 elements, then a second trip
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    print('\nlargest err / bound per quantity:')
-    for k in sorted(RATIO):
-        print(f'  {k:20s} {RATIO[k]:.3f}')
-
-
-def f32(x):
-    """the fp32 value a C float argument receives"""
-    return float(np.float32(x))
-
-
-def sent(shape, dev, dtype=torch.float32):
-    if dtype == torch.bfloat16:
-        return torch.full(shape, 0x7fb1, dtype=torch.int16, device=dev).view(torch.bfloat16)
-    return torch.full(shape, SENT_BITS, dtype=torch.int32, device=dev).view(torch.float32)
-
-
-def is_sent(t):
-    if t.numel() == 0:
-        return True
-    if t.dtype == torch.bfloat16:
-        return bool((t.contiguous().view(torch.int16) == 0x7fb1).all())
-    return bool((t.contiguous().view(torch.int32) == SENT_BITS).all())
-
-
-def arena(vals64, dtype=torch.float32):
-    n = vals64.numel()
-    t = sent((n + 8,), vals64.device, dtype)
-    t[:n] = vals64.to(dtype)
-    return t
-
-
-def same_bits(got, ref64, what):
-    r32 = ref64.to(torch.float32)
-    assert bool((r32.double() == ref64).all()), f'{what}: the float64 reference is not representable in fp32 (test data)'
-    g = (got.contiguous() + 0.0).view(torch.int32)
-    r = (r32.contiguous() + 0.0).view(torch.int32)
-    bad = g != r
-    assert not bool(bad.any()), (f'{what}: {int(bad.sum())} of {bad.numel()} elements differ from float64; first at '
-                                 f'{bad.nonzero()[0].tolist()}: got {got[bad][0].item()!r} want {r32[bad][0].item()!r}')
-
-
-def within(got, ref64, bound, what, quiet=False):
-    g = got.double()
-    assert bool(torch.isfinite(g).all()), f'{what}: non-finite output'
-    err = (g - ref64).abs()
-    zero = bound == 0
-    assert bool((err[zero] == 0).all()), f'{what}: error where the bound is exactly 0'
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    key = what.split(' ')[0]
-    RATIO[key] = max(RATIO.get(key, 0.0), ratio)
-    if not quiet:
-        print(f'    {what}: max err {float(err.max()):.3e}  err/bound {ratio:.3f}')
-    assert ratio <= 1.0, f'{what}: err / bound = {ratio:.3f}'
-    return ratio
-
-
-def check_copy(copy, p, n, dtype, what):
-    if dtype is None:
-        assert is_sent(copy), what + ': copy = NULL but the copy buffer changed'
-        return
-    want = p[:n].to(dtype)
-    it = torch.int16 if dtype == torch.bfloat16 else torch.int32
-    assert torch.equal(copy[:n].view(it), want.view(it)), what + ': the copy is not the round-to-nearest-even cast of the new value'
-    assert is_sent(copy[n:]), what + ': copy written past n'
 
 
 # ------------------------------------------------------------------------------------------------- the float64 reference
@@ -145,10 +82,6 @@ class Hyper:
     def of_torch(cls, lr, b1, b2, eps, wd, t):
         """torch.optim.Adam on float64 tensors: every hyper-parameter a double"""
         return cls(lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5, 1.0 - b1, b2, 1.0 - b2, eps, wd, 1.0, 3.01 * U, 1.51 * U, U)
-
-
-def rnd(x, prop):
-    return prop + U * (x.abs() + prop)
 
 
 def adam_ref(p, g, m, v, bp, bm, bv, c, exact=False):
@@ -201,17 +134,6 @@ def call_adam(p, g, m, v, n, lr, b1, b2, eps, wd, t, gs, code, cp):
 
 
 # ------------------------------------------------------------------------------------------------------ (A) exact grid
-def copy_buffer(n, copy, dev):
-    """copy case -> (torch dtype or None, DV code, the whole sentinel buffer, the [n + 8] view the entry writes).  'bf16-odd': the
-    view starts one element (2 bytes) past the allocation, so no 8-byte store of four bf16 is possible"""
-    dt = {'bf16': torch.bfloat16, 'bf16-odd': torch.bfloat16, 'f32': torch.float32, 'none': None}[copy]
-    off = 1 if copy == 'bf16-odd' else 0
-    whole = sent((n + 8 + off,), dev, dt or torch.float32)
-    cp = whole[off:]
-    assert cp.data_ptr() % 8 == 2 * off
-    return dt, DV_BF16 if dt == torch.bfloat16 else DV_F32, whole, cp
-
-
 COPY_CASES = [(n, c) for n in NS for c in ('bf16', 'f32', 'none')] + [(n, 'bf16-odd') for n in (5, 1003)]
 
 
@@ -313,26 +235,6 @@ def test_adam_bf16_copy_is_the_cast_of_the_new_value(gpu, n):
 
 
 # ------------------------------------------------------------------------------- optim.Adam on a real model's arenas
-def _classifier(gpu, mode, dtype):
-    from dualvar_amd.model import LinearClassifier
-    torch.manual_seed(0)
-    kw = dict(use_dropout=False) if mode == 'ft' else dict(use_dropout=True, use_l2_norm=True, use_final_bn=True)
-    c = LinearClassifier(num_class=10, network='r3d', **kw)
-    if mode == 'last':
-        for n_, p_ in c.named_parameters():
-            if 'backbone' in n_:
-                p_.requires_grad = False
-    c.set_compute_dtype('fp32' if dtype == DV_F32 else 'bf16')
-    for st in c.stores():
-        st.materialize(gpu, dtype)
-    return c
-
-
-def _fill_grads(params, gen, scale=1e-2):
-    for p in params:
-        p.grad.copy_((torch.randn(p.shape, generator=gen) * scale).to(p.device))
-
-
 @pytest.mark.parametrize('dtype', [DV_F32, DV_BF16])
 @pytest.mark.parametrize('mode', ['ft', 'last'])
 def test_optim_adam_on_classifier_arenas_against_torch(gpu, mode, dtype):

@@ -13,14 +13,9 @@ import pretrain                                     # before oracle.harness puts
 from dualvar_amd.utils import transforms as T
 from dualvar_amd.utils.transforms import (AUG_BRIGHTNESS, AUG_CONTRAST, AUG_GRAY, AUG_HUE, AUG_NONE, AUG_PATCH, AUG_SATURATION,
                                           ClipState, ColorJitter, FrameBatch)
+from tests.dataset_support import _seed
 
 FOUR = (AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE)
-
-
-def _seed(s):
-    random.seed(s)
-    np.random.seed(s)
-    torch.manual_seed(s)
 
 
 def _clip(N=8, crop=112, Hs=128, Ws=171):

@@ -4,9 +4,9 @@ dv_bn_rows_partials_f32, dv_fill_cols_f32) against a plain float64 reference of 
 
 engine.BNGroupOp.launches gives these entries to every lone member: the residual-closing and ReLU-free BatchNorms of the
 ResNets, the stems and separable pairs of S3D-G, every eval-mode layer and the classifier head's BatchNorm1d.  The kernel bodies
-are those of the multi-tensor entries (tests/test_batchnorm_multi_gpu.py, whose Member / View / check_* helpers and sentinel
-discipline this file reuses); what is pinned here is what the single-tensor wrappers decide themselves, at the rows of
-tests/bn_cases.py: 1024-thread statistics from 2048 tiles, reduce grids whose trailing blocks own no rows, the atomic form and
+are those of the multi-tensor entries (tests/test_batchnorm_multi_gpu.py; the Member / check_* helpers of tests/bn_support.py
+and the sentinel discipline of tests/checks.py serve both files); what is pinned here is what the single-tensor wrappers decide
+themselves, at the rows of tests/bn_cases.py: 1024-thread statistics from 2048 tiles, reduce grids whose trailing blocks own no rows, the atomic form and
 its replicas, the second trip of the capped grid-stride loops, the LDS limit of dv_bn_bwd_apply, dv_bn_finalize inside a wider
 gathered row.  Two kinds of data, as in the sibling file:
 
@@ -60,9 +60,10 @@ from dualvar_amd import _lib as L  # noqa: E402
 from dualvar_amd._lib import DV_ACCUM, DV_BF16, DV_F32  # noqa: E402
 from tests import bn_cases as T  # noqa: E402
 from tests import bn_reference as REF  # noqa: E402
-from tests import test_batchnorm_multi_gpu as MU  # noqa: E402
-from tests.test_batchnorm_multi_gpu import (BF16_U, DTYPES, EPS, MOM, U, Member, bits, ceil_div, check_bound, cp8,  # noqa: E402
-                                            f32_sentinel, is_sentinel, launch)
+from tests import bn_support as MU  # noqa: E402
+from tests.bn_support import DTYPES, EPS, MOM, Member  # noqa: E402
+from tests.chains import bwd_reduce_chain, column_chain, m2_bound, stats_chain  # noqa: E402
+from tests.checks import BF16_U, U, ceil_div, chan, cp8, equal_bits, is_sent, launch, sent, vec, within  # noqa: E402
 
 KINDS = [pytest.param(True, id='exact'), pytest.param(False, id='gauss')]
 NAN = float('nan')
@@ -79,18 +80,9 @@ def ratio(what, err, bound):
     return r
 
 
-def bounded(got, ref, bound, what):
-    ratio(what, (got - ref).abs(), bound)
-    check_bound(got, ref, bound, what)
-
-
 def twin(make):
     """two members with the same data: one for each of two launch forms whose outputs are compared bit for bit"""
     return make(), make()
-
-
-def same_bits(a, b, what):
-    assert torch.equal(bits(a), bits(b)), f'{what}: the two forms differ'
 
 
 # ----------------------------------------------------------------------------------------------------------- launches
@@ -163,7 +155,7 @@ def ordered_reduce_twice(m, g, xhat, what):
         bwd_reduce(m, m.sums[k], 1, m.red_ws)
         torch.cuda.synchronize()
         MU.check_ticket_area(m, f'{what} launch {k}')
-    same_bits(m.sums[0], m.sums[1], f'{what}: two ordered reduces')
+    assert equal_bits(m.sums[0], m.sums[1]), f'{what}: two ordered reduces: the two forms differ'
     MU.check_reduce(m, m.sums[0], g, xhat, 0, what)
 
 
@@ -176,8 +168,8 @@ def stats_member(dev, c, exact, seed=5):
 
 
 def fresh_outputs(m, dev):
-    return ({k: f32_sentinel(m.CP, dev) for k in ('mean', 'invstd', 'scale', 'shift')}, MU.chan(m.rm0, m.CP, dev),
-            MU.chan(m.rv0, m.CP, dev))
+    return ({k: sent((m.CP,), dev) for k in ('mean', 'invstd', 'scale', 'shift')}, chan(m.rm0, m.CP, dev),
+            chan(m.rv0, m.CP, dev))
 
 
 @pytest.mark.parametrize('exact', KINDS)
@@ -190,7 +182,7 @@ def test_stats_finalize_against_float64(gpu, case, exact):
     assert T.stats_threads(c.n_tiles) == c.threads
     m = stats_member(gpu, c, exact)
     print(f'\n  {w}: M={m.M} C={m.C} tiles={m.n_tiles} threads={c.threads}')
-    local = f32_sentinel(2 * m.C + 1 + 8, gpu)
+    local = sent((2 * m.C + 1 + 8,), gpu)
     stats_finalize(m, local)
     torch.cuda.synchronize()
     S, M2, dS, dM2, sabs = MU.stats_reference(m, c.threads)
@@ -199,21 +191,21 @@ def test_stats_finalize_against_float64(gpu, case, exact):
     if not exact:
         ratio(f'{w} S', (row[:m.C] - S).abs(), dS)
     ratio(f'{w} M2', (row[m.C:] - M2).abs(), dM2)
-    assert is_sentinel(local[2 * m.C + 1:], DV_F32), f'{w}: wrote behind the local row'
-    assert all(is_sentinel(t[m.C:], DV_F32) for t in m.o.values()), f'{w}: outputs past C'
+    assert is_sent(local[2 * m.C + 1:]), f'{w}: wrote behind the local row'
+    assert all(is_sent(t[m.C:]) for t in m.o.values()), f'{w}: outputs past C'
     assert bool((m.rm[m.C:] == 0.625).all()) and bool((m.rv[m.C:] == 0.625).all()), f'{w}: running statistics past C'
     MU.check_finalized(m, m.o, S, M2, m.M, dS, dM2, m.rm, m.rv, w)
     # the exchange form: reduce_stats, then finalize over the one row
-    local2 = f32_sentinel(2 * m.C + 1 + 8, gpu)
+    local2 = sent((2 * m.C + 1 + 8,), gpu)
     o2, rm2, rv2 = fresh_outputs(m, gpu)
     launch('dv_bn_reduce_stats', m.partials_ptr(), m.n_tiles, m.tile_rows, m.pitch, m.M, m.C, local2.data_ptr())
     torch.cuda.synchronize()
-    assert all(is_sentinel(t, DV_F32) for t in o2.values()), f'{w}: reduce_stats wrote the affine map'
+    assert all(is_sent(t) for t in o2.values()), f'{w}: reduce_stats wrote the affine map'
     finalize(local2.data_ptr(), 1, 2 * m.C + 1, m, o2, rm2, rv2)
     torch.cuda.synchronize()
     for a, b, n in [(local, local2, 'local row'), (m.rm, rm2, 'running_mean'), (m.rv, rv2, 'running_var')] + \
                    [(m.o[k], o2[k], k) for k in m.o]:
-        same_bits(a, b, f'{w} stats_finalize vs reduce_stats + finalize: {n}')
+        assert equal_bits(a, b), f'{w} stats_finalize vs reduce_stats + finalize: {n}: the two forms differ'
     if c.threads == 256:                            # the multi-tensor launch always runs 256 threads: the same grid
         m3 = stats_member(gpu, c, exact)
         loc3, _ = MU.group_local([m3], gpu)
@@ -222,7 +214,7 @@ def test_stats_finalize_against_float64(gpu, case, exact):
         torch.cuda.synchronize()
         for a, b, n in [(local[:2 * m.C + 1], loc3, 'local row'), (m.rm, m3.rm, 'running_mean'), (m.rv, m3.rv, 'running_var')] + \
                        [(m.o[k], m3.o[k], k) for k in m.o]:
-            same_bits(a, b, f'{w} single vs multi: {n}')
+            assert equal_bits(a, b), f'{w} single vs multi: {n}: the two forms differ'
 
 
 # ----------------------------------------------------------------------------------------------------------- finalize
@@ -236,7 +228,7 @@ def finalize_bounds(S_r, Q_r, n_r, dS_r=None, dQ_r=None):
     n = n_r.double()[:, None]
     dS = dS_r.sum(0) + R * U * (S_r.abs() + dS_r).sum(0)
     a = S_r / n
-    dM2 = MU.m2_bound(n, dS_r / n + U * a.abs(), a - mean, Q_r, dQ_r, dS / cnt + U * mean.abs(), R)
+    dM2 = m2_bound(n, dS_r / n + U * a.abs(), a - mean, Q_r, dQ_r, dS / cnt + U * mean.abs(), R)
     return cnt, S, M2, dS, dM2
 
 
@@ -263,8 +255,8 @@ def test_finalize_against_float64(gpu, case):
                                  'beta': 0.1 * torch.randn(C_, generator=gen, device=gpu)},
                         rm0=torch.randint(-8, 9, (C_,), generator=gen, device=gpu).float() / 8,
                         rv0=0.5 + torch.randint(0, 9, (C_,), generator=gen, device=gpu).float() / 8)
-    out = {k: f32_sentinel(C_ + 8, gpu) for k in ('mean', 'invstd', 'scale', 'shift')}
-    rm, rv = (MU.chan(m.rm0, C_ + 8, gpu), MU.chan(m.rv0, C_ + 8, gpu)) if c.running else (None, None)
+    out = {k: sent((C_ + 8,), gpu) for k in ('mean', 'invstd', 'scale', 'shift')}
+    rm, rv = (chan(m.rm0, C_ + 8, gpu), chan(m.rv0, C_ + 8, gpu)) if c.running else (None, None)
     finalize(table.data_ptr() + 4 * c.base, R, stride, m, out, rm, rv)
     torch.cuda.synchronize()
     cnt, S, M2, dS, dM2 = finalize_bounds(S_r.double(), Q_r.double(), n_r)
@@ -272,7 +264,7 @@ def test_finalize_against_float64(gpu, case):
     print(f'\n  {w}: R={R} C={C_} stride={stride} base={c.base}')
     MU.check_finalized(m, out, S, M2, cnt, dS, dM2, rm, rv, w)
     ratio(f'{w} mean', (out['mean'][:C_].double() - S / cnt).abs(), dS / cnt + U * (S / cnt).abs())
-    assert all(is_sentinel(t[C_:], DV_F32) for t in out.values()), f'{w}: outputs past C'
+    assert all(is_sent(t[C_:]) for t in out.values()), f'{w}: outputs past C'
     if c.running:
         assert bool((rm[C_:] == 0.625).all()) and bool((rv[C_:] == 0.625).all()), f'{w}: running statistics past C'
 
@@ -289,7 +281,7 @@ def test_apply_against_float64(gpu, dtype, case, exact):
     """dv_bn_apply (y bit for bit with exact data; the over-cap row takes a second grid-stride trip in both dtypes), and a
     one-member dv_bn_apply_multi gives the same bits"""
     c, w = case, f'apply {case.name}'
-    v = MU.vec(dtype)
+    v = vec(dtype)
     assert T.stride_trip(c.M, c.C, v, T.APPLY_CAP) == (c.trip[v == 8], c.wraps[v == 8])
     m, m2 = twin(lambda: apply_member(gpu, dtype, c, exact))
     apply(m)
@@ -299,7 +291,7 @@ def test_apply_against_float64(gpu, dtype, case, exact):
     assert ends['apply'] * 256 == c.trip[v == 8]
     launch('dv_bn_apply_multi', dtype, tab.data_ptr(), 1, ends['apply'])
     torch.cuda.synchronize()
-    same_bits(m.y.buf, m2.y.buf, f'{w} single vs multi: y')
+    assert equal_bits(m.y.buf, m2.y.buf), f'{w} single vs multi: y: the two forms differ'
 
 
 # ----------------------------------------------------------------------------------------------------------- backward
@@ -312,7 +304,7 @@ def atomic_chain(c, dtype):
     """longest chain of fp32 additions behind one value of a replica: column_chain over the rows of one block, then the float
     atomics of the ceil(blocks / n_rep) blocks that bid % n_rep sends there"""
     blocks, rpb = c.red[0], c.red[1]
-    return MU.column_chain(rpb, cp8(c.C), dtype, 2, ceil_div(blocks, c.n_rep))
+    return column_chain(rpb, cp8(c.C), dtype, 2, ceil_div(blocks, c.n_rep))
 
 
 def check_atomic(m, c, rep, g, xhat, what):
@@ -326,14 +318,14 @@ def check_atomic(m, c, rep, g, xhat, what):
     sg, sgx = zero.clone().index_add_(0, owner, g), zero.clone().index_add_(0, owner, gx)
     ag, agx = zero.clone().index_add_(0, owner, g.abs()), zero.clone().index_add_(0, owner, gx.abs())
     r = rep.view(n_rep + 1, 2, CP)
-    assert is_sentinel(r[n_rep], DV_F32) and is_sentinel(r[:n_rep, :, C_:], DV_F32), f'{what}: wrote outside its replicas'
+    assert is_sent(r[n_rep]) and is_sent(r[:n_rep, :, C_:]), f'{what}: wrote outside its replicas'
     got_g, got_gx = r[:n_rep, 0, :C_].double(), r[:n_rep, 1, :C_].double()
     chain = atomic_chain(c, m.dtype)
     if m.exact:
         assert torch.equal(got_g, sg) and torch.equal(got_gx, sgx), f'{what}: a replica is not the exact sum of its blocks'
         assert torch.equal(got_g.sum(0), g.sum(0)) and torch.equal(got_gx.sum(0), gx.sum(0)), f'{what}: replicas do not add up'
-    check_bound(got_g, sg, chain * U * ag, f'{what} replica sum g')
-    check_bound(got_gx, sgx, (chain + 3) * U * agx, f'{what} replica sum g*xhat')
+    within(got_g, sg, chain * U * ag, f'{what} replica sum g', quiet=True)
+    within(got_gx, sgx, (chain + 3) * U * agx, f'{what} replica sum g*xhat', quiet=True)
     if not m.exact:
         ratio(f'{what} sum g (L={chain})', (got_g - sg).abs(), chain * U * ag)
         ratio(f'{what} sum g*xhat', (got_gx - sgx).abs(), (chain + 3) * U * agx)
@@ -360,12 +352,12 @@ def test_backward_against_float64(gpu, dtype, case, exact):
     ordered_reduce_twice(m, g, xhat, f'{w} ordered')
     rep = torch.zeros((c.n_rep + 1) * 2 * m.CP, dtype=torch.float32, device=gpu)
     r = rep.view(c.n_rep + 1, 2, m.CP)
-    r[c.n_rep] = f32_sentinel(2 * m.CP, gpu).view(2, m.CP)
-    r[:c.n_rep, :, m.C:] = f32_sentinel(c.n_rep * 2 * (m.CP - m.C), gpu).view(c.n_rep, 2, m.CP - m.C)
+    r[c.n_rep] = sent((2 * m.CP,), gpu).view(2, m.CP)
+    r[:c.n_rep, :, m.C:] = sent((c.n_rep * 2 * (m.CP - m.C),), gpu).view(c.n_rep, 2, m.CP - m.C)
     bwd_reduce(m, rep, c.n_rep, None)
     torch.cuda.synchronize()
     total, dsums = check_atomic(m, c, rep, g, xhat, f'{w} atomic')
-    v = MU.vec(dtype)
+    v = vec(dtype)
     assert T.stride_trip(c.M, c.C, v, T.BAPPLY_CAP) == (c.bapply[0][v == 8], c.bapply[1][v == 8])
     inv_count = 1.0 / (c.R * c.M)
     if c.n_rep > 1:
@@ -403,7 +395,7 @@ def test_backward_single_equals_multi(gpu, dtype, case):
     if a.dres:
         pairs.append((a.dres.buf, b.dres.buf, 'dres'))
     for x, y, n in pairs:
-        same_bits(x, y, f'{w}: {n}')
+        assert equal_bits(x, y), f'{w}: {n}: the two forms differ'
     assert not bool(torch.isnan(a.dx.val()).any())
 
 
@@ -421,7 +413,7 @@ def test_train_chain_against_float64(gpu, dtype, M, C_, tile_rows):
     m = Member(gpu, dtype, M, C_, 23, exact=False, relu=True, res=True, accum=True, views=True, tile_rows=tile_rows)
     threads = T.stats_threads(m.n_tiles)
     print(f'\n  {w}: tiles={m.n_tiles} threads={threads}')
-    local = f32_sentinel(2 * C_ + 1, gpu)
+    local = sent((2 * C_ + 1,), gpu)
     stats_finalize(m, local)
     torch.cuda.synchronize()
     # float64 of x itself: the partials the member stores are float64 tile sums rounded once
@@ -430,15 +422,15 @@ def test_train_chain_against_float64(gpu, dtype, M, C_, tile_rows):
     mean = S / M
     M2 = ((x - mean) ** 2).sum(0)
     ps, pq, n = m.ps(), m.pq(), m.tile_n[:, None]
-    chain = MU.stats_chain(m.n_tiles, threads)
+    chain = stats_chain(m.n_tiles, threads)
     dps = U * ps.abs()
     dS = dps.sum(0) + chain * U * ps.abs().sum(0)
     a = ps / n
-    dM2 = MU.m2_bound(n, dps / n + U * a.abs(), a - mean, pq, U * pq, dS / M + U * mean.abs(), chain)
+    dM2 = m2_bound(n, dps / n + U * a.abs(), a - mean, pq, U * pq, dS / M + U * mean.abs(), chain)
     row = local.double()
     assert float(row[2 * C_]) == M
-    bounded(row[:C_], S, dS, f'{w} S')
-    bounded(row[C_:2 * C_], M2, dM2, f'{w} M2')
+    within(row[:C_], S, dS, f'{w} S')
+    within(row[C_:2 * C_], M2, dM2, f'{w} M2')
     MU.check_finalized(m, m.o, S, M2, M, dS, dM2, m.rm, m.rv, w)
     adopt(m, m.o)
     g, xhat = forward_for_backward(m, w)
@@ -494,11 +486,11 @@ def test_reduce_stats_then_finalize_is_syncbn(gpu, dtype):
     total = ranks[0].sums[0] + ranks[1].sums[0] + ranks[2].sums[0]                 # the all-reduce, fp32
     g_all = torch.cat([g for g, _ in gx])
     gx_all = torch.cat([g * xh for g, xh in gx])
-    chain = max(MU.bwd_reduce_chain(m.M, C_, dtype, MU.n_blocks(L.load(), 'red', m.M, C_, dtype)) for m in ranks) + R
+    chain = max(bwd_reduce_chain(m.M, C_, dtype, MU.n_blocks(L.load(), 'red', m.M, C_, dtype)) for m in ranks) + R
     t = total.double()
     CP = cp8(C_)
-    bounded(t[:C_], g_all.sum(0), chain * U * g_all.abs().sum(0), 'syncbn sum g')
-    bounded(t[CP:CP + C_], gx_all.sum(0), (chain + 3) * U * gx_all.abs().sum(0), 'syncbn sum g*xhat')
+    within(t[:C_], g_all.sum(0), chain * U * g_all.abs().sum(0), 'syncbn sum g')
+    within(t[CP:CP + C_], gx_all.sum(0), (chain + 3) * U * gx_all.abs().sum(0), 'syncbn sum g*xhat')
     for r, m in enumerate(ranks):
         bwd_apply(m, total, 1, 1.0 / cnt)
     torch.cuda.synchronize()
@@ -519,12 +511,12 @@ def test_eval_chain_against_float64(gpu, dtype, C_):
     rm, rv = m.rm0.clone(), m.rv0.clone()
     rv[::4] = 0
     gamma, beta = m.p['gamma'][:C_].clone(), m.p['beta'][:C_].clone()                # (exactly C floats: nothing behind is read)
-    scale, shift = f32_sentinel(CP + 8, gpu), f32_sentinel(CP + 8, gpu)
+    scale, shift = sent((CP + 8,), gpu), sent((CP + 8,), gpu)
     launch('dv_bn_eval_coeffs', gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(), rv.data_ptr(), EPS, C_, scale.data_ptr(),
            shift.data_ptr())
     torch.cuda.synchronize()
     for t in (scale, shift):
-        assert bool((t[C_:CP] == 0).all()) and is_sentinel(t[CP:], DV_F32), f'{w}: pad lanes / behind CP'
+        assert bool((t[C_:CP] == 0).all()) and is_sent(t[CP:]), f'{w}: pad lanes / behind CP'
     g64, b64, rm64, rv64, bias64 = (t.double() for t in (gamma, beta, rm, rv, b))
     eps = float(torch.tensor(EPS, dtype=torch.float32))
     inv = (rv64 + eps).rsqrt()
@@ -534,15 +526,15 @@ def test_eval_chain_against_float64(gpu, dtype, C_):
     sh = b64 - rm64 * sc
     dsh = (rm64.abs() * dsc + U * (rm64 * sc).abs() + U * sh.abs()) * (1 + 2 * U)
     print(f'\n  {w}')
-    bounded(scale[:C_].double(), sc, dsc, f'{w} scale')
-    bounded(shift[:C_].double(), sh, dsh, f'{w} shift')
+    within(scale[:C_].double(), sc, dsc, f'{w} scale')
+    within(shift[:C_].double(), sh, dsh, f'{w} shift')
     sc_k, sh_k = scale[:C_].double(), shift[:C_].double()                           # as stored
     launch('dv_addcmul_f32', shift.data_ptr(), scale.data_ptr(), b.data_ptr(), 1.0, C_)
     torch.cuda.synchronize()
-    assert bool((shift[C_:CP] == 0).all()) and is_sentinel(shift[CP:], DV_F32), f'{w}: addcmul wrote past n'
+    assert bool((shift[C_:CP] == 0).all()) and is_sent(shift[CP:]), f'{w}: addcmul wrote past n'
     shp = sh_k + sc_k * bias64
     dadd = 3 * U * (sh_k.abs() + (sc_k * bias64).abs())
-    bounded(shift[:C_].double(), shp, dadd, f'{w} shift + scale * bias')
+    within(shift[:C_].double(), shp, dadd, f'{w} shift + scale * bias')
     # apply, against float64 of the stored coefficients ...
     m.scale, m.shift = sc_k, shift[:C_].double()
     apply(m, scale, shift)
@@ -556,7 +548,7 @@ def test_eval_chain_against_float64(gpu, dtype, C_):
     bound = x.abs() * dsc + dshp + 3 * U * (x.abs() * (sc.abs() + dsc) + (sh + bias64 * sc).abs() + dshp)
     if dtype == DV_BF16:
         bound = bound * (1 + BF16_U) + BF16_U * ref.abs()
-    bounded(m.y.val(), ref, bound, f'{w} y against the float64 layer')
+    within(m.y.val(), ref, bound, f'{w} y against the float64 layer')
 
 
 @pytest.mark.parametrize('n', [1, 255, 256, 257, 2048])
@@ -571,18 +563,18 @@ def test_addcmul_bias_fixup(gpu, n):
             alpha = 0.5
         else:
             y0, a, alpha = torch.randn(n, generator=gen, device=gpu), torch.randn(n, generator=gen, device=gpu), MOM
-        y = f32_sentinel(n + 8, gpu)
+        y = sent((n + 8,), gpu)
         y[:n] = y0
         launch('dv_addcmul_f32', y.data_ptr(), a.data_ptr(), 0, alpha, n)
         torch.cuda.synchronize()
-        assert is_sentinel(y[n:], DV_F32), 'addcmul wrote past n'
+        assert is_sent(y[n:]), 'addcmul wrote past n'
         al = float(torch.tensor(alpha, dtype=torch.float32))
         ref = y0.double() + al * a.double()
         if exact:
             assert torch.equal(y[:n].double(), ref)
         else:
             print()
-            bounded(y[:n].double(), ref, 3 * U * (y0.double().abs() + (al * a.double()).abs()), f'addcmul n={n}')
+            within(y[:n].double(), ref, 3 * U * (y0.double().abs() + (al * a.double()).abs()), f'addcmul n={n}')
 
 
 HEAD = [(c.tile_rows, c.C) for c in T.STATS_CASES if c.name.startswith('bn1d')]
@@ -596,29 +588,29 @@ def test_head_batchnorm1d_chain(gpu, M, C_):
     w = f'head M={M} C={C_}'
     m = Member(gpu, DV_F32, M, C_, 71, exact=False, relu=False, views=True, tile_rows=M)
     assert m.n_tiles == 1 and m.x.ld > C_
-    part = f32_sentinel(2 * C_ + 8, gpu)
+    part = sent((2 * C_ + 8,), gpu)
     launch('dv_bn_rows_partials_f32', m.x.ptr, m.x.ld, M, C_, part.data_ptr())
     torch.cuda.synchronize()
-    assert is_sentinel(part[2 * C_:], DV_F32), f'{w}: partials past [2][C]'
+    assert is_sent(part[2 * C_:]), f'{w}: partials past [2][C]'
     x = m.x.val()
     ref = REF.bn1d_reference(x, m.gamma, m.beta, m.rm0.double(), m.rv0.double(), m.dy.val(), EPS, MOM)
     S, M2 = ref['S'], ref['M2']
     mean = S / M
     dps = M * U * x.abs().sum(0)                                                   # M sequential additions
     ones = torch.ones((M, 1), dtype=torch.float64, device=gpu)
-    dpq = MU.m2_bound(ones, torch.zeros_like(x), x - mean, torch.zeros_like(x), torch.zeros_like(x), dps / M + U * mean.abs(), M)
+    dpq = m2_bound(ones, torch.zeros_like(x), x - mean, torch.zeros_like(x), torch.zeros_like(x), dps / M + U * mean.abs(), M)
     print(f'\n  {w}')
-    bounded(part[:C_].double(), S, dps, f'{w} partial sums')
-    bounded(part[C_:2 * C_].double(), M2, dpq, f'{w} partial M2')
+    within(part[:C_].double(), S, dps, f'{w} partial sums')
+    within(part[C_:2 * C_].double(), M2, dpq, f'{w} partial M2')
     m.part, m.coff, m.pitch = part[:2 * C_].view(2, C_, 1), 0, C_
-    local = f32_sentinel(2 * C_ + 1, gpu)
+    local = sent((2 * C_ + 1,), gpu)
     stats_finalize(m, local)
     torch.cuda.synchronize()
-    chain = MU.stats_chain(1)
+    chain = stats_chain(1)
     dS = dps + chain * U * (S.abs() + dps)
     n1 = torch.full((1, 1), float(M), dtype=torch.float64, device=gpu)
     a = m.ps() / M
-    dM2 = MU.m2_bound(n1, dps[None] / M + U * a.abs(), a - mean, m.pq(), dpq[None], dS / M + U * mean.abs(), chain)
+    dM2 = m2_bound(n1, dps[None] / M + U * a.abs(), a - mean, m.pq(), dpq[None], dS / M + U * mean.abs(), chain)
     MU.check_finalized(m, m.o, S, M2, M, dS, dM2, m.rm, m.rv, w)
     adopt(m, m.o)
     g, xhat = forward_for_backward(m, w)
@@ -635,11 +627,11 @@ FILL = [(1, 1, 1, 0), (51, 5, 9, 4), (257, 1, 3, 0), (85, 3, 3, 0), (300000, 4, 
 def test_fill_cols(gpu, rows, ncols, pitch, col0):
     """dv_fill_cols_f32: only columns [col0, col0 + ncols) of a sentinel [rows][pitch] buffer change (rows * ncols = 1, 255,
     257, and past one trip of the 4096-block grid; col0 = 0 and col0 + ncols = pitch included)"""
-    buf = f32_sentinel(rows * pitch + 8, gpu)
+    buf = sent((rows * pitch + 8,), gpu)
     launch('dv_fill_cols_f32', buf.data_ptr(), rows, pitch, col0, ncols, -1.25)
     torch.cuda.synchronize()
     v = buf[:rows * pitch].view(rows, pitch)
     assert bool((v[:, col0:col0 + ncols] == -1.25).all()), 'a column of the range was not filled'
-    assert is_sentinel(v[:, :col0], DV_F32) and is_sentinel(v[:, col0 + ncols:], DV_F32) and is_sentinel(buf[rows * pitch:], DV_F32)
+    assert is_sent(v[:, :col0]) and is_sent(v[:, col0 + ncols:]) and is_sent(buf[rows * pitch:])
     if rows == 300000:
         assert rows * ncols > 4096 * 256

@@ -17,8 +17,6 @@ import json
 import os
 import pickle
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -31,7 +29,8 @@ import classifier as CLI
 from dualvar_amd import ops
 from dualvar_amd.ops import DV_F32
 from dualvar_amd.utils import finetune_dataset as FD
-from tests.test_frame_dataset_host import _seed, write_dataset
+from tests.checks import child as _child
+from tests.dataset_support import _seed, write_dataset
 from tests.util import CLIP, gold
 
 pytestmark = pytest.mark.gpu
@@ -242,17 +241,6 @@ def test_validate_and_summaries_equal_torch(gpu, tmp_path, monkeypatch):
 STATE = {}
 COMMON = ['--net', 'r3d', '--seq_len', '8', '--img_dim', '64', '--img_resize_dim', '72', '--ds', '2', '--batch_size', '4', '-j', '2',
           '--print_freq', '1']
-
-
-def _child(argv, cwd, timeout):
-    """one GPU child process under its own timeout; a failure marks the chain as broken"""
-    assert not STATE.get('broken'), 'an earlier child failed or died: no further GPU child is started'
-    STATE['broken'] = True
-    r = subprocess.run([sys.executable] + argv, capture_output=True, text=True, timeout=timeout, cwd=cwd)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    STATE['broken'] = False
-    return out
 
 
 def _data(tmp):

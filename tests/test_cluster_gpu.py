@@ -30,41 +30,16 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib, ops  # noqa: E402
 from tests import cluster_reference as R  # noqa: E402
-from tests.test_loss_gemm_optim_gpu import U, gemm_chain, is_sent, sent  # noqa: E402
+from tests.chains import gemm_chain  # noqa: E402
+from tests.checks import U, Ratios, bits, is_sent, lib, report_fixture, sent  # noqa: E402
+from tests.dataset_support import write_dataset  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E52 = 2.0 ** -52
-WORST = {}
+WORST = Ratios()
+ratio = WORST.ratio
+_report_worst = report_fixture(WORST, 28)
 NAN, INF = float('nan'), float('inf')
-
-
-def lib():
-    return _lib.load()
-
-
-def ratio(err, bound, what):
-    """largest err / bound over the elements; where the bound is 0 the error must be 0"""
-    err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
-    assert np.isfinite(err).all(), what + ': non-finite output'
-    zero = bound == 0
-    assert (err[zero] == 0).all(), what + ': error where the bound is exactly 0'
-    r = float((err[~zero] / bound[~zero]).max()) if (~zero).any() else 0.0
-    key = what.split(' ')[0]
-    WORST[key] = max(WORST.get(key, 0.0), r)
-    assert r <= 1.0, '%s: err / bound = %.3f' % (what, r)
-    return r
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _report_worst():
-    yield
-    print('\nlargest err / bound per quantity:')
-    for k in sorted(WORST):
-        print('  %-28s %.3f' % (k, WORST[k]))
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int64)
 
 
 # --------------------------------------------------------------------------------------------------------------- assign
@@ -381,7 +356,6 @@ def test_fit_with_seven_clusters_on_six_groups(gpu):
 # ------------------------------------------------------------------------------------------------------- the driver, one child
 def test_cli_retrieval_with_cluster(gpu, tmp_path_factory):
     from dualvar_amd.utils.cluster import cluster_eval
-    from tests.test_frame_dataset_host import write_dataset
     d = tmp_path_factory.mktemp('cluster_cli')
     split, frame = write_dataset(str(d / 'data'), videos=((0, 40), (0, 9), (1, 70)), rows=830, sizes=[(90, 120), (120, 90), (80, 100)])
     os.makedirs(str(d / 'run' / 'model'))

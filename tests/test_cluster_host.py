@@ -21,6 +21,7 @@ import torch
 
 from tests import abi_coverage as A
 from tests import cluster_reference as R
+from tests.checks import lib
 from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,11 +38,6 @@ CLUSTER_COVERAGE = {
     'dv_kmeans_seed_workspace': ('test_cluster_host.py', A.HOST_QUERY),
     'dv_kmeans_seed_f32': ('test_cluster_gpu.py', A.FLOAT64),
 }
-
-
-def lib():
-    from dualvar_amd import _lib
-    return _lib.load()
 
 
 def test_cluster_header_table_and_library_agree():

@@ -1,7 +1,7 @@
 """The convolution kernels (csrc/conv.hip, conv_tap.hip, conv_tap_wgrad.hip) against a float64 reference, on the route
 each row of tests/conv_cases.py names.  Every entry is called through the C ABI / dualvar_amd.ops on explicit tensors.
 
-Reference: a plain float64 convolution written here (`ref_fwd`, `ref_dgrad`, `ref_wgrad`): a loop over the kernel taps, each
+Reference: a plain float64 convolution (`ref_fwd`, `ref_dgrad`, `ref_wgrad` of tests/conv_reference.py): a loop over the kernel taps, each
 a shifted, zero-padded, strided slice of the NDHWC input times the [Cin, Cout] weight slice, summed in float64 on the GPU by
 torch; the same loop over |x|, |w| gives S = sum|terms| per element and over ones the number of terms `cnt`.  Three small
 cases check it against torch.nn.functional.conv3d / autograd in float64 on the CPU.  It never calls the library under test.
@@ -61,6 +61,7 @@ The measured figures (largest err / bound per quantity and route, the rms figure
 DESIGN.md section 2.
 """
 import ctypes as C
+import functools
 
 import pytest
 import torch
@@ -70,129 +71,33 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib as L, ops  # noqa: E402
 from dualvar_amd._lib import DV_ACCUM, DV_BF16, DV_BIAS, DV_F32, DV_RELU, DV_SIGMOID, DV_STATS, DV_W3  # noqa: E402
+from tests import checks  # noqa: E402
 from tests import conv_cases as T  # noqa: E402
+from tests.chains import e_exp, gamma  # noqa: E402
+from tests.checks import F64, TDT, U, Ratios, dev_gen, is_sent, sent  # noqa: E402
+from tests.conv_reference import gauss_bound, ref_dgrad, ref_fwd, ref_wgrad  # noqa: E402
 
-U = 2.0 ** -24
-SENT_BITS = 0x7fb12345            # a NaN no kernel produces
-F64 = torch.float64
-RATIO = {}                        # quantity -> largest err / bound of the run
+RATIO = Ratios()                  # quantity -> largest err / bound of the run
+within = RATIO.within
+# bit for bit against float64 (bf16: against its round-to-nearest-even bf16): the reference must be an fp32 number; + 0.0 on
+# both sides only folds -0 into +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in=torch.float32, signed_zeros=False)
 RMS = {}                          # quantity -> (kernel rms figure, torch fp32 figure or None)
-TDT = {DV_F32: torch.float32, DV_BF16: torch.bfloat16}
 CPU_REF_MAX_FLOPS = 2.5e10        # torch's fp32 CPU conv is taken where 2 M K Cout stays below this: every fp32 row of the table
-
-
-def e_exp(x):
-    return (4.2 + 4.1 * x.abs()) * U
-
-
-def gamma(n):
-    return n * U / (1 - n * U)
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _report():
     yield
-    print('\nlargest err / bound per quantity:')
-    for k in sorted(RATIO):
-        print(f'  {k:44s} {RATIO[k]:.3f}')
+    RATIO.report(44)
     print('rms(err) / (u rms(ref)):  kernel   torch fp32 (CPU)')
     for k in sorted(RMS):
         a, b = RMS[k]
         print(f'  {k:44s} {a:7.3f}   {"-" if b is None else "%.3f" % b}')
 
 
-# ----------------------------------------------------------------------------------------------------------- helpers
-def sent(shape, dev, dtype=torch.float32):
-    if dtype == torch.bfloat16:
-        return torch.full(shape, 0x7fb1, dtype=torch.int16, device=dev).view(torch.bfloat16)
-    return torch.full(shape, SENT_BITS, dtype=torch.int32, device=dev).view(torch.float32)
-
-
-def is_sent(t):
-    if t.numel() == 0:
-        return True
-    if t.dtype == torch.bfloat16:
-        return bool((t.contiguous().view(torch.int16) == 0x7fb1).all())
-    return bool((t.contiguous().view(torch.int32) == SENT_BITS).all())
-
-
-def same_bits(got, ref64, what):
-    """got equals the float64 reference bit for bit (bf16: the round-to-nearest-even bf16 of it); the reference must itself be
-    an fp32 number"""
-    r32 = ref64.to(torch.float32)
-    assert bool((r32.double() == ref64).all()), f'{what}: the float64 reference is not representable in fp32 (test data)'
-    if got.dtype == torch.bfloat16:
-        g = (got.contiguous() + 0.0).view(torch.int16)
-        r = (r32.to(torch.bfloat16).contiguous() + 0.0).view(torch.int16)
-    else:
-        g = (got.contiguous() + 0.0).view(torch.int32)
-        r = (r32.contiguous() + 0.0).view(torch.int32)
-    bad = g != r
-    assert not bool(bad.any()), (f'{what}: {int(bad.sum())} of {bad.numel()} elements differ from float64; first at '
-                                 f'{bad.nonzero()[0].tolist()}: got {got[bad][0].item()!r} want {r32[bad][0].item()!r}')
-
-
-def within(got, ref64, bound, what):
-    """|got - ref| <= bound elementwise, no element left out; records and prints err / bound"""
-    g = got.double()
-    assert bool(torch.isfinite(g).all()), f'{what}: non-finite output'
-    err = (g - ref64).abs()
-    zero = bound == 0
-    assert bool((err[zero] == 0).all()), f'{what}: error where the bound is exactly 0'
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    key = what.split(' ')[0]
-    RATIO[key] = max(RATIO.get(key, 0.0), ratio)
-    print(f'    {what}: max err {float(err.max()):.3e}  err/bound {ratio:.3f}')
-    assert ratio <= 1.0, f'{what}: err / bound = {ratio:.3f}'
-    return ratio
-
-
 def rms_figure(got64, ref64):
     return float(((got64 - ref64) ** 2).mean().sqrt() / (U * (ref64 ** 2).mean().sqrt()))
-
-
-# ------------------------------------------------------------------------------------------------------ the reference
-def _slices(dims_out, k3, s3, tap):
-    return tuple(slice(d, d + (o - 1) * s + 1, s) for d, o, s in zip(tap, dims_out, s3))
-
-
-def _taps(k3):
-    return [(a, b, c) for a in range(k3[0]) for b in range(k3[1]) for c in range(k3[2])]
-
-
-def ref_fwd(x, w, s3, p3):
-    """x [N,T,H,W,Cin], w [Cout,kt,kh,kw,Cin] float64 -> y [N,To,Ho,Wo,Cout]"""
-    k3 = tuple(w.shape[1:4])
-    xp = F.pad(x, (0, 0, p3[2], p3[2], p3[1], p3[1], p3[0], p3[0]))
-    do = tuple((i + 2 * p - k) // s + 1 for i, k, s, p in zip(x.shape[1:4], k3, s3, p3))
-    y = torch.zeros((x.shape[0],) + do + (w.shape[0],), dtype=F64, device=x.device)
-    for tap in _taps(k3):
-        st, sh, sw = _slices(do, k3, s3, tap)
-        y += xp[:, st, sh, sw, :] @ w[:, tap[0], tap[1], tap[2], :].t()
-    return y
-
-
-def ref_dgrad(dy, w, xdims, s3, p3):
-    """dy [N,To,Ho,Wo,Cout], w as above -> dx [N,T,H,W,Cin]: scatter over the taps"""
-    k3 = tuple(w.shape[1:4])
-    do = tuple(dy.shape[1:4])
-    dxp = torch.zeros((dy.shape[0],) + tuple(i + 2 * p for i, p in zip(xdims, p3)) + (w.shape[4],), dtype=F64, device=dy.device)
-    for tap in _taps(k3):
-        st, sh, sw = _slices(do, k3, s3, tap)
-        dxp[:, st, sh, sw, :] += dy @ w[:, tap[0], tap[1], tap[2], :]
-    return dxp[:, p3[0]:p3[0] + xdims[0], p3[1]:p3[1] + xdims[1], p3[2]:p3[2] + xdims[2], :].contiguous()
-
-
-def ref_wgrad(x, dy, k3, s3, p3):
-    """-> dw [Cout,kt,kh,kw,Cin] = x_slice^T dy per tap"""
-    xp = F.pad(x, (0, 0, p3[2], p3[2], p3[1], p3[1], p3[0], p3[0]))
-    do = tuple(dy.shape[1:4])
-    dw = torch.zeros((dy.shape[4],) + tuple(k3) + (x.shape[4],), dtype=F64, device=x.device)
-    dy2 = dy.reshape(-1, dy.shape[4])
-    for tap in _taps(k3):
-        st, sh, sw = _slices(do, k3, s3, tap)
-        dw[:, tap[0], tap[1], tap[2], :] = dy2.t() @ xp[:, st, sh, sw, :].reshape(-1, x.shape[4])
-    return dw
 
 
 def test_reference_against_torch_float64_on_the_cpu():
@@ -244,10 +149,6 @@ class Frame:
 
 
 # ---------------------------------------------------------------------------------------------------------------- data
-def dev_gen(dev, seed):
-    return torch.Generator(device=dev).manual_seed(seed)
-
-
 def g1(gen, shape, dev, r=2):
     return torch.randint(-r, r + 1, shape, generator=gen, device=dev).double() / 4
 
@@ -459,24 +360,6 @@ def route_key(c, mode):
     path = r.path + (str(r.kind) if r.path in ('TAP', 'TAP_CLASSES') else '')
     form = ('' if c.dtype != DV_F32 else ':w3' if (c.w3 if mode == 'fwd' else r.w3) else ':split')
     return '%s:%s:%s%s' % (mode, dt, path, form)
-
-
-def fold_adds(c, mode):
-    """fp32 additions that follow the accumulator: the 4-wave fold of the K-split kernel; the slab additions and `+=` of dw"""
-    if mode == 'wgrad':
-        return (c.wgrad.splits if c.wgrad.splits > 1 else 0) + 1
-    r = c.fwd if mode == 'fwd' else c.dgrad
-    return 3 if r.path == 'KS' else 0
-
-
-def gauss_bound(c, mode, S, cnt, ref, extra_adds=0):
-    if c.dtype == DV_F32:
-        n = 6 * cnt + fold_adds(c, mode) + extra_adds
-        d = 2.0 ** -23 if mode == 'wgrad' else 2.0 ** -24
-        return gamma((n - 1).clamp_min(0)) * (1 + 2.0 ** -7) * S + d * S
-    n = cnt + fold_adds(c, mode) + extra_adds
-    b = gamma((n - 1).clamp_min(0)) * S
-    return b if mode == 'wgrad' else b + 2.0 ** -8 * (ref.abs() + b)
 
 
 # ------------------------------------------------------------------------------------------------------ the main sweep

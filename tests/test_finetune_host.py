@@ -22,7 +22,7 @@ import classifier as CLI
 from dualvar_amd.utils import finetune_dataset as FD
 from dualvar_amd.utils import resample as R
 from dualvar_amd.utils import transforms as T
-from tests.test_frame_dataset_host import _rng_state, _seed, write_dataset
+from tests.dataset_support import _rng_state, _seed, ref, write_dataset  # noqa: F401  (ref: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
@@ -59,17 +59,6 @@ def test_samplers_against_fixture():
                 assert len(idx) == n_win * nf and (n_win == 1 or idx[nf] - idx[0] == nf * ds // 2 - 1)
             else:
                 assert len(idx) == nf
-
-
-@pytest.fixture
-def ref():
-    from oracle import harness
-    if not harness.available():
-        pytest.skip('reference tree not present')
-    harness.load_reference()
-    import dataset.local_dataset as LD
-    import utils.augmentation as RA
-    return LD, RA
 
 
 def test_getitem_order_against_reference(ref, tmp_path, monkeypatch):

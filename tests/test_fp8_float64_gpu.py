@@ -51,6 +51,8 @@ halves swapped: every GEMM test; one scale dropped: every row and all-codes case
 rows; truncation instead of rounding: every quantiser grid and Gaussian row); halving amax_partials_kernel's grid stride still
 computes the maximum and fails nothing.
 """
+import functools
+
 import pytest
 import torch
 
@@ -60,12 +62,16 @@ from dualvar_amd import ops  # noqa: E402
 from dualvar_amd._lib import DV_ACCUM, DV_BF16, DV_F32, DV_STATS  # noqa: E402
 from tests import fp8_cases as T  # noqa: E402
 from tests import fp8_reference as R  # noqa: E402
-from tests.test_conv_float64_gpu import gamma, is_sent, same_bits, sent  # noqa: E402
+from tests import checks  # noqa: E402
+from tests.chains import gamma  # noqa: E402
+from tests.checks import F64, TDT, Ratios, dev_gen, is_sent, sent  # noqa: E402
 
-F64 = torch.float64
-TDT = {DV_F32: torch.float32, DV_BF16: torch.bfloat16}
 E4, E5 = R.E4M3, R.E5M2
-RATIO, RMS, AMBIG = {}, {}, {}
+RATIO, RMS, AMBIG = Ratios(), {}, {}
+within = RATIO.within
+# bit for bit against float64 (bf16: against its round-to-nearest-even bf16): the reference must be an fp32 number; + 0.0 on
+# both sides only folds -0 into +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in=torch.float32, signed_zeros=False)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -77,17 +83,6 @@ def _report():
     print('ambiguous elements (of which took the other candidate) / elements:')
     for k in sorted(AMBIG):
         print(f'  {k:40s} {AMBIG[k][0]} ({AMBIG[k][1]}) / {AMBIG[k][2]}')
-
-
-def within(got64, ref64, bound, key, what):
-    assert bool(torch.isfinite(got64).all()), f'{what}: non-finite output'
-    err = (got64 - ref64).abs()
-    zero = bound == 0
-    assert bool((err[zero] == 0).all()), f'{what}: error where the bound is exactly 0'
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    RATIO[key] = max(RATIO.get(key, 0.0), ratio)
-    print(f'    {what}: max err {float(err.max()):.3e}  err/bound {ratio:.3f}')
-    assert ratio <= 1.0, f'{what}: err / bound = {ratio:.3f}'
 
 
 # ================================================================================================ dv_quantize_fp8
@@ -252,10 +247,6 @@ def run_dgrad(r, dev, dy8, wd8, sdy, sw, old=None):
     return dxa
 
 
-def dev_gen(dev, seed):
-    return torch.Generator(device=dev).manual_seed(seed)
-
-
 def g1_bytes(gen, shape, dev, fmt, rng=8):
     """integers in [-rng, rng] / 4 as bytes of `fmt` (asserted to decode to themselves)"""
     v = torch.randint(-rng, rng + 1, shape, generator=gen, device=dev).double() / 4
@@ -313,8 +304,8 @@ def stats_check(dev, y64, stats, rows_t, exact, unit, key, what):
         assert float(yt.abs().sum(1).max() + rows_t * amax.max()) < 2.0 ** 24 * unit, what + ': tile sums leave the exact range (test data)'
         same_bits(stats[0].t(), s, what + ' tile sums')
     else:
-        within(stats[0].t().double(), s, gamma(rows_t + 8) * (yt.abs().sum(1) + rows_t * amax), 'stats_sum:' + key, what + ' tile sums')
-    within(stats[1].t().double(), m2, gamma(rows_t + 8) * 2 * ((yt ** 2).sum(1) + rows_t * amax ** 2), 'stats_m2:' + key, what + ' tile M2')
+        within(stats[0].t().double(), s, gamma(rows_t + 8) * (yt.abs().sum(1) + rows_t * amax), what + ' tile sums', key='stats_sum:' + key)
+    within(stats[1].t().double(), m2, gamma(rows_t + 8) * 2 * ((yt ** 2).sum(1) + rows_t * amax ** 2), what + ' tile M2', key='stats_m2:' + key)
 
 
 SA, SB = 2.0 ** -3, 2.0 ** 5            # the scales of the exact cases: powers of two, not both 1
@@ -346,7 +337,7 @@ def test_fp8_gemm_fwd(gpu, row):
     ya, stats, rows_t = run_fwd(r, dev, x8, w8, sx, sw, flags=DV_STATS)
     ya.check_frame(what)
     got = ya.get().double()
-    within(got, ref, gauss_bound(S, cnt, ref, sx * sw, R.group_term(x8, E4, w8, E4)), key, what)
+    within(got, ref, gauss_bound(S, cnt, ref, sx * sw, R.group_term(x8, E4, w8, E4)), what, key=key)
     print(f'    {what}: rms figure {rms_figure(got, ref, key):.3f}')
     stats_check(dev, got, stats, rows_t, False, None, key, what)
     ya2, _, _ = run_fwd(r, dev, x8, w8, sx, sw)                                  # without DV_STATS: the same bits, stats untouched
@@ -380,7 +371,7 @@ def test_fp8_gemm_dgrad(gpu, row):
     dxa = run_dgrad(r, dev, dy8, wd8, sdy, sw)
     dxa.check_frame(what)
     got = dxa.get().double()
-    within(got, ref, gauss_bound(S, cnt, ref, sdy * sw, R.group_term(dy8, E5, wd8, E4)), key, what)
+    within(got, ref, gauss_bound(S, cnt, ref, sdy * sw, R.group_term(dy8, E5, wd8, E4)), what, key=key)
     print(f'    {what}: rms figure {rms_figure(got, ref, key):.3f}')
 
 

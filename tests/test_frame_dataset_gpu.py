@@ -16,7 +16,7 @@ from dualvar_amd import ops
 from dualvar_amd.ops import DV_F32
 from dualvar_amd.utils import frame_dataset as FD
 from dualvar_amd.utils import resample as R
-from tests.test_frame_dataset_host import SIZES, TARGETS, _img, _seed, write_dataset
+from tests.dataset_support import SIZES, TARGETS, _img, _seed, write_dataset
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

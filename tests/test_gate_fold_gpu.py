@@ -26,7 +26,8 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib as L, ops  # noqa: E402
 from dualvar_amd._lib import DV_BF16, DV_F32  # noqa: E402
-from tests import test_batchnorm_multi_gpu as B  # noqa: E402
+from tests import bn_support as B  # noqa: E402
+from tests.checks import View, bits, is_sent, launch, sent  # noqa: E402
 
 WIDTHS = (8, 24, 16, 8)
 OFFS = (0, 8, 32, 48)
@@ -38,11 +39,11 @@ SHAPES = [(3, 98), (37, 9)]        # (N, S)
 
 
 def _shared_view(dtype, M, C_, off, buf, values=None):
-    """a tests.test_batchnorm_multi_gpu.View on columns [off, off + C) of an existing [M][ld] buffer"""
-    v = B.View(dtype, M, C_, off, buf.shape[1], buf.device)
+    """a tests.checks.View on columns [off, off + C) of an existing [M][ld] buffer"""
+    v = View(dtype, M, C_, off, buf.shape[1], buf.device)
     v.buf = buf
     if values is not None:
-        v.set(values, junk=False)
+        v.set(values, pad=None)
     return v
 
 
@@ -52,8 +53,8 @@ class Level:
     def __init__(self, dev, dtype, N, S):
         self.dev, self.dtype, self.N, self.S, self.M = dev, dtype, N, S, N * S
         M = self.M
-        self.cat = B.sentinel_like((M, CAT_LD), dtype, dev)
-        self.dcat = B.sentinel_like((M, CAT_LD), dtype, dev)
+        self.cat = sent((M, CAT_LD), dev, dtype)
+        self.dcat = sent((M, CAT_LD), dev, dtype)
         self.members = []
         for k, (w, off) in enumerate(zip(WIDTHS, OFFS)):
             m = B.Member(dev, dtype, M, w, seed=100 + 17 * k, exact=False, from_x=True, views=k in SLICED_X)
@@ -67,7 +68,7 @@ class Level:
         gen = torch.Generator(device=dev).manual_seed(7 + N)
         self.g = torch.sigmoid(torch.randn(N, CT, generator=gen, device=dev))
         self.dmean = torch.randn(N, CT, generator=gen, device=dev) * 4
-        self.mean = B.f32_sentinel(N * CT, dev).view(N, CT)
+        self.mean = sent((N * CT,), dev).view(N, CT)
 
     @property
     def gated(self):
@@ -78,13 +79,13 @@ class Level:
 
     def apply_multi(self):
         tab, ends = self.table()
-        B.launch('dv_bn_apply_multi', self.dtype, tab.data_ptr(), len(self.members), ends['apply'])
+        launch('dv_bn_apply_multi', self.dtype, tab.data_ptr(), len(self.members), ends['apply'])
 
     def backward_outputs(self):
         out = []
         for m in self.members:
-            out += [m.sums[0], B.bits(m.dx.buf), m.dgamma, m.dbeta]
-        return [B.bits(t) if t.dtype == torch.float32 else t for t in out]
+            out += [m.sums[0], bits(m.dx.buf), m.dgamma, m.dbeta]
+        return [bits(t) if t.dtype == torch.float32 else t for t in out]
 
 
 DTYPES = [pytest.param(DV_F32, id='fp32'), pytest.param(DV_BF16, id='bf16')]
@@ -112,19 +113,19 @@ def test_gate_mean_and_scale_equal_the_unfused_sequence(gpu, dtype, N, S):
     n = len(a.members)
     # today's sequence
     a.apply_multi()
-    B.launch('dv_spatial_mean', dtype, a.cat.data_ptr(), CAT_LD, N, S, CT, a.mean.data_ptr())
-    B.launch('dv_gate_scale', dtype, a.cat.data_ptr(), CAT_LD, a.g.data_ptr(), N, S, CT, a.cat.data_ptr(), CAT_LD)
+    launch('dv_spatial_mean', dtype, a.cat.data_ptr(), CAT_LD, N, S, CT, a.mean.data_ptr())
+    launch('dv_gate_scale', dtype, a.cat.data_ptr(), CAT_LD, a.g.data_ptr(), N, S, CT, a.cat.data_ptr(), CAT_LD)
     # fused
     tab, _ = b.table()
-    B.launch('dv_gate_mean_bn', dtype, tab.data_ptr(), n, b.gate_off.data_ptr(), N, S, CT, b.mean.data_ptr())
+    launch('dv_gate_mean_bn', dtype, tab.data_ptr(), n, b.gate_off.data_ptr(), N, S, CT, b.mean.data_ptr())
     torch.cuda.synchronize()
     assert b.members[0].y.untouched(), 'dv_gate_mean_bn wrote the concat'
-    B.launch('dv_gate_scale_bn', dtype, tab.data_ptr(), n, b.gate_off.data_ptr(), a.g.data_ptr(), N, S, CT)
+    launch('dv_gate_scale_bn', dtype, tab.data_ptr(), n, b.gate_off.data_ptr(), a.g.data_ptr(), N, S, CT)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(a.mean).all()) and float(a.mean.abs().max()) > 0
-    assert torch.equal(B.bits(a.mean), B.bits(b.mean)), float((a.mean - b.mean).abs().max())
-    assert torch.equal(B.bits(a.cat), B.bits(b.cat)), 'gated concat differs (or a column past Ct was written)'
-    assert B.is_sentinel(b.cat[:, CT:], dtype)
+    assert torch.equal(bits(a.mean), bits(b.mean)), float((a.mean - b.mean).abs().max())
+    assert torch.equal(bits(a.cat), bits(b.cat)), 'gated concat differs (or a column past Ct was written)'
+    assert is_sent(b.cat[:, CT:])
     assert b.members[4].y.untouched(), 'the un-gated member is not the gate kernels\' to write'
     for m in b.members:
         assert not m.x.untouched() and m.dx.untouched()
@@ -142,19 +143,19 @@ def test_gated_batchnorm_backward_equals_the_unfused_sequence(gpu, dtype, N, S):
     torch.cuda.synchronize()
     y_in = [m.y.val() for m in a.members]
     # today's sequence: the gate rewrites dy in place, then the plain BatchNorm backward
-    B.launch('dv_gate_bwd_apply', dtype, a.dcat.data_ptr(), CAT_LD, a.g.data_ptr(), a.dmean.data_ptr(), N, S, CT,
+    launch('dv_gate_bwd_apply', dtype, a.dcat.data_ptr(), CAT_LD, a.g.data_ptr(), a.dmean.data_ptr(), N, S, CT,
              a.dcat.data_ptr(), CAT_LD, 0)
     tab, ends = a.table()
-    B.launch('dv_bn_bwd_reduce_multi', dtype, tab.data_ptr(), n, ends['red'])
-    B.launch('dv_bn_bwd_apply_multi', dtype, tab.data_ptr(), n, ends['bapply'], max(m.C for m in a.members))
+    launch('dv_bn_bwd_reduce_multi', dtype, tab.data_ptr(), n, ends['red'])
+    launch('dv_bn_bwd_apply_multi', dtype, tab.data_ptr(), n, ends['bapply'], max(m.C for m in a.members))
     # fused: gate on load
     tab, ends = b.table()
     gargs = (a.g.data_ptr(), a.dmean.data_ptr(), S, CT, b.gate_off.data_ptr())
-    B.launch('dv_bn_bwd_reduce_multi_gated', dtype, tab.data_ptr(), n, ends['red'], *gargs)
-    B.launch('dv_bn_bwd_apply_multi_gated', dtype, tab.data_ptr(), n, ends['bapply'], max(m.C for m in b.members), *gargs)
+    launch('dv_bn_bwd_reduce_multi_gated', dtype, tab.data_ptr(), n, ends['red'], *gargs)
+    launch('dv_bn_bwd_apply_multi_gated', dtype, tab.data_ptr(), n, ends['bapply'], max(m.C for m in b.members), *gargs)
     torch.cuda.synchronize()
-    assert torch.equal(B.bits(b.dcat), B.bits(dcat0)), 'the gated launches must leave dy as it was'
-    assert not torch.equal(B.bits(a.dcat), B.bits(dcat0))
+    assert torch.equal(bits(b.dcat), bits(dcat0)), 'the gated launches must leave dy as it was'
+    assert not torch.equal(bits(a.dcat), bits(dcat0))
     names = [f'member {i} {what}' for i in range(n) for what in ('sums', 'dx', 'dgamma', 'dbeta')]
     for name, x, y in zip(names, a.backward_outputs(), b.backward_outputs()):
         assert torch.equal(x, y), name
@@ -173,7 +174,7 @@ def test_gated_batchnorm_backward_equals_the_unfused_sequence(gpu, dtype, N, S):
             cols = slice(OFFS[i], OFFS[i] + m.C)
             dy = dcat0[:, cols].float()
             gated = (dy * a.g[rows][:, cols] + a.dmean[rows][:, cols] * inv_s).to(tdt)
-            m.dy = B.View(dtype, m.M, m.C, 0, m.C, gpu, gated.double(), junk=False)
+            m.dy = View(dtype, m.M, m.C, 0, m.C, gpu, gated.double(), pad=None)
         g, xhat = B.backward_terms(m, y_in[i])
         B.check_reduce(m, m.sums[0], g, xhat, 1, f'gated member {i}')
         B.check_bwd_apply(m, g, m.sums[0], 1.0 / m.M, f'gated member {i}')

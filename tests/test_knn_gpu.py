@@ -2,7 +2,7 @@
 (dualvar_amd/utils/knn.py) and `classifier.py --retrieval --knn` against float64 references written here from
 include/dualvar_select.h.
 
-Conventions (those of tests/test_loss_gemm_optim_gpu.py, whose helpers are imported): outputs sit in buffers filled with a NaN
+Conventions (those of tests/test_loss_gemm_optim_gpu.py; the helpers are tests/checks.py's): outputs sit in buffers filled with a NaN
 bit pattern no kernel produces and larger than needed (two more rows, ldk = k + 2, lds = n_class + 3): after every call the rows
 >= R and the columns >= k / >= n_class must still hold it.  Input rows carry NaN in sim[:, n_cols:ld).
 
@@ -28,11 +28,10 @@ reaches its half ulp), vote.score 0.035, topk_neighbours |val - s64| 0.011; ever
 128 / 127 of 130 rows of knn_eval at k = 200 for Acc@1 / Acc@5.  The whole file takes about 15 s, 11.5 s of it the two
 classifier.py children (5 s each, so the optional second child runs).
 """
+import functools
 import math
 import os
 import re
-import subprocess
-import sys
 import time
 
 import pytest
@@ -41,20 +40,22 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from dualvar_amd import ops  # noqa: E402
-from tests.test_loss_gemm_optim_gpu import E_EXPF, U, f32, gemm_bound, gemm_chain, is_sent, same_bits, sent, within  # noqa: E402
+from tests import checks  # noqa: E402
+from tests.chains import E_EXPF, gemm_bound, gemm_chain  # noqa: E402
+from tests.checks import U, Ratios, child as _child, f32, is_sent, report_fixture, sent  # noqa: E402
+from tests.dataset_support import write_dataset  # noqa: E402
+from tests.eval_support import chunks_of, grid_rows, knn_eval_case, unit_gauss  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = math.inf
-CACHE = {}
+RATIO = Ratios()
+within = RATIO.within
+_report = report_fixture(RATIO, 20)
+# bit for bit against float64: the reference must be an fp32 number; + 0.0 on both sides only folds -0 into +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in=torch.float32, signed_zeros=False)
 
 
 # --------------------------------------------------------------------------------------------------------------- helpers
-def grid_rows(seed, R, n):
-    """multiples of 1/4 in [-2, 2], fp32, on the host"""
-    gen = torch.Generator().manual_seed(seed)
-    return torch.randint(-8, 9, (R, n), generator=gen).float() / 4
-
-
 def select_ref(rows, k, col0=0):
     """rows [R, n] (any float dtype, NaN / inf allowed) -> (val [R, k] float64, idx [R, k] int32) of the header's total order"""
     x = rows.double().clone()
@@ -172,11 +173,6 @@ def test_selection_adversarial_rows(gpu, k, kind):
 
 
 # ----------------------------------------------------------------------------------------------- 3. chunking is invisible
-def chunks_of(n, m, descending=False):
-    c = [(s, min(m, n - s)) for s in range(0, n, m)]
-    return c[::-1] if descending else c
-
-
 @pytest.mark.parametrize('k', [5, 200])
 def test_chunking_is_invisible(gpu, k):
     R, N = 5, 5000
@@ -286,11 +282,6 @@ def test_vote_degenerate_totals_count_as_empty(gpu):
 
 
 # ------------------------------------------------------------------------------------------- 5. vote, Gaussian, derived bound
-def unit_gauss(gen, n, D):
-    x = torch.randn((n, D), generator=gen, dtype=torch.float64)
-    return (x / x.norm(dim=1, keepdim=True)).float()
-
-
 def vote_ref64(val, lab, n_class, inv_T, extra=0.0):
     """val [R, k] fp32 values as float64, lab [R, k] valid labels -> (score64 [R, C], bound [R, C]); extra: added to the bracket's
     per-weight term (the error the values themselves carry, times inv_T)"""
@@ -396,17 +387,6 @@ def test_topk_neighbours_gaussian_interval(gpu):
 
 
 # ------------------------------------------------------------------------- 8. knn_eval against the tested retrieval path
-def knn_eval_case(gpu):
-    if 'eval' not in CACHE:
-        from dualvar_amd.utils.features import centre_normalise
-        n_test, n_train, D, C = 130, 1000, 512, 10
-        gen = torch.Generator().manual_seed(2024)
-        te, tr = torch.randn((n_test, D), generator=gen).to(gpu), torch.randn((n_train, D), generator=gen).to(gpu)
-        tel, trl = torch.randint(0, C, (n_test,), generator=gen), torch.randint(0, C, (n_train,), generator=gen)
-        CACHE['eval'] = (te, tel, tr, trl, C, centre_normalise(te).double(), centre_normalise(tr).double())
-    return CACHE['eval']
-
-
 def eval_ref64(ten, trn, tel, trl, C, k, T, ks, gpu):
     """float64 protocol on the normalised fp32 features the library formed: retrieval hits, decidable rows, pred, top-5 hits"""
     n_train = trn.shape[0]
@@ -500,22 +480,7 @@ def test_knn_eval_against_retrieval_and_float64(gpu):
 
 
 # --------------------------------------------------------------------------------------------------- 9. the driver, one child
-STATE = {}
-
-
-def _child(argv, cwd, timeout):
-    """one GPU child process under its own timeout; a failure marks the chain as broken"""
-    assert not STATE.get('broken'), 'an earlier child failed or died: no further GPU child is started'
-    STATE['broken'] = True
-    r = subprocess.run([sys.executable] + argv, capture_output=True, text=True, timeout=timeout, cwd=cwd)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    STATE['broken'] = False
-    return out
-
-
 def test_cli_retrieval_with_knn(gpu, tmp_path_factory):
-    from tests.test_frame_dataset_host import write_dataset
     d = tmp_path_factory.mktemp('knn_cli')
     split, frame = write_dataset(str(d / 'data'), videos=((0, 40), (0, 9), (1, 70)), rows=830, sizes=[(90, 120), (120, 90), (80, 100)])
     os.makedirs(str(d / 'run' / 'model'))

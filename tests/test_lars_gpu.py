@@ -16,7 +16,7 @@ rounded once.  Every term is >= 0, so a path from a term to the total crosses 1 
   (A) a grid on which every operation is exact (|p| = 2^-3, |d| = 2^-4, n = 4^k, eta = 2^-10, mu = 1/2, lr = 2^-8; wd = 0 or 1/4):
       p', buf' and q equal float64 BIT FOR BIT.
   (B) Gaussian data, three steps, against float64 with a DERIVED bound.  b(x) bounds |x_fp32 - x_float64|;
-      rnd(x, prop) = prop + u (|x| + prop) is one rounding of a value within prop of x (tests/test_adam_gpu.py).  The reference uses
+      rnd(x, prop) = prop + u (|x| + prop) is one rounding of a value within prop of x (tests/optim_support.py).  The reference uses
       the very floats the entries receive (lr, mu, wd, eta, gs), the gradient is the same fp32 data, so per step, from b(p), b(buf):
           b(a1) = rnd(a1, 0)        b(a2) = rnd(a2, wd b(p))        b(d) = DECAY ? rnd(d, b(a1) + b(a2)) : b(a1)
           E(x)  = sum (2 |x| b(x) + b(x)^2) + n 2^-149              [sum x^^2 - sum x^2, and a square may underflow]
@@ -41,10 +41,9 @@ rounded once.  Every term is >= 0, so a path from a term to the total crosses 1 
   A numpy float32 replay of the operation list and of the summation tree, run under this file's own code on the CPU, gives the
   same lars.* and clf.* figures: every operation rounds as IEEE does.
 """
-import ctypes as C
+import functools
 import math
 
-import numpy as np
 import pytest
 import torch
 
@@ -52,70 +51,20 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib, ops  # noqa: E402
 from dualvar_amd._lib import DV_BF16, DV_F32  # noqa: E402
+from tests import checks  # noqa: E402
+from tests.checks import F64, U, Ratios, bits, f32, is_sent, report_fixture, sent  # noqa: E402
+from tests.optim_support import _classifier, _fill_grads, rnd  # noqa: E402
 
-U = 2.0 ** -24
 ADAPT, DECAY = 1, 2
-SENT_BITS = 0x7fb12345            # a NaN no kernel produces
-F64 = torch.float64
-RATIO = {}
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    print('\nlargest err / bound per quantity:')
-    for k in sorted(RATIO):
-        print(f'  {k:20s} {RATIO[k]:.3f}')
-
-
-def f32(x):
-    """the fp32 value a C float argument receives"""
-    return float(np.float32(x))
+RATIO = Ratios()
+within = RATIO.within
+_report = report_fixture(RATIO, 20)
+# bit for bit against float64: the reference must be an fp32 number; + 0.0 on both sides only folds -0 into +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in=torch.float32, signed_zeros=False)
 
 
 def chunk():
     return int(_lib.load().dv_lars_chunk())
-
-
-def sent(shape, dev, dtype=torch.float32):
-    if dtype == torch.bfloat16:
-        return torch.full(shape, 0x7fb1, dtype=torch.int16, device=dev).view(torch.bfloat16)
-    return torch.full(shape, SENT_BITS, dtype=torch.int32, device=dev).view(torch.float32)
-
-
-def sent_mask(t):
-    if t.dtype == torch.bfloat16:
-        return t.contiguous().view(torch.int16) == 0x7fb1
-    return t.contiguous().view(torch.int32) == SENT_BITS
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
-
-
-def same_bits(got, ref64, what):
-    r32 = ref64.to(torch.float32)
-    assert bool((r32.double() == ref64).all()), f'{what}: the float64 reference is not representable in fp32 (test data)'
-    g = (got.contiguous() + 0.0).view(torch.int32)
-    r = (r32.contiguous() + 0.0).view(torch.int32)
-    bad = g != r
-    assert not bool(bad.any()), (f'{what}: {int(bad.sum())} of {bad.numel()} elements differ from float64; first at '
-                                 f'{bad.nonzero()[0].tolist()}: got {got[bad][0].item()!r} want {r32[bad][0].item()!r}')
-
-
-def within(got, ref64, bound, what, quiet=False):
-    g = got.double()
-    assert bool(torch.isfinite(g).all()), f'{what}: non-finite output'
-    err = (g - ref64).abs()
-    zero = bound == 0
-    assert bool((err[zero] == 0).all()), f'{what}: error where the bound is exactly 0'
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    key = what.split(' ')[0]
-    RATIO[key] = max(RATIO.get(key, 0.0), ratio)
-    if not quiet:
-        print(f'    {what}: max err {float(err.max()):.3e}  err/bound {ratio:.3f}')
-    assert ratio <= 1.0, f'{what}: err / bound = {ratio:.3f}'
-    return ratio
 
 
 # ------------------------------------------------------------------------------------------------- tables
@@ -178,11 +127,9 @@ class Hyper:
         self.lr, self.mu, self.wd, self.eta, self.gs = f32(lr), f32(mu), f32(wd), f32(eta), f32(gs)
 
 
-def rnd(x, prop):
-    return prop + U * (x.abs() + prop)
-
-
-def gamma(n_blocks):
+def tree_gamma(n_blocks):
+    """G of the module docstring: the relative error of the kernels' summation tree (not chains.gamma: 75 roundings compounded,
+    plus the double fold of the chunk partials)"""
     return (1.0 + U) ** 75 - 1.0 + n_blocks * 2.0 ** -53
 
 
@@ -190,7 +137,7 @@ def sum_bound(x, bx, n_blocks):
     """S = sum x^2 in float64 and b(S) for the kernel's tree over operands within bx of x"""
     S = float((x * x).sum())
     E = float((2 * x.abs() * bx + bx * bx).sum()) + x.numel() * 2.0 ** -149
-    return S, E + gamma(n_blocks) * (S + E)
+    return S, E + tree_gamma(n_blocks) * (S + E)
 
 
 def ratio_ref(p, bp, d, bd, flags, c, n_blocks, what=''):
@@ -276,7 +223,7 @@ def test_lars_exact_grid(gpu, wd):
         same_bits(tab.q_out[i:i + 1], torch.tensor([q], dtype=F64, device=gpu), 'lars q ' + what)
         assert torch.equal(g[tab.sl(i)].double(), g64[i]), what + ': the gradient was written'
     keep = tab.outside()
-    assert bool(sent_mask(p)[keep].all()) and bool(sent_mask(buf)[keep].all()) and bool(sent_mask(g)[keep].all())
+    assert is_sent(p, keep) and is_sent(buf, keep) and is_sent(g, keep)
 
 
 # ---------------------------------------------------------------------------------------------------- (B) Gaussian data
@@ -319,7 +266,7 @@ def test_lars_gaussian_three_steps(gpu, wd, gs):
             within(buf[tab.sl(i)], b64[i], bb[i], 'lars.buf ' + tag, quiet=quiet)
             check_q(q_got[i], q, bq, 'lars.q ' + tag, quiet=quiet)
             assert torch.equal(g[tab.sl(i)], g32[i]), tag + ': the gradient was written'
-        assert bool(sent_mask(p)[keep].all()) and bool(sent_mask(buf)[keep].all()) and bool(sent_mask(g)[keep].all()), \
+        assert is_sent(p, keep) and is_sent(buf, keep) and is_sent(g, keep), \
             'an element outside the segments was written'
 
 
@@ -352,8 +299,8 @@ def test_lars_decay_only_segments_are_sgd_momentum(gpu, copy):
     for a, b, name in zip(state[0], state[1], ('p', 'buf', 'bf16 copy')):
         assert torch.equal(bits(a), bits(b)), f'{name}: LARS without ADAPT is not dv_sgd_momentum'
     assert not torch.equal(state[0][0][:N], p0)
-    assert bool(sent_mask(state[0][0][N:]).all()) and bool(sent_mask(state[0][2][N:]).all())
-    assert bool(sent_mask(state[0][2]).all()) == (dt is None)
+    assert is_sent(state[0][0][N:]) and is_sent(state[0][2][N:])
+    assert is_sent(state[0][2]) == (dt is None)
     assert tab.q_out.tolist() == [1.0] * len(ns)
 
 
@@ -442,33 +389,13 @@ def test_lars_compute_copy_is_the_cast_of_the_new_master(gpu, copy):
         tab.step(p, g, buf, h, code, cp if dt is not None else None, q_out=step != 1)
         assert not torch.equal(before[~keep], p[~keep])
         if dt is None:
-            assert bool(sent_mask(cp).all()), 'copy = NULL but the copy buffer changed'
+            assert is_sent(cp), 'copy = NULL but the copy buffer changed'
         else:
             assert torch.equal(bits(cp[~keep]), bits(p[~keep].to(dt))), 'the copy is not the round-to-nearest-even cast of the new master'
-            assert bool(sent_mask(cp)[keep].all()), 'copy written outside the segments'
+            assert is_sent(cp, keep), 'copy written outside the segments'
 
 
 # ------------------------------------------------------------------------------- (G) optim.LARS on a real model's arenas
-def _classifier(gpu, mode, dtype):
-    from dualvar_amd.model import LinearClassifier
-    torch.manual_seed(0)
-    kw = dict(use_dropout=False) if mode == 'ft' else dict(use_dropout=True, use_l2_norm=True, use_final_bn=True)
-    c = LinearClassifier(num_class=10, network='r3d', **kw)
-    if mode == 'last':
-        for n_, p_ in c.named_parameters():
-            if 'backbone' in n_:
-                p_.requires_grad = False
-    c.set_compute_dtype('fp32' if dtype == DV_F32 else 'bf16')
-    for st in c.stores():
-        st.materialize(gpu, dtype)
-    return c
-
-
-def _fill_grads(params, gen, scale=1e-2):
-    for p in params:
-        p.grad.copy_((torch.randn(p.shape, generator=gen) * scale).to(p.device))
-
-
 def _blocks(st, p):
     s = st.slot(p)
     return (((s.size + 7) & ~7) + chunk() - 1) // chunk()

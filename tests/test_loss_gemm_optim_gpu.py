@@ -55,6 +55,7 @@ write outside the stated range shows as a NaN in the result or as a changed sent
 Finding (test_ntxent_drows_splitk_is_atomic): drows of NT-Xent at 2N >= 4096 and <= 64 output tiles goes through dv_gemm_f32's
 atomic split-K: inside the bound (<= 0.005), but about 70 % of the 32 768 elements differ in bits between two launches.
 """
+import functools
 import math
 
 import numpy as np
@@ -65,80 +66,19 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib as L, ops  # noqa: E402
 from dualvar_amd._lib import DV_ACCUM, DV_BF16, DV_F32, DV_RELU, DV_SIGMOID  # noqa: E402
+from tests import checks  # noqa: E402
+from tests.chains import E_EXPF, E_LOG, E_LOG1P, TINY, e_exp, gemm_bound, gemm_chain, gemm_form, splitk_plan  # noqa: E402
+from tests.checks import F64, U, Ratios, ceil_div, f32, is_sent, report_fixture, sent  # noqa: E402
+from tests.optim_support import arena, check_copy, copy_buffer  # noqa: E402
 
-U = 2.0 ** -24
-E_LOG, E_LOG1P, E_EXPF = 5.4 * U, 2.1 * U, 2.8 * U
-TINY = 2.0 ** -126                # below it __expf may flush to 0: an absolute term next to the relative E_EXP
-SENT_BITS = 0x7fb12345            # a NaN no kernel produces
-F64 = torch.float64
-RATIO = {}                        # quantity -> largest err / bound of the run
-
-
-def e_exp(x):
-    return (4.2 + 4.1 * x.abs()) * U
-
-
-def f32(x):
-    """the fp32 value a C float argument receives"""
-    return float(np.float32(x))
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    print('\nlargest err / bound per quantity:')
-    for k in sorted(RATIO):
-        print(f'  {k:34s} {RATIO[k]:.3f}')
+RATIO = Ratios()                  # quantity -> largest err / bound of the run
+within = RATIO.within
+_report = report_fixture(RATIO, 34)
+# bit for bit against float64: the reference must be an fp32 number; + 0.0 on both sides only folds -0 into +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in=torch.float32, signed_zeros=False)
 
 
 # ----------------------------------------------------------------------------------------------------------- helpers
-def sent(shape, dev, dtype=torch.float32):
-    if dtype == torch.float32:
-        return torch.full(shape, SENT_BITS, dtype=torch.int32, device=dev).view(torch.float32)
-    if dtype == torch.bfloat16:
-        return torch.full(shape, 0x7fb1, dtype=torch.int16, device=dev).view(torch.bfloat16)
-    return torch.full(shape, SENT_BITS, dtype=torch.int32, device=dev)
-
-
-def is_sent(t):
-    if t.numel() == 0:
-        return True
-    if t.dtype == torch.bfloat16:
-        return bool((t.contiguous().view(torch.int16) == 0x7fb1).all())
-    return bool((t.contiguous().view(torch.int32) == SENT_BITS).all())
-
-
-def same_bits(got, ref64, what):
-    """got (fp32) equals the float64 reference bit for bit; the reference must itself be an fp32 number"""
-    r32 = ref64.to(torch.float32)
-    assert bool((r32.double() == ref64).all()), f'{what}: the float64 reference is not representable in fp32 (test data)'
-    g = (got.contiguous() + 0.0).view(torch.int32)
-    r = (r32.contiguous() + 0.0).view(torch.int32)
-    bad = g != r
-    assert not bool(bad.any()), (f'{what}: {int(bad.sum())} of {bad.numel()} elements differ from float64; first at '
-                                 f'{bad.nonzero()[0].tolist()}: got {got[bad][0].item()!r} want {r32[bad][0].item()!r}')
-
-
-def within(got, ref64, bound, what, quiet=False):
-    """|got - ref| <= bound elementwise, no element left out; records and prints err / bound"""
-    g = got.double()
-    assert bool(torch.isfinite(g).all()), f'{what}: non-finite output'
-    err = (g - ref64).abs()
-    zero = bound == 0
-    assert bool((err[zero] == 0).all()), f'{what}: error where the bound is exactly 0'
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    key = what.split(' ')[0]
-    RATIO[key] = max(RATIO.get(key, 0.0), ratio)
-    if not quiet:
-        print(f'    {what}: max err {float(err.max()):.3e}  err/bound {ratio:.3f}')
-    assert ratio <= 1.0, f'{what}: err / bound = {ratio:.3f}'
-    return ratio
-
-
 def grid(gen, shape, dev, density=1.0):
     """integers in [-2, 2] / 4 as float64 on the device"""
     v = torch.randint(-2, 3, shape, generator=gen, dtype=torch.int64)
@@ -185,42 +125,9 @@ class Out:
 
 
 # ----------------------------------------------------------------------------------------------------------- GEMM plan
-def splitk_plan(M, N, K):
-    """gemm_splitk_plan of loss.hip: (tiles, splits, kslice); splits 0 = not split"""
-    tiles = cdiv(M, 32) * cdiv(N, 32)
-    splits = kslice = 0
-    if tiles <= 64 and K >= 4096:
-        splits = min(1024 // tiles, K // 256)
-        kslice = cdiv(cdiv(K, splits), 64) * 64
-        splits = cdiv(K, kslice)
-    return tiles, splits, kslice
-
-
-def gemm_form(M, N, K):
-    tiles, splits, _ = splitk_plan(M, N, K)
-    if splits:
-        return 'split'
-    return 'tile4' if tiles <= 1024 and K >= 64 else 'plain'
-
-
 def splitk_ws_bytes(M, N, K):
     tiles, splits, _ = splitk_plan(M, N, K)
     return (splits * tiles * 1024 + ((tiles + 7) & ~7)) * 4 if splits else 0
-
-
-def gemm_chain(M, N, K, form=None):
-    form = form or gemm_form(M, N, K)
-    if form == 'plain':
-        return K + (K & 1)
-    if form == 'tile4':
-        return 16 * cdiv(cdiv(K, 16), 4) + 3
-    _, splits, kslice = splitk_plan(M, N, K)
-    return 16 * cdiv(cdiv(kslice, 16), 4) + 3 + splits
-
-
-def gemm_bound(A64, B64t, alpha, chain):
-    """A64 [M][K], B64t [N][K]"""
-    return (chain + 2) * U * abs(alpha) * (A64.abs() @ B64t.abs().t())
 
 
 def assert_exact_sum(A64, B64t, alpha, extra=None):
@@ -265,7 +172,7 @@ def test_sweep_reaches_every_form_and_threshold():
     """the shape list puts at least three shapes on each side of each rule of launch_gemm_f32 / gemm_splitk_plan"""
     forms = [gemm_form(*s) for s in SWEEP]
     assert min(forms.count(f) for f in ('plain', 'tile4', 'split')) >= 7
-    t = lambda s: cdiv(s[0], 32) * cdiv(s[1], 32)  # noqa: E731
+    t = lambda s: ceil_div(s[0], 32) * ceil_div(s[1], 32)  # noqa: E731
     assert sum(1 for s in SWEEP if s[2] >= 4096 and t(s) <= 64) >= 3 and sum(1 for s in SWEEP if s[2] >= 4096 and t(s) > 64) >= 3
     assert sum(1 for s in SWEEP if t(s) <= 64 and 4000 <= s[2] < 4096) >= 3
     assert sum(1 for s in SWEEP if t(s) > 1024) >= 3 and sum(1 for s in SWEEP if t(s) == 1024) >= 1
@@ -391,7 +298,7 @@ def test_gemm_f32_grouped_exact(gpu, n_groups):
         d, k = make_desc(gpu, gen, M, N, K, [0, DV_RELU, DV_ACCUM, DV_ACCUM | DV_RELU][g % 4], ALPHAS[g % 6], g % 3 != 2,
                          (g & 1) == 0, (g >> 1) & 1 == 0, PES[g % 5], (g // 3) & 1)
         if g not in empty:
-            end += cdiv(M, 32) * cdiv(N, 32)
+            end += ceil_div(M, 32) * ceil_div(N, 32)
         d.tile_end = end
         descs[g] = d
         keep.append(k)
@@ -473,7 +380,7 @@ def run_ntxent(dev, rows, cols, n_local, N, row_index0, inv_T, exact, tag):
     mx = torch.where(mask, ref['s'], torch.full_like(ref['s'], -1e300)).max(1).values
     x = torch.where(mask, ref['s'] - mx[:, None], torch.zeros_like(ref['s']))
     b_in = torch.where(mask, b, torch.zeros_like(b)).max(1).values
-    b_lse = b_in + (cdiv(C2, 64) + 6 + 1) * U + (ref['p'] * (e_exp(x) + U * x.abs())).sum(1) + E_LOG * (ref['lse'] - mx).abs() \
+    b_lse = b_in + (ceil_div(C2, 64) + 6 + 1) * U + (ref['p'] * (e_exp(x) + U * x.abs())).sum(1) + E_LOG * (ref['lse'] - mx).abs() \
         + U * ref['lse'].abs()
     within(loss[:R], ref['loss'], b_lse + b[rr, ref['pos']] + U * ref['loss'].abs(), f'ntxent.loss_rows {tag}')
     xl = ref['s'] - ref['lse'][:, None]
@@ -590,7 +497,7 @@ def run_infonce(dev, q, k, queue, inv_T, exact, tag, form):
     lib = L.load()
     ws_bytes = int(lib.dv_infonce_workspace(B, D, K))
     # the plan of dq = dlogits . queue^T (M = B, N = D over K): split when it has <= 64 tiles of 32 x 32 and K >= 4096
-    assert (ws_bytes > 0) == (cdiv(B, 32) * cdiv(D, 32) <= 64 and K >= 4096) and ws_bytes == splitk_ws_bytes(B, D, K)
+    assert (ws_bytes > 0) == (ceil_div(B, 32) * ceil_div(D, 32) <= 64 and K >= 4096) and ws_bytes == splitk_ws_bytes(B, D, K)
     logits, dlog = sent((B + 1, K + 1), dev), sent((B + 1, K + 1), dev)
     loss, rank0, dq = sent((B + 8,), dev), sent((B + 8,), dev, torch.int32), sent((B + 1, D), dev)
     ws = None
@@ -613,7 +520,7 @@ def run_infonce(dev, q, k, queue, inv_T, exact, tag, form):
         assert torch.equal(rank0[:B].long(), ref['rank']), tag + ': rank0'
         b = torch.zeros_like(ref['logits'])
     else:
-        b = torch.cat([((cdiv(D, 256) + 10 + 2) * U * f32(inv_T) * (q * k).abs().sum(1))[:, None],
+        b = torch.cat([((ceil_div(D, 256) + 10 + 2) * U * f32(inv_T) * (q * k).abs().sum(1))[:, None],
                        gemm_bound(q, queue.t().contiguous(), inv_T, gemm_chain(B, K, D))], 1)
         within(logits[:B], ref['logits'], b, f'infonce.logits {tag}')
         bb = b[:, 1:] + b[:, :1]
@@ -622,7 +529,7 @@ def run_infonce(dev, q, k, queue, inv_T, exact, tag, form):
         assert bool(((got >= (diff > bb).sum(1)) & (got <= (diff >= -bb).sum(1))).all()), tag + ': rank0 outside its interval'
     mx = ref['logits'].max(1).values
     x = ref['logits'] - mx[:, None]
-    b_lse = b.max(1).values + (cdiv(K, 256) + 11 + 1) * U + (ref['p'] * (e_exp(x) + U * x.abs())).sum(1) \
+    b_lse = b.max(1).values + (ceil_div(K, 256) + 11 + 1) * U + (ref['p'] * (e_exp(x) + U * x.abs())).sum(1) \
         + E_LOG * (ref['lse'] - mx).abs() + U * ref['lse'].abs()
     within(loss[:B], ref['loss'], b_lse + b[:, 0] + U * ref['loss'].abs(), f'infonce.loss_rows {tag}')
     xl = ref['logits'] - ref['lse'][:, None]
@@ -745,7 +652,7 @@ def run_rank_margin(dev, f64, s, theta, clip, weight, tag):
     sg = torch.sigmoid(zc)
     b_term = bz + (e_exp(zc) * sg + E_LOG1P) * sp
     scale = w / ref['count']
-    b_loss = scale * b_term.sum() + (n2 + 8 + cdiv(Bn, 256) + 11) * U * float(ref['loss'].detach().abs())
+    b_loss = scale * b_term.sum() + (n2 + 8 + ceil_div(Bn, 256) + 11) * U * float(ref['loss'].detach().abs())
     within(loss[:1], ref['loss'].detach().view(1), b_loss.view(1), f'margin.loss {tag}')
     # gradient: dz = weight / count * sigmoid * pass / theta into dS[i][j] and -dS[i][pair]
     passed = (z <= cl).double() if clip > 0 else torch.ones_like(z)
@@ -786,7 +693,7 @@ def run_rank_margin_exact(dev, f, s, clip):
     zc = ref['zc']
     sp = torch.nn.functional.softplus(zc, threshold=1e9)
     b_loss = ((e_exp(zc) * torch.sigmoid(zc) + E_LOG1P) * sp).sum() / ref['count'] \
-        + (n2 + 8 + cdiv(Bn, 256) + 11) * U * ref['loss'].abs()
+        + (n2 + 8 + ceil_div(Bn, 256) + 11) * U * ref['loss'].abs()
     within(loss[:1], ref['loss'].view(1), b_loss.view(1), f'margin.loss grid s={s} Bn={Bn} clip={clip}')
     if clip > 0 and Bn > 1:
         assert bool((ref['z'] > clip).any()) and bool((ref['z'] < clip).any())
@@ -820,7 +727,7 @@ def test_softmax_ce_and_rows(gpu, R, K):
     mx = x64.max(1).values
     p = torch.exp(x64 - lse[:, None])
     xm = x64 - mx[:, None]
-    b_lse = (cdiv(K, 64) + 6 + 1) * U + (p * (e_exp(xm) + U * xm.abs())).sum(1) + E_LOG * (lse - mx).abs() + U * lse.abs()
+    b_lse = (ceil_div(K, 64) + 6 + 1) * U + (p * (e_exp(xm) + U * xm.abs())).sum(1) + E_LOG * (lse - mx).abs() + U * lse.abs()
     onehot = torch.nn.functional.one_hot(labels.long(), K).double()
     gs = f32(np.float32(1.0) / np.float32(R))
     xl = x64 - lse[:, None]
@@ -840,7 +747,7 @@ def test_softmax_ce_and_rows(gpu, R, K):
     probs = sent((R + 1, K + 5), gpu)
     ops.call('dv_softmax_rows_f32', lg, ld, R, K, probs, K + 5)
     pm = torch.softmax(x64, 1)
-    within(probs[:R, :K], pm, pm * ((cdiv(K, 64) + 6 + 2) * U + 2 * (E_EXPF + U * xm.abs()).max(1).values[:, None] + U * xm.abs()),
+    within(probs[:R, :K], pm, pm * ((ceil_div(K, 64) + 6 + 2) * U + 2 * (E_EXPF + U * xm.abs()).max(1).values[:, None] + U * xm.abs()),
            f'softmax_rows R={R} K={K}', quiet=True)
     assert is_sent(probs[:R, K:]) and is_sent(probs[R:])
 
@@ -897,7 +804,7 @@ def test_mean_f32(gpu, n):
     out = sent((8,), gpu)
     ops.call('dv_mean_f32', x, n, out)
     x64 = x[:n].double()
-    within(out[:1], x64.mean().view(1), ((cdiv(n, 256) + 6 + 4 + 1) * U * x64.abs().sum() / n).view(1), f'mean n={n}', quiet=True)
+    within(out[:1], x64.mean().view(1), ((ceil_div(n, 256) + 6 + 4 + 1) * U * x64.abs().sum() / n).view(1), f'mean n={n}', quiet=True)
     assert is_sent(out[1:])
     xi = torch.randint(-8, 9, (n,), generator=gen).float().to(gpu)
     ops.call('dv_mean_f32', xi, n, out)
@@ -925,7 +832,7 @@ def test_colsum_f32(gpu, R):
         out[:Cc] = out0
         ops.call('dv_colsum_f32', x, ld, R, Cc, out)
         ref = out0.double() + xg.double().sum(0)
-        within(out[:Cc], ref, (cdiv(R, 32) + 2 + 8 + 1) * U * (out0.double().abs() + xg.double().abs().sum(0)), f'colsum R={R}',
+        within(out[:Cc], ref, (ceil_div(R, 32) + 2 + 8 + 1) * U * (out0.double().abs() + xg.double().abs().sum(0)), f'colsum R={R}',
                quiet=True)
 
 
@@ -946,34 +853,6 @@ def sgd_ref(p, g, buf, lr, mu, wd, gs, exact):
         for name, t in (('g*gs', g * gs), ('wd*p', wd * p), ('d', d), ('mu*buf', mu * buf), ('buf', nb), ('lr*buf', lb), ('p', npar)):
             assert_f32(t, name)
     return npar, nb
-
-
-def arena(vals64, dtype=torch.float32):
-    n = vals64.numel()
-    t = sent((n + 8,), vals64.device, dtype)
-    t[:n] = vals64.to(dtype)
-    return t
-
-
-def check_copy(copy, p, n, dtype, what):
-    if dtype is None:
-        assert is_sent(copy), what + ': copy = NULL but the copy buffer changed'
-        return
-    want = p[:n].to(dtype)
-    it = torch.int16 if dtype == torch.bfloat16 else torch.int32
-    assert torch.equal(copy[:n].view(it), want.view(it)), what + ': the copy is not the round-to-nearest-even cast of the new value'
-    assert is_sent(copy[n:]), what + ': copy written past n'
-
-
-def copy_buffer(n, copy, dev):
-    """copy case -> (torch dtype or None, DV code, the whole sentinel buffer, the [n + 8] view the entry writes).  'bf16-odd': the
-    view starts one element (2 bytes) past the allocation, so no 8-byte store of four bf16 is possible"""
-    dt = {'bf16': torch.bfloat16, 'bf16-odd': torch.bfloat16, 'f32': torch.float32, 'none': None}[copy]
-    off = 1 if copy == 'bf16-odd' else 0
-    whole = sent((n + 8 + off,), dev, dt or torch.float32)
-    cp = whole[off:]
-    assert cp.data_ptr() % 8 == 2 * off
-    return dt, DV_BF16 if dt == torch.bfloat16 else DV_F32, whole, cp
 
 
 COPY_CASES = [(n, c) for n in NS for c in ('bf16', 'f32', 'none')] + [(n, 'bf16-odd') for n in (5, 1003)]

@@ -490,7 +490,7 @@ def test_augment_gaussian_blur_against_pil_fixture(gpu, dtype, pad):
 def test_augment_hue_against_reference_fixture(gpu):
     """DV_AUG_HUE on the GPU == the reference's adjust_hue_np (uint8 result in tests/golden/augment.npz, part C)"""
     from tests.util import gold
-    from tests.test_oracle_golden import _hue_matches
+    from tests.util import _hue_matches
     from dualvar_amd.utils.transforms import AUG_ROW
     g = gold('augment')
     H, W = (int(v) for v in g['HW'])

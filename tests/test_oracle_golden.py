@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import CLIP, gold, grad_summary, param_checksum, total_loss
+from tests.util import CLIP, _hue_matches, gold, grad_summary, param_checksum, total_loss
 
 
 def _build(kind, net, distributed=False):
@@ -195,13 +195,6 @@ def test_augment_oracle_matches_reference_fixture():
     want = torch.from_numpy(g['A/want'])                                        # [clips, T, 3, H, W]
     got = A.augment_ingest(g['frames'], table, want.shape[0], want.shape[1], H, W, g['mean'].tolist(), g['std'].tolist())
     assert float((got.permute(0, 2, 1, 3, 4) - want).abs().max()) < 2e-6
-
-
-def _hue_matches(q, want_u8):
-    """floor(255 * x) == the reference's uint8 result; a float within rounding of an integer may truncate either way"""
-    diff = np.abs(np.floor(q) - want_u8.astype(np.float64))
-    near = np.abs(q - np.round(q)) < 2e-3
-    return int(((diff > 0) & ~((diff <= 1) & near)).sum()), int(((diff > 0) & near).sum())
 
 
 def test_augment_hue_oracle_matches_reference_fixture():

@@ -24,34 +24,9 @@ from dualvar_amd import _lib as L  # noqa: E402
 from dualvar_amd import engine  # noqa: E402
 from dualvar_amd._lib import DV_ACCUM  # noqa: E402
 from tests import plan_audit as A  # noqa: E402
+from tests.plan_audit import LARGE, NETS, SMALL, fusion_counts  # noqa: E402
 
-# net -> (T, H = W) of the SMALL cases
-SMALL = {'s3dg': (8, 64), 'r21d': (1, 32), 'r3d': (1, 32), 'r50': (1, 48), 's3d': (8, 64), 'r2d3d18': (1, 48), 'c3d': (8, 32)}
-NETS = tuple(SMALL)
-# net -> N of the LARGE (8 x 112 x 112, fp32) cases and the counts the plan must hold there
-LARGE = {'s3dg': (8, dict(bn_in=1, bn_wgrad=1, pool=2, gate=9, pair_fwd_sp=1, pair_fwd_tm=1, pair_dgrad=1, pair_ks=20)),
-         'r21d': (3, dict(bn_in=1, bn_wgrad=1, pool=0, gate=0, pair_fwd_sp=0, pair_fwd_tm=0, pair_dgrad=0, pair_ks=0))}
 DTYPES = ['fp32', 'bf16']
-
-
-def fusion_counts(plan):
-    """how many of each fusion and pairing a plan holds"""
-    c = dict(bn_in=0, bn_wgrad=0, pool=0, gate=0, pair_fwd_sp=0, pair_fwd_tm=0, pair_dgrad=0, pair_ks=0)
-    for op in plan.ops:
-        if isinstance(op, engine.ConvOp):
-            c['bn_in'] += op.bn_in is not None
-            c['bn_wgrad'] += op.bn_apply is not None
-        elif isinstance(op, engine.PoolOp):
-            c['pool'] += op.bn_member is not None
-        elif isinstance(op, engine.GateGroupOp):
-            c['gate'] += bool(op.fused)
-    for l in plan.f_list + plan.b_list:
-        if getattr(l, 'members', ()):
-            key = ('pair_ks' if 'conv_gemm_ks' in l.kname else 'pair_dgrad' if l.name == 'conv_dgrad'
-                   else 'pair_fwd_sp' if ',sp,' in l.kname else 'pair_fwd_tm' if ',tm,' in l.kname else None)
-            assert key is not None, l.kname
-            c[key] += 1
-    return c
 
 
 @pytest.fixture(scope='module', autouse=True)

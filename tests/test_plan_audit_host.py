@@ -9,7 +9,7 @@ from dualvar_amd.backbone import select_backbone
 from oracle import procedural as P
 from oracle import torch_ref as O
 from tests import plan_audit as A
-from tests.test_plan_audit_gpu import LARGE, NETS, SMALL, fusion_counts
+from tests.plan_audit import LARGE, NETS, SMALL, fusion_counts
 
 CPU = torch.device('cpu')
 _free = {}

@@ -2,7 +2,7 @@
 restatements of include/dualvar_hip.h, through the C ABI on explicit tensors, on every launch route of tests/pool_cases.py
 (tests/test_abi_and_host.py::test_pool_case_table_routes_and_coverage pins each row to its route without a GPU).
 
-Conventions (those of tests/test_batchnorm_multi_gpu.py, whose helpers are imported): gaps of input buffers -- pitch padding,
+Conventions (those of tests/test_batchnorm_multi_gpu.py; the helpers are tests/checks.py's): gaps of input buffers -- pitch padding,
 columns outside a channel slice, the stride between ingest samples, the slack in front of an offset idx -- hold NaN (0xff
 bytes for idx); pad lanes [C, CP) of input activations hold zeros, the stated convention for activations; outputs start as a
 NaN bit pattern no kernel produces, and after a call everything outside the stated range keeps those bits while pad lanes of
@@ -28,7 +28,7 @@ written views are 0.
     helpers, ingest   dv_relu_bwd_f32, dv_l2norm_fwd on rows of power-of-two norm, the ingest copies: exact.
 (B) Gaussian data, derived bounds, u = 2^-24 (bf16 store: + 2^-8 |ref|):
     column sums       |err| <= (L + r) u sum|terms|: L = column_chain() (next to bwd_reduce_chain in
-                      tests/test_batchnorm_multi_gpu.py), the longest chain of sequential fp32 additions
+                      tests/chains.py), the longest chain of sequential fp32 additions
                       column_reduce forms (rows per thread + ceil(log2 rg) + blocks per replica for the atomic form), r the
                       roundings inside one term
     dx of dv_bn_bwd_apply_maxpool   the kernel's own expression k1*g + k2*x + k3, k3 = -k1*sg/M - k2*mean:
@@ -64,33 +64,32 @@ Seeded faults, each built into a scratch copy of the kernels and run against thi
     bn_apply_maxpool_kernel pooling x before the affine map: test_bn_relu_pool_forward (8).
 """
 import ctypes as C
+import functools
 import math
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib as L, ops  # noqa: E402
 from dualvar_amd._lib import DV_ACCUM, DV_BF16, DV_F32  # noqa: E402
 from tests import pool_cases as T  # noqa: E402
-from tests import test_batchnorm_multi_gpu as B  # noqa: E402
-from tests.test_batchnorm_multi_gpu import BF16_U, U, ceil_div, column_chain, cp8, vec  # noqa: E402
+from tests.bn_support import DTYPES  # noqa: E402
+from tests.chains import column_chain  # noqa: E402
+from tests import checks  # noqa: E402
+from tests.checks import (BF16_U, U, Ratios, View, bits, ceil_div, chan, cp8, is_sent, launch, report_fixture,  # noqa: E402
+                          sent, vec)
+from tests.pool_reference import ref_pool_bwd, ref_pool_fwd  # noqa: E402
 
-DTYPES = B.DTYPES
 IDX_SENT = 0xEE                    # idx bytes before a launch: no tap is that large (kt*kh*kw <= 27 here)
 SQRT_MEASURED = 1.0                # max |sqrtf(s) - sqrt(s)| / (u sqrt(s)) on the MI355X: 0.9999 measured (see the docstring)
-RATIOS = {}
+RATIOS = Ratios()
+# bit for bit against float64: the reference must be a number of the storage dtype, and -0 is not +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in='storage', signed_zeros=True)
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _report():
-    yield
-    if RATIOS:
-        print('\n  largest err / bound per quantity')
-        for k in sorted(RATIOS):
-            print('    %-44s %.3f' % (k, RATIOS[k]))
+_report = report_fixture(RATIOS, 44)
 
 
 def tdt(dtype):
@@ -101,67 +100,17 @@ def store_u(dtype):
     return 0.0 if dtype == DV_F32 else BF16_U
 
 
-def launch(name, *args):
-    B.launch(name, *args)
-
-
 def rc_of(name, *args):
     return getattr(L.load(), name)(*args, ops.stream_ptr())
 
 
-def bounded(name, got, ref, bound):
-    """err <= bound everywhere; the largest err / bound is kept for the report"""
-    got, ref, bound = got.double().cpu(), ref.double().cpu(), bound.double().cpu()
-    err = (got - ref).abs()
-    bad = ~(err <= bound)
-    ratio = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    RATIOS[name] = max(RATIOS.get(name, 0.0), ratio)
-    print('    %-44s err / bound = %.3f' % (name, ratio))
-    assert not bool(bad.any()), '%s: %d values outside the bound, worst err / bound %.3f' % (name, int(bad.sum()), ratio)
-
-
-def same_bits(got, ref, what):
-    """got (device, storage dtype) equals ref (float64, any device) bit for bit; +-0 are told apart"""
-    r = ref.to(got.dtype).to(got.device)
-    assert torch.equal(r.double().cpu(), ref.double().cpu()), what + ': the reference is not representable (test bug)'
-    ok = B.bits(got.contiguous()) == B.bits(r.contiguous())
-    assert bool(ok.all()), '%s: %d of %d values differ, first at %s' % (
-        what, int((~ok).sum()), ok.numel(), (~ok).nonzero()[0].tolist())
+def bounded(got, ref, bound, name):
+    """the shared bound check, recorded under the whole name"""
+    RATIOS.within(got, ref, bound, name, key=name)
 
 
 def gen(seed):
     return torch.Generator().manual_seed(seed)
-
-
-# ------------------------------------------------------------------------------------------------------------ views
-class View:
-    """[M][C] values as columns [off, off + CP) of a [M][ld] buffer.  Inputs: NaN outside the view, zeros in the pad lanes;
-    outputs: sentinel bits everywhere."""
-
-    def __init__(self, dtype, M, C_, dev, sliced=False, values=None, pitch_pad=0):
-        self.dtype, self.M, self.C, self.CP = dtype, M, C_, cp8(C_)
-        self.off = 8 if sliced else 0
-        self.ld = self.CP + (24 if sliced else pitch_pad)
-        self.buf = B.sentinel_like((M, self.ld), dtype, dev)
-        if values is not None:
-            self.set(values)
-
-    def set(self, values):
-        self.buf[:, self.off:self.off + self.C] = values.reshape(self.M, -1)[:, :self.C].to(self.buf.dtype).to(self.buf.device)
-        self.buf[:, self.off + self.C:self.off + self.CP] = 0
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.off * self.buf.element_size()
-
-    def cols(self):
-        """the CP columns of the view, storage dtype"""
-        return self.buf[:, self.off:self.off + self.CP]
-
-    def check_frame(self, what):
-        assert B.is_sentinel(self.buf[:, :self.off], self.dtype) and B.is_sentinel(self.buf[:, self.off + self.CP:], self.dtype), \
-            what + ': a column outside the view was written'
-        assert bool((self.buf[:, self.off + self.C:self.off + self.CP] == 0).all()), what + ': pad lanes [C, CP) not zero'
 
 
 def padded(v5, CP):
@@ -194,55 +143,6 @@ class IdxBuf:
             what + ': idx written outside [M][CP]'
 
 
-# ------------------------------------------------------------------------------------------------------------ pool references
-def ref_pool_fwd(x5, c):
-    """x5 [N, T, H, W, CP] float64 (CPU) -> pooled values [N, To, Ho, Wo, CP] and the tap (dt*kh + dh)*kw + dw of the first
-    maximum in (t, h, w) scan order, from F.max_pool3d's flat input index"""
-    y, flat = F.max_pool3d(x5.permute(0, 4, 1, 2, 3).contiguous(), c.k, c.s, c.p, return_indices=True)
-    To, Ho, Wo = y.shape[2:]
-    t, h, w = flat // (c.H * c.W), (flat // c.W) % c.H, flat % c.W
-    ar = lambda n, s, p: torch.arange(n) * s - p      # noqa: E731
-    dt = t - ar(To, c.s[0], c.p[0]).view(1, 1, To, 1, 1)
-    dh = h - ar(Ho, c.s[1], c.p[1]).view(1, 1, 1, Ho, 1)
-    dw = w - ar(Wo, c.s[2], c.p[2]).view(1, 1, 1, 1, Wo)
-    assert bool(((dt >= 0) & (dt < c.k[0]) & (dh >= 0) & (dh < c.k[1]) & (dw >= 0) & (dw < c.k[2])).all())
-    tap = (dt * c.k[1] + dh) * c.k[2] + dw
-    return y.permute(0, 2, 3, 4, 1).contiguous(), tap.permute(0, 2, 3, 4, 1).contiguous().to(torch.uint8)
-
-
-def ref_pool_bwd(gy5, tap5, c, start, acc_dtype=torch.float64):
-    """dx [N, T, H, W, CP] = start + the contributions gy of the windows that chose each element, added in ASCENDING TAP ORDER
-    in acc_dtype: float64 is the exact reference, float32 the kernels' promised sum (distinct windows reach an element
-    through distinct taps, so the order is total).  Also the number of windows and sum |gy| per element."""
-    To, Ho, Wo = T.out_dims(c)
-    acc = start.to(acc_dtype).clone()
-    cnt = torch.zeros(start.shape, dtype=torch.int32)
-    mag = torch.zeros(start.shape, dtype=torch.float64)
-    gy5 = gy5.to(acc_dtype)
-    for tp in range(c.k[0] * c.k[1] * c.k[2]):
-        dt, dh, dw = tp // (c.k[1] * c.k[2]), (tp // c.k[2]) % c.k[1], tp % c.k[2]
-        sel = []
-        for o, s, p, d, n in ((To, c.s[0], c.p[0], dt, c.T), (Ho, c.s[1], c.p[1], dh, c.H), (Wo, c.s[2], c.p[2], dw, c.W)):
-            i = torch.arange(o) * s - p + d
-            sel.append((i >= 0) & (i < n))
-        ot, oh, ow = (m.nonzero().flatten() for m in sel)
-        if not (len(ot) and len(oh) and len(ow)):
-            continue
-        it, ih, iw = ot * c.s[0] - c.p[0] + dt, oh * c.s[1] - c.p[1] + dh, ow * c.s[2] - c.p[2] + dw
-        O = (slice(None), ot[:, None, None], oh[None, :, None], ow[None, None, :])
-        I = (slice(None), it[:, None, None], ih[None, :, None], iw[None, None, :])
-        hit = tap5[O] == tp
-        contrib = torch.where(hit, gy5[O], torch.zeros((), dtype=acc_dtype))
-        add = torch.zeros(start.shape, dtype=acc_dtype)
-        add[I] = contrib
-        acc = torch.where(add != 0, acc + add, acc)        # (an element no window chose keeps its bits, -0.0 included)
-        c1 = torch.zeros(start.shape, dtype=torch.int32)
-        c1[I] = hit.to(torch.int32)
-        cnt += c1
-        mag += add.double().abs()
-    return acc, cnt, mag
-
-
 def pool_x(c, kind, seed):
     """[N, T, H, W, C] float64 test data (CPU)"""
     g = gen(seed)
@@ -267,8 +167,8 @@ def run_pool_fwd(c, dtype, dev, x5, what):
     """x5: [N, T, H, W, C] values representable in dtype.  Launch dv_maxpool3d_fwd, check the frames, return (y, idx, refs)"""
     CP = cp8(c.C)
     M_in, M_out = c.N * c.T * c.H * c.W, c.N * math.prod(T.out_dims(c))
-    x = View(dtype, M_in, c.C, dev, c.sliced, x5.reshape(M_in, c.C))
-    y = View(dtype, M_out, c.C, dev, c.sliced)
+    x = View.sliced(dtype, M_in, c.C, dev, c.sliced, x5.reshape(M_in, c.C))
+    y = View.sliced(dtype, M_out, c.C, dev, c.sliced)
     idx = IdxBuf(M_out, CP, dev)
     d = T.desc(c, dtype, x.ld, y.ld)
     launch('dv_maxpool3d_fwd', C.byref(d), x.ptr, y.ptr, idx.ptr)
@@ -318,8 +218,8 @@ def run_pool_bwd(c, dtype, dev, tap, gy, old, lead=0):
     """dv_maxpool3d_bwd plain (old is None) or DV_ACCUM onto old; returns the dx view"""
     CP = cp8(c.C)
     M_in, M_out = c.N * c.T * c.H * c.W, c.N * math.prod(T.out_dims(c))
-    dy = View(dtype, M_out, c.C, dev, c.sliced, gy.reshape(M_out, CP))
-    dx = View(dtype, M_in, c.C, dev, c.sliced, None if old is None else old.reshape(M_in, CP))
+    dy = View.sliced(dtype, M_out, c.C, dev, c.sliced, gy.reshape(M_out, CP))
+    dx = View.sliced(dtype, M_in, c.C, dev, c.sliced, None if old is None else old.reshape(M_in, CP))
     idx = IdxBuf(M_out, CP, dev, lead, tap)
     d = T.desc(c, dtype, dx.ld, dy.ld)
     launch('dv_maxpool3d_bwd', C.byref(d), dy.ptr, idx.ptr, dx.ptr, 0 if old is None else DV_ACCUM)
@@ -364,16 +264,16 @@ def test_pool_with_idx_at_a_4_byte_offset(gpu, dtype, c):
     for o in (None, old):
         a = run_pool_bwd(c, dtype, gpu, tap, gy, o, lead=0)
         b = run_pool_bwd(c, dtype, gpu, tap, gy, o, lead=4)
-        assert torch.equal(B.bits(a.buf), B.bits(b.buf))
+        assert torch.equal(bits(a.buf), bits(b.buf))
         assert bool(torch.isfinite(a.cols().float()).all()) and float(a.cols().float().abs().max()) > 0
     M_in, M_out = c.N * c.T * c.H * c.W, c.N * math.prod(T.out_dims(c))
-    x = View(dtype, M_in, c.C, gpu, False, pool_x(c, 'gauss', 1).reshape(M_in, c.C))
-    y = View(dtype, M_out, c.C, gpu)
+    x = View.sliced(dtype, M_in, c.C, gpu, False, pool_x(c, 'gauss', 1).reshape(M_in, c.C))
+    y = View.sliced(dtype, M_out, c.C, gpu)
     idx = IdxBuf(M_out, CP, gpu, lead=4)
     d = T.desc(c, dtype, x.ld, y.ld)
     assert rc_of('dv_maxpool3d_fwd', C.byref(d), x.ptr, y.ptr, idx.ptr) == -2
     torch.cuda.synchronize()
-    assert B.is_sentinel(y.buf, dtype) and bool((idx.raw == IDX_SENT).all())
+    assert is_sent(y.buf) and bool((idx.raw == IDX_SENT).all())
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
@@ -403,10 +303,6 @@ def test_signed_zeros(gpu, dtype):
 
 
 # ------------------------------------------------------------------------------------------------------------ BN + ReLU + pool
-def chan(vals, CP, dev, junk=0.625):
-    return B.chan(vals.float().to(dev), CP, dev, junk)
-
-
 class BnPool:
     """dv_bn_apply_maxpool / dv_bn_bwd_reduce_maxpool / dv_bn_bwd_apply_maxpool on one case"""
 
@@ -446,7 +342,7 @@ class BnPool:
             assert bool((scale < 0).any()) and bool((scale == 0).any()) and bool((shift <= 0).any())
         self.x5, self.gy5 = x, gy
         self.mean, self.invstd, self.gamma, self.scale, self.shift = mean, invstd, gamma, scale, shift
-        self.x = View(dtype, self.M, C_, dev, sliced, x.reshape(self.M, C_))
+        self.x = View.sliced(dtype, self.M, C_, dev, sliced, x.reshape(self.M, C_))
         self.p = {k: chan(v, CP, dev) for k, v in (('mean', mean), ('invstd', invstd), ('gamma', gamma), ('scale', scale),
                                                    ('shift', shift))}
         # the fp32 restatement, one operation at a time (torch on the CPU: two roundings), over the CP lanes the kernel sees
@@ -463,7 +359,7 @@ class BnPool:
 
     def forward(self):
         c, CP = self.c, cp8(self.c.C)
-        y = View(self.dtype, self.Mo, c.C, self.dev, self.sliced)
+        y = View.sliced(self.dtype, self.Mo, c.C, self.dev, self.sliced)
         idx = IdxBuf(self.Mo, CP, self.dev)
         launch('dv_bn_apply_maxpool', C.byref(self.desc(y.ld)), self.x.ptr, self.p['scale'].data_ptr(), self.p['shift'].data_ptr(),
                y.ptr, idx.ptr)
@@ -505,15 +401,15 @@ def test_bn_relu_pool_forward(gpu, dtype, kind, c):
         y64, _ = ref_pool_fwd(padded(a64, CP), c)
         xs = ref_pool_fwd(padded((b.x5 * b.scale).abs(), CP), c)[0]          # the largest |x scale| of the window: an upper bound
         bound = 2 * U * (xs + y64) + store_u(dtype) * y64
-        bounded('bn_apply_maxpool y vs float64 [%s]' % ('fp32' if dtype == DV_F32 else 'bf16'),
-                y.cols()[:, :c.C].double().cpu(), y64.reshape(-1, CP)[:, :c.C], bound.reshape(-1, CP)[:, :c.C])
+        bounded(y.cols()[:, :c.C].double().cpu(), y64.reshape(-1, CP)[:, :c.C], bound.reshape(-1, CP)[:, :c.C],
+                'bn_apply_maxpool y vs float64 [%s]' % ('fp32' if dtype == DV_F32 else 'bf16'))
 
 
 def run_bn_pool_backward(b, n_rep, dscale, what):
     c, dtype, dev = b.c, b.dtype, b.dev
     C_, CP, M = c.C, cp8(c.C), b.M
     lib = L.load()
-    dyp = View(dtype, b.Mo, C_, dev, b.sliced, b.gy5.reshape(b.Mo, C_))
+    dyp = View.sliced(dtype, b.Mo, C_, dev, b.sliced, b.gy5.reshape(b.Mo, C_))
     idx = IdxBuf(b.Mo, CP, dev, 0, b.tap)
     sums = torch.zeros(n_rep * 2 * CP, dtype=torch.float32, device=dev)
     d = b.desc(dyp.ld)
@@ -535,15 +431,15 @@ def run_bn_pool_backward(b, n_rep, dscale, what):
         w = int(cnt.max())
         Lc = column_chain(rpb, CP, dtype, 2, ceil_div(nblk, n_rep))
         name = 'bn_bwd_reduce_maxpool %s [%s]' % ('%s', 'fp32' if dtype == DV_F32 else 'bf16')
-        bounded(name % 'sum g', got[0, :C_], ref[0], (Lc + w - 1) * U * mag.sum(0))
+        bounded(got[0, :C_], ref[0], (Lc + w - 1) * U * mag.sum(0), name % 'sum g')
         # one term g * (x - mean) * invstd: the w - 1 additions of the gather, the subtraction, two products.  The subtraction
         # rounds relative to |x - mean| because x and mean are fp32 numbers (Sterbenz or not, one rounding of the difference)
-        bounded(name % 'sum g xhat', got[1, :C_], ref[1], (Lc + w - 1 + 3) * U * (mag * xhat.abs()).sum(0))
+        bounded(got[1, :C_], ref[1], (Lc + w - 1 + 3) * U * (mag * xhat.abs()).sum(0), name % 'sum g xhat')
     # ---- apply: the device's own sums are the input (as for the multi-tensor suite)
     dg0 = torch.arange(C_, dtype=torch.float64) / 4 - 1
     db0 = 2 - torch.arange(C_, dtype=torch.float64) / 8
     dgamma, dbeta = chan(dg0, CP, dev), chan(db0, CP, dev)
-    dx = View(dtype, M, C_, dev, b.sliced)
+    dx = View.sliced(dtype, M, C_, dev, b.sliced)
     inv_count = 1.0 / M
     launch('dv_bn_bwd_apply_maxpool', C.byref(d), dyp.ptr, idx.ptr, b.x.ptr, b.p['mean'].data_ptr(), b.p['invstd'].data_ptr(),
            b.p['gamma'].data_ptr(), b.p['scale'].data_ptr(), b.p['shift'].data_ptr(), sums.data_ptr(), n_rep, inv_count, dscale,
@@ -566,7 +462,7 @@ def run_bn_pool_backward(b, n_rep, dscale, what):
         # the replicas are added in fp32 on the device (n_rep - 1 roundings), the product and the sum round once each
         for nm, t, t0, s in (('dbeta', dbeta, db0, sg), ('dgamma', dgamma, dg0, sgx)):
             rs = sums.view(n_rep, 2, CP)[:, 0 if nm == 'dbeta' else 1, :C_].double().abs().sum(0).cpu()
-            bounded('bn_bwd_apply_maxpool %s' % nm, t[:C_], t0 + dscale * s, U * ((n_rep + 1) * dscale * rs + (t0 + dscale * s).abs()))
+            bounded(t[:C_], t0 + dscale * s, U * ((n_rep + 1) * dscale * rs + (t0 + dscale * s).abs()), 'bn_bwd_apply_maxpool %s' % nm)
     if b.exact and pow2:
         # every product and sum of the kernel's expression is exact on this data: one rounding, the bf16 store
         same_bits(dx.cols()[:, :C_], ref_dx.to(tdt(dtype)).double(), what + ' dx')
@@ -578,8 +474,8 @@ def run_bn_pool_backward(b, n_rep, dscale, what):
         if rep:                                                            # sg / sgx as the kernel adds them: sum |replica| scales it
             rs = sums.view(n_rep, 2, CP).double().abs().sum(0).cpu()[:, :C_]
             bound = bound + U * rep * (k1.abs() * rs[0] * ic + (k1 * b.invstd).abs() * rs[1] * ic * (x.abs() + b.mean.abs()))
-        bounded('bn_bwd_apply_maxpool dx [%s]%s' % ('fp32' if dtype == DV_F32 else 'bf16', ' ill-centred' if 'ill' in what else ''),
-                got_dx, ref_dx, bound)
+        bounded(got_dx, ref_dx, bound,
+                'bn_bwd_apply_maxpool dx [%s]%s' % ('fp32' if dtype == DV_F32 else 'bf16', ' ill-centred' if 'ill' in what else ''))
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
@@ -633,7 +529,7 @@ def run_means_and_gates(dev, dtype, N, S, C_, exact, lead, tag, nan_pads=False):
     dn = 'fp32' if dtype == DV_F32 else 'bf16'
     x, dy, old, gate, dm = gate_data(N, S, C_, dtype, exact, 3 + N + S + C_)
     rows = torch.arange(M) // S
-    xv, dyv = View(dtype, M, C_, dev, True, x), View(dtype, M, C_, dev, False, dy, pitch_pad=8)
+    xv, dyv = View.sliced(dtype, M, C_, dev, True, x), View.sliced(dtype, M, C_, dev, False, dy, pitch_pad=8)
     if nan_pads:
         xv.buf[:, xv.off + C_:xv.off + CP] = float('nan')
         dyv.buf[:, dyv.off + C_:dyv.off + CP] = float('nan')
@@ -648,21 +544,21 @@ def run_means_and_gates(dev, dtype, N, S, C_, exact, lead, tag, nan_pads=False):
     Lc = max(column_chain(S, w * vec(dtype), dtype, 1) for w in {ccv, CV - (chunks - 1) * ccv} if w > 0)
 
     def out_table():
-        return B.f32_sentinel(N * C_ + 8, dev)
+        return sent((N * C_ + 8,), dev)
 
     def elementwise(name, got_view, ref, bound):
         got_view.check_frame(name)
         if bit:
             same_bits(got_view.cols()[:, :C_], ref, '%s %s' % (tag, name))
         else:
-            bounded('%s [%s]' % (name, dn), got_view.cols()[:, :C_], ref, bound + su * ref.abs())
+            bounded(got_view.cols()[:, :C_], ref, bound + su * ref.abs(), '%s [%s]' % (name, dn))
 
     def tab(name, got, ref, bound):
-        assert B.is_sentinel(got[N * C_:], DV_F32), name + ': wrote behind the [N][C] table'
+        assert is_sent(got[N * C_:]), name + ': wrote behind the [N][C] table'
         if bit:
             same_bits(got[:N * C_].view(N, C_), ref, '%s %s' % (tag, name))
         else:
-            bounded('%s [%s]' % (name, dn), got[:N * C_].view(N, C_), ref, bound)
+            bounded(got[:N * C_].view(N, C_), ref, bound, '%s [%s]' % (name, dn))
 
     # dv_spatial_mean: the sum, then * fl(1 / S)
     out = out_table()
@@ -680,7 +576,7 @@ def run_means_and_gates(dev, dtype, N, S, C_, exact, lead, tag, nan_pads=False):
         # one rounding per product, the chain, then 1 - g, (g * .), the final product
         tab('gate_bwd_reduce x_is_output=%d' % xio, out, prod.sum(1) * f, (Lc + 1 + 3) * U * prod.abs().sum(1) * f.abs())
     # dv_gate_scale
-    y = View(dtype, M, C_, dev, True)
+    y = View.sliced(dtype, M, C_, dev, True)
     launch('dv_gate_scale', dtype, xv.ptr, xv.ld, gp, N, S, C_, y.ptr, y.ld)
     torch.cuda.synchronize()
     elementwise('gate_scale', y, x * gate[rows], U * (x * gate[rows]).abs())
@@ -688,14 +584,14 @@ def run_means_and_gates(dev, dtype, N, S, C_, exact, lead, tag, nan_pads=False):
     for o in (None, old):
         fl = 0 if o is None else DV_ACCUM
         sfx = '' if o is None else ' (DV_ACCUM)'
-        dx = View(dtype, M, C_, dev, True, o)
+        dx = View.sliced(dtype, M, C_, dev, True, o)
         launch('dv_gate_bwd_apply', dtype, dyv.ptr, dyv.ld, gp, dp, N, S, C_, dx.ptr, dx.ld, fl)
         torch.cuda.synchronize()
         t1, t2 = dy * gate[rows], dm[rows] / S
         r = t1 + t2
         bnd = U * (2 * t1.abs() + 3 * t2.abs()) + (0 if o is None else U * (o.abs() + r.abs()))
         elementwise('gate_bwd_apply' + sfx, dx, r if o is None else o + r, bnd)
-        dx = View(dtype, M, C_, dev, False, o, pitch_pad=8)
+        dx = View.sliced(dtype, M, C_, dev, False, o, pitch_pad=8)
         launch('dv_spatial_mean_bwd', dtype, dp, N, S, C_, dx.ptr, dx.ld, fl)
         torch.cuda.synchronize()
         elementwise('spatial_mean_bwd' + sfx, dx, t2 if o is None else o + t2, 2 * U * t2.abs() + (0 if o is None else U * (o.abs() + t2.abs())))
@@ -750,13 +646,13 @@ def test_gate_fold_level_against_float64(gpu, dtype):
     M = N * S
     assert int(L.load().dv_spatial_chunks(dtype, N, S, Ct)) == gl['chunks'][0 if dtype == DV_F32 else 1] > 1
     g = gen(77)
-    cat = B.sentinel_like((M, Ct + 16), dtype, gpu)
+    cat = sent((M, Ct + 16), gpu, dtype)
     members, refs, off = [], [], 0
     for k, w in enumerate(gl['widths']):
         x = torch.randint(-3, 4, (M, w), generator=g).double()
         scale = torch.tensor([-1.0, 0.0, 0.5, 1.0, 2.0], dtype=torch.float64)[torch.randint(0, 5, (w,), generator=g)]
         shift = torch.randint(-4, 5, (w,), generator=g).double() / 4
-        members.append(dict(x=View(dtype, M, w, gpu, k in gl['sliced'], x), scale=chan(scale, w, gpu), shift=chan(shift, w, gpu),
+        members.append(dict(x=View.sliced(dtype, M, w, gpu, k in gl['sliced'], x), scale=chan(scale, w, gpu), shift=chan(shift, w, gpu),
                             C=w, M=M, y_ptr=cat.data_ptr() + off * cat.element_size(), ldy=cat.shape[1]))
         refs.append((x * scale + shift).clamp_min(0))
         off += w
@@ -764,16 +660,16 @@ def test_gate_fold_level_against_float64(gpu, dtype):
     offs = [sum(gl['widths'][:k]) for k in range(4)]
     gate_off = torch.tensor(offs, dtype=torch.int32, device=gpu)
     tab = bn_items(members, gpu)
-    mean = B.f32_sentinel(N * Ct + 8, gpu)
+    mean = sent((N * Ct + 8,), gpu)
     launch('dv_gate_mean_bn', dtype, tab.data_ptr(), 4, gate_off.data_ptr(), N, S, Ct, mean.data_ptr())
     torch.cuda.synchronize()
-    assert B.is_sentinel(cat, dtype) and B.is_sentinel(mean[N * Ct:], DV_F32)
+    assert is_sent(cat) and is_sent(mean[N * Ct:])
     same_bits(mean[:N * Ct].view(N, Ct), act.view(N, S, Ct).mean(1), 'gate_mean_bn')
     gate = torch.randint(0, 5, (N, Ct), generator=g).double() / 4
     gt = gate.float().to(gpu)
     launch('dv_gate_scale_bn', dtype, tab.data_ptr(), 4, gate_off.data_ptr(), gt.data_ptr(), N, S, Ct)
     torch.cuda.synchronize()
-    assert B.is_sentinel(cat[:, Ct:], dtype)
+    assert is_sent(cat[:, Ct:])
     same_bits(cat[:, :Ct], act * gate[torch.arange(M) // S], 'gate_scale_bn')
 
 
@@ -788,7 +684,7 @@ def test_sqrtf_accuracy_on_the_device(gpu):
     sq = x * x
     s = (sq[:, 0] + sq[:, 1]).double()
     xd = x.to(gpu)
-    y, nrm = B.f32_sentinel(2 * R, gpu), B.f32_sentinel(R, gpu)
+    y, nrm = sent((2 * R,), gpu), sent((R,), gpu)
     launch('dv_l2norm_fwd', xd.data_ptr(), R, 2, 1e-12, y.data_ptr(), nrm.data_ptr())
     torch.cuda.synchronize()
     rel = ((nrm.double().cpu() - s.sqrt()).abs() / (U * s.sqrt())).max()
@@ -814,10 +710,10 @@ def test_l2norm(gpu, R, D):
         sgn = torch.randint(0, 2, (4 ** k,), generator=g).double() * 2 - 1
         x[r, pos] = sgn * 2.0 ** (r % 5 - 3)
     xd = x.float().to(gpu)
-    y, nrm = B.f32_sentinel(R * D + 8, gpu), B.f32_sentinel(R + 8, gpu)
+    y, nrm = sent((R * D + 8,), gpu), sent((R + 8,), gpu)
     launch('dv_l2norm_fwd', xd.data_ptr(), R, D, eps, y.data_ptr(), nrm.data_ptr())
     torch.cuda.synchronize()
-    assert B.is_sentinel(y[R * D:], DV_F32) and B.is_sentinel(nrm[R:], DV_F32)
+    assert is_sent(y[R * D:]) and is_sent(nrm[R:])
     n_ref = x.pow(2).sum(1).sqrt().clamp_min(eps)
     assert all(math.frexp(float(v))[0] == 0.5 for v in n_ref)
     same_bits(nrm[:R], n_ref, 'l2norm_fwd norm')
@@ -825,23 +721,23 @@ def test_l2norm(gpu, R, D):
     assert float(nrm[0]) == eps and not bool(y[:D].any())
     # the zero row backward: finite, dy * (1 / eps) within 2u
     dy = torch.randn(R, D, generator=g, dtype=torch.float64).float().double()
-    dx = B.f32_sentinel(R * D + 8, gpu)
+    dx = sent((R * D + 8,), gpu)
     dyd = dy.float().to(gpu)
     launch('dv_l2norm_bwd', dyd.data_ptr(), y.data_ptr(), nrm.data_ptr(), R, D, dx.data_ptr())
     torch.cuda.synchronize()
-    assert B.is_sentinel(dx[R * D:], DV_F32) and bool(torch.isfinite(dx[:R * D]).all())
-    bounded('l2norm_bwd zero row', dx[:D], dy[0] / eps, 2 * U * (dy[0] / eps).abs())
+    assert is_sent(dx[R * D:]) and bool(torch.isfinite(dx[:R * D]).all())
+    bounded(dx[:D], dy[0] / eps, 2 * U * (dy[0] / eps).abs(), 'l2norm_bwd zero row')
     # (B) Gaussian rows
     x = torch.randn(R, D, generator=g, dtype=torch.float64).float().double() * 2.0 ** torch.randint(-3, 4, (R, 1), generator=g).double()
     xd = x.float().to(gpu)
-    y, nrm = B.f32_sentinel(R * D, gpu), B.f32_sentinel(R, gpu)
+    y, nrm = sent((R * D,), gpu), sent((R,), gpu)
     launch('dv_l2norm_fwd', xd.data_ptr(), R, D, eps, y.data_ptr(), nrm.data_ptr())
     torch.cuda.synchronize()
     n_ref = x.pow(2).sum(1).sqrt()
     # s: one rounding per square + the chain, all terms positive: relative (Lc + 1) u; sqrt halves it and adds its own error
     rel_n = (Lc + 1) * U / 2 + e_sqrt
-    bounded('l2norm_fwd norm', nrm, n_ref, rel_n * n_ref)
-    bounded('l2norm_fwd y', y.view(R, D), x / n_ref[:, None], (rel_n + U) * (x / n_ref[:, None]).abs())
+    bounded(nrm, n_ref, rel_n * n_ref, 'l2norm_fwd norm')
+    bounded(y.view(R, D), x / n_ref[:, None], (rel_n + U) * (x / n_ref[:, None]).abs(), 'l2norm_fwd y')
     # backward on the device's own y and norm: s = <dy, y>, inv = 1 / norm, dx = (dy - y*s) * inv
     yv, nv = y.view(R, D).double().cpu(), nrm.double().cpu()
     s = (dy * yv).sum(1, keepdim=True)
@@ -849,10 +745,10 @@ def test_l2norm(gpu, R, D):
     ys = (yv * s).abs()
     ref = (dy - yv * s) / nv[:, None]
     bound = (yv.abs() * (Lc + 1) * U * sa + U * ys + 3 * U * (dy.abs() + ys)) / nv[:, None]
-    dx = B.f32_sentinel(R * D, gpu)
+    dx = sent((R * D,), gpu)
     launch('dv_l2norm_bwd', dyd.data_ptr(), y.data_ptr(), nrm.data_ptr(), R, D, dx.data_ptr())
     torch.cuda.synchronize()
-    bounded('l2norm_bwd dx', dx.view(R, D), ref, bound)
+    bounded(dx.view(R, D), ref, bound, 'l2norm_bwd dx')
 
 
 def test_relu_bwd_small(gpu):
@@ -861,11 +757,11 @@ def test_relu_bwd_small(gpu):
     dy = torch.randn(n, generator=g)
     y = torch.randn(n, generator=g).clamp_min(0)
     y[::7] = -0.0
-    dx = B.f32_sentinel(n + 8, gpu)
+    dx = sent((n + 8,), gpu)
     dyd, yd = dy.to(gpu), y.to(gpu)
     launch('dv_relu_bwd_f32', dyd.data_ptr(), yd.data_ptr(), n, dx.data_ptr())
     torch.cuda.synchronize()
-    assert B.is_sentinel(dx[n:], DV_F32)
+    assert is_sent(dx[n:])
     same_bits(dx[:n], torch.where(y > 0, dy, torch.zeros(())).double(), 'relu_bwd')
 
 
@@ -886,7 +782,7 @@ def run_ingest(dev, dtype, N, C_, T_, H, W, ldy, pad, n_seg, extra, with_mean, s
         xbuf[n * sxn:n * sxn + C_ * T_ * H * W] = x[n].reshape(-1)
     xd = xbuf.to(dev)
     Hp, Wp = H + 2 * pad, W + 2 * pad
-    y = B.sentinel_like((N * T_, Hp, Wp, ldy), dtype, dev)
+    y = sent((N * T_, Hp, Wp, ldy), dev, dtype)
     perm = None
     src = x
     if n_seg:
@@ -917,16 +813,16 @@ def run_ingest(dev, dtype, N, C_, T_, H, W, ldy, pad, n_seg, extra, with_mean, s
     got = inner[..., :C_].reshape(N, T_, H, W, C_).permute(0, 4, 1, 2, 3)
     name = 'ingest' + ('_pad' if padded_entry else '')
     if with_mean:
-        bounded('%s normalised [%s]' % (name, 'fp32' if dtype == DV_F32 else 'bf16'), got, ref, bound + store_u(dtype) * ref.abs())
+        bounded(got, ref, bound + store_u(dtype) * ref.abs(), '%s normalised [%s]' % (name, 'fp32' if dtype == DV_F32 else 'bf16'))
     else:
         want = src.to(tdt(dtype))                          # fp32: the bits; bf16: torch's round-to-nearest-even cast
-        assert torch.equal(B.bits(got.contiguous().cpu()), B.bits(want.contiguous())), name + ': not a bit-exact copy / RNE cast'
+        assert torch.equal(bits(got.contiguous().cpu()), bits(want.contiguous())), name + ': not a bit-exact copy / RNE cast'
     assert bool((inner[..., C_:4] == 0).all()), name + ': lanes [C, 4) not zero'
-    assert B.is_sentinel(inner[..., 4:], dtype), name + ': lanes [4, ldy) written'
+    assert is_sent(inner[..., 4:]), name + ': lanes [4, ldy) written'
     if pad:
         border = torch.ones((Hp, Wp), dtype=torch.bool, device=dev)
         border[pad:pad + H, pad:pad + W] = False
-        assert B.is_sentinel(y[:, border], dtype), name + ': the border was written'
+        assert is_sent(y[:, border]), name + ': the border was written'
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
@@ -942,12 +838,12 @@ def test_ingest(gpu, dtype, case):
 
 def test_ingest_refuses_segments_that_do_not_divide_t(gpu):
     x = torch.zeros(2 * 3 * 4 * 5 * 7, device=gpu)
-    y = B.sentinel_like((8, 5, 7, 4), DV_F32, gpu)
+    y = sent((8, 5, 7, 4), gpu, DV_F32)
     perm = torch.zeros(2, 3, dtype=torch.int32, device=gpu)
     args = (DV_F32, x.data_ptr(), y.data_ptr(), 2, 3, 4, 5, 7, 3 * 4 * 5 * 7, 4, 0, 0, perm.data_ptr(), 3)
     assert rc_of('dv_ingest_ncdhw', *args) == -1 and rc_of('dv_ingest_ncdhw_pad', *args, 0) == -1
     torch.cuda.synchronize()
-    assert B.is_sentinel(y, DV_F32)
+    assert is_sent(y)
 
 
 # ------------------------------------------------------------------------------------------------------------ grid wrap
@@ -965,8 +861,8 @@ def test_grid_wrap_rowscale(gpu, mode):
     x, dy, old, gate, dm = gate_data(N, S, C_, DV_F32, True, 50 + mode)
     rows = torch.arange(M) // S
     gt, dmt = gate.float().to(gpu), dm.float().to(gpu)
-    a = View(DV_F32, M, C_, gpu, False, x)
-    o = View(DV_F32, M, C_, gpu, False, old if mode else None)
+    a = View.sliced(DV_F32, M, C_, gpu, False, x)
+    o = View.sliced(DV_F32, M, C_, gpu, False, old if mode else None)
     if mode == 0:
         launch('dv_gate_scale', DV_F32, a.ptr, a.ld, gt.data_ptr(), N, S, C_, o.ptr, o.ld)
         ref = x * gate[rows]
@@ -986,11 +882,11 @@ def test_grid_wrap_relu_bwd(gpu):
     g = gen(3)
     dy = torch.randint(-4, 5, (n,), generator=g).float()
     y = torch.randint(-1, 2, (n,), generator=g).float()
-    dx = B.f32_sentinel(n + 8, gpu)
+    dx = sent((n + 8,), gpu)
     dyd, yd = dy.to(gpu), y.to(gpu)
     launch('dv_relu_bwd_f32', dyd.data_ptr(), yd.data_ptr(), n, dx.data_ptr())
     torch.cuda.synchronize()
-    assert B.is_sentinel(dx[n:], DV_F32)
+    assert is_sent(dx[n:])
     same_bits(dx[:n], torch.where(y > 0, dy, torch.zeros(())).double(), 'relu_bwd over the cap')
 
 

@@ -6,7 +6,7 @@ Everything the kernels produce is an integer or a fixed sequence of IEEE operati
 indices, counts and hits as integers, the list values and the average precision bit for bit (AP = ascending sum of
 double(i + 1) / double(rank_i), one division by double(P): the model does the same operations in Python floats).
 
-Conventions (those of tests/test_loss_gemm_optim_gpu.py, whose helpers are imported): the similarity block sits in a buffer of
+Conventions (those of tests/test_loss_gemm_optim_gpu.py; the helpers are tests/checks.py's): the similarity block sits in a buffer of
 pitch ld > n_cols whose padding holds NaN (a kernel that read it would count it); lists, counts and outputs sit in buffers
 filled with a NaN bit pattern no kernel produces, two rows longer than needed and with pitches larger than needed (ldp = P_max +
 3 unless P_max is the cap, ldh = ldp + 4); after every call the rows >= R, the list and rank slots >= P, the buckets > P must
@@ -26,8 +26,10 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import ops  # noqa: E402
 from tests import rankeval_reference as M  # noqa: E402
-from tests.test_knn_gpu import _child, chunks_of, grid_rows, knn_eval_case, unit_gauss  # noqa: E402
-from tests.test_loss_gemm_optim_gpu import gemm_bound, gemm_chain, is_sent, sent  # noqa: E402
+from tests.chains import gemm_bound, gemm_chain  # noqa: E402
+from tests.checks import child as _child, is_sent, sent  # noqa: E402
+from tests.dataset_support import write_dataset  # noqa: E402
+from tests.eval_support import chunks_of, grid_rows, knn_eval_case, unit_gauss  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF, NAN = math.inf, math.nan
@@ -465,7 +467,6 @@ def test_ranking_eval_within_by_construction(gpu):
 
 # --------------------------------------------------------------------------------------------------- 9. the driver, one child
 def test_cli_retrieval_with_map(gpu, tmp_path_factory):
-    from tests.test_frame_dataset_host import write_dataset
     d = tmp_path_factory.mktemp('map_cli')
     split, frame = write_dataset(str(d / 'data'), videos=((0, 40), (0, 9), (1, 70)), rows=830, sizes=[(90, 120), (120, 90), (80, 100)])
     os.makedirs(str(d / 'run' / 'model'))

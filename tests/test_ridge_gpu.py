@@ -28,22 +28,10 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib, ops  # noqa: E402
 from tests import ridge_reference as R  # noqa: E402
+from tests.checks import F64, is_sent, lib, sent  # noqa: E402
 
 E52 = 2.0 ** -52
-SENT64 = 0x7ff8123456789abc                      # a NaN no kernel produces
 SLAB = R.SLAB
-
-
-def lib():
-    return _lib.load()
-
-
-def sent64(shape, dev):
-    return torch.full(shape, SENT64, dtype=torch.int64, device=dev).view(torch.float64)
-
-
-def is_sent64(t):
-    return t.numel() == 0 or bool((t.contiguous().view(torch.int64) == SENT64).all())
 
 
 def ratio(err, bound, what):
@@ -68,16 +56,16 @@ def run_gram(dev, z, label, C, G, B, accumulate, pad=3):
     ld = torch.from_numpy(np.asarray(label, dtype=np.int32)).to(dev)
     nbytes = lib().dv_ridge_gram_workspace(n, D, C)
     assert nbytes == R.gram_workspace_bytes(n, D, C)
-    ws = sent64((nbytes // 8 + 4,), dev)
+    ws = sent((nbytes // 8 + 4,), dev, F64)
     _lib.check(lib().dv_ridge_gram_f64(zd.data_ptr(), D + pad, n, D, ld.data_ptr(), C, G.data_ptr(), G.shape[1], B.data_ptr(), B.shape[1],
                                        accumulate, ws.data_ptr(), ops.stream_ptr()), 'dv_ridge_gram_f64')
     torch.cuda.synchronize()
-    assert is_sent64(ws[nbytes // 8:])
+    assert is_sent(ws[nbytes // 8:])
 
 
 def gram_buffers(dev, D, C):
     """[Da + 1][Da + 2] and [Da + 1][C + 2] of sentinels: one row and two columns more than the entry may write"""
-    return sent64((D + 2, D + 3), dev), sent64((D + 2, C + 2), dev)
+    return sent((D + 2, D + 3), dev, F64), sent((D + 2, C + 2), dev, F64)
 
 
 def labels_with_skips(rng, n, C):
@@ -109,12 +97,12 @@ def test_gram_exact_integers(gpu, n, D, C):
     G1, B1 = R.gram_ref(np.nan_to_num(z1), l1, C)
     assert np.abs(G1).max() < 2 ** 40
     assert (G[:Da, :Da].cpu().numpy() == G1).all() and (B[:Da, :C].cpu().numpy() == B1).all()
-    assert is_sent64(G[Da:]) and is_sent64(G[:, Da:]) and is_sent64(B[Da:]) and is_sent64(B[:, C:])
+    assert is_sent(G[Da:]) and is_sent(G[:, Da:]) and is_sent(B[Da:]) and is_sent(B[:, C:])
     assert G1[D, D] == ((l1 >= 0) & (l1 < C)).sum()
     run_gram(gpu, z2, l2, C, G, B, 1)            # a second row set on top
     G2, B2 = R.gram_ref(np.nan_to_num(z2), l2, C)
     assert (G[:Da, :Da].cpu().numpy() == G1 + G2).all() and (B[:Da, :C].cpu().numpy() == B1 + B2).all()
-    assert is_sent64(G[Da:]) and is_sent64(G[:, Da:]) and is_sent64(B[Da:]) and is_sent64(B[:, C:])
+    assert is_sent(G[Da:]) and is_sent(G[:, Da:]) and is_sent(B[Da:]) and is_sent(B[:, C:])
 
 
 @pytest.mark.parametrize('n,D,C', [(300, 38, 5), (2 * SLAB + 9, 130, 101), (5 * SLAB, 513, 7)])
@@ -144,7 +132,7 @@ def run_solve(dev, G, B, lam, n_pen, pad=2):
     Da, C = B.shape
     Gd = torch.from_numpy(np.triu(np.full((Da, Da), np.nan), 1) + np.tril(G)).to(dev)      # the upper triangle is never read
     Bd = torch.from_numpy(np.ascontiguousarray(B)).to(dev)
-    chol, W = sent64((Da + 1, Da + pad), dev), sent64((Da + 1, C + pad), dev)
+    chol, W = sent((Da + 1, Da + pad), dev, F64), sent((Da + 1, C + pad), dev, F64)
     info = torch.full((2,), 77, dtype=torch.int32, device=dev)
     _lib.check(lib().dv_ridge_solve_f64(Gd.data_ptr(), Da, Da, n_pen, lam, Bd.data_ptr(), C, C, W.data_ptr(), C + pad, chol.data_ptr(),
                                         Da + pad, info.data_ptr(), ops.stream_ptr()), 'dv_ridge_solve_f64')
@@ -155,8 +143,8 @@ def run_solve(dev, G, B, lam, n_pen, pad=2):
 
 def untouched(chol, W, Da, C):
     upper = torch.triu(torch.ones(Da, Da, dtype=torch.bool, device=chol.device), 1)
-    return (is_sent64(chol[:Da, :Da][upper]) and is_sent64(chol[Da:]) and is_sent64(chol[:, Da:]) and is_sent64(W[Da:]) and
-            is_sent64(W[:, C:]))
+    return (is_sent(chol[:Da, :Da][upper]) and is_sent(chol[Da:]) and is_sent(chol[:, Da:]) and is_sent(W[Da:]) and
+            is_sent(W[:, C:]))
 
 
 @pytest.mark.parametrize('Da,C', [(1, 1), (17, 3), (64, 2), (65, 33), (66, 65), (130, 7), (257, 5)])

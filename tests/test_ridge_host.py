@@ -20,6 +20,7 @@ import torch
 
 from tests import abi_coverage as A
 from tests import ridge_reference as R
+from tests.checks import lib
 from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,11 +34,6 @@ RIDGE_COVERAGE = {
     'dv_ridge_gram_f64': ('test_ridge_gpu.py', A.FLOAT64),
     'dv_ridge_solve_f64': ('test_ridge_gpu.py', A.FLOAT64),
 }
-
-
-def lib():
-    from dualvar_amd import _lib
-    return _lib.load()
 
 
 def test_ridge_header_table_and_library_agree():

@@ -27,37 +27,21 @@ pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib, ops  # noqa: E402
 from tests import spectrum_reference as R  # noqa: E402
+from tests.checks import F64, equal_bits, is_sent, lib, sent  # noqa: E402
 
 EPS = R.EPS
 U = 2.0 ** -24
-SENT64 = 0x7ff8123456789abc                      # a NaN no kernel produces
-
-
-def lib():
-    return _lib.load()
-
-
-def sent64(shape, dev):
-    return torch.full(shape, SENT64, dtype=torch.int64, device=dev).view(torch.float64)
-
-
-def is_sent64(t):
-    return t.numel() == 0 or bool((t.contiguous().view(torch.int64) == SENT64).all())
 
 
 def framed(x, dev, rows=2, cols=3):
     """x [r][c] float64 numpy -> a device buffer [r + rows][c + cols] of sentinels with x in its corner"""
-    buf = sent64((x.shape[0] + rows, x.shape[1] + cols), dev)
+    buf = sent((x.shape[0] + rows, x.shape[1] + cols), dev, F64)
     buf[:x.shape[0], :x.shape[1]] = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     return buf
 
 
 def frame_ok(buf, r, c):
-    return is_sent64(buf[:r, c:]) and is_sent64(buf[r:])
-
-
-def same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
+    return is_sent(buf[:r, c:]) and is_sent(buf[r:])
 
 
 @pytest.fixture(scope='module')
@@ -78,8 +62,8 @@ def test_covariance_exact_integers(gpu, D):
     mean, cov = SP.covariance(torch.from_numpy(z).to(gpu))
     want_mean, want = R.cov_from_gram(R.gram_of(z))
     assert cov.dtype == torch.float64 and tuple(cov.shape) == (D, D) and tuple(mean.shape) == (D,)
-    assert same_bits(cov.cpu(), torch.from_numpy(want)) and same_bits(mean.cpu(), torch.from_numpy(want_mean))
-    assert same_bits(cov, cov.t())
+    assert equal_bits(cov.cpu(), torch.from_numpy(want)) and equal_bits(mean.cpu(), torch.from_numpy(want_mean))
+    assert equal_bits(cov, cov.t())
     assert np.array_equal(want, R.cov_of(z))                   # and that is the covariance
 
 
@@ -89,12 +73,12 @@ def test_covariance_random_within_four_roundings(gpu):
     n, D = 333, 130
     z = np.random.RandomState(1).randn(n, D).astype(np.float32)
     G = R.gram_of(z)
-    Gd, Cd = framed(G, gpu), sent64((D + 2, D + 5), gpu)
-    md = sent64((D + 3,), gpu)
+    Gd, Cd = framed(G, gpu), sent((D + 2, D + 5), gpu, F64)
+    md = sent((D + 3,), gpu, F64)
     _lib.check(lib().dv_spectrum_cov_f64(Gd.data_ptr(), Gd.shape[1], D, Cd.data_ptr(), Cd.shape[1], md.data_ptr(), ops.stream_ptr()),
                'dv_spectrum_cov_f64')
     torch.cuda.synchronize()
-    assert frame_ok(Cd, D, D) and is_sent64(md[D:])
+    assert frame_ok(Cd, D, D) and is_sent(md[D:])
     cov, mean = Cd[:D, :D].cpu().numpy(), md[:D].cpu().numpy()
     Gl = G.astype(np.longdouble)
     s, nn = Gl[D, :D], Gl[D, D]
@@ -142,7 +126,7 @@ def test_eigh_jacobi_is_deterministic_and_reports_a_nan(gpu):
         A = torch.from_numpy(R.cases()[name]).to(gpu)
         l1, c1, i1 = SP.eigh_jacobi(A)
         l2, c2, i2 = SP.eigh_jacobi(A.clone())
-        assert same_bits(l1, l2) and same_bits(c1, c2) and i1 == i2
+        assert equal_bits(l1, l2) and equal_bits(c1, c2) and i1 == i2
     _, _, capped = SP.eigh_jacobi(torch.from_numpy(R.cases()['n65']).to(gpu), max_sweeps=2)
     assert capped == dict(capped, sweeps=2, converged=False) and capped['rotations'] > 0
     bad = R.cases()['n7'].copy()
@@ -168,13 +152,13 @@ def test_three_rounds_of_a_wide_matrix(gpu, K, n):
     norm2 = norm2_from_below(A)
     s = ops.stream_ptr()
     Ad = torch.from_numpy(A).to(gpu)
-    W, V = sent64((n + 2, n + 3), gpu), sent64((n + 2, n + 5), gpu)
-    scale, stat = sent64((3,), gpu), sent64((m + 4,), gpu)
+    W, V = sent((n + 2, n + 3), gpu, F64), sent((n + 2, n + 5), gpu, F64)
+    scale, stat = sent((3,), gpu, F64), sent((m + 4,), gpu, F64)
     _lib.check(lib().dv_spectrum_init_f64(Ad.data_ptr(), n, n, W.data_ptr(), W.shape[1], V.data_ptr(), V.shape[1], scale.data_ptr(), s),
                'dv_spectrum_init_f64')
-    assert same_bits(W[:n, :n], Ad) and same_bits(V[:n, :n], torch.eye(n, dtype=torch.float64, device=gpu))
+    assert equal_bits(W[:n, :n], Ad) and equal_bits(V[:n, :n], torch.eye(n, dtype=torch.float64, device=gpu))
     fro = float(scale[0])
-    assert abs(fro - np.linalg.norm(A)) <= (n * n // 256 + 10) * EPS * fro and is_sent64(scale[1:])
+    assert abs(fro - np.linalg.norm(A)) <= (n * n // 256 + 10) * EPS * fro and is_sent(scale[1:])
     assert lib().dv_spectrum_rounds(n) == m - 1
     rotated = 0
     for r in range(3):
@@ -183,7 +167,7 @@ def test_three_rounds_of_a_wide_matrix(gpu, K, n):
                                                 stat.data_ptr(), s), 'dv_spectrum_rounds_f64')
         torch.cuda.synchronize()
         # the row that sits out: row r is paired with index m - 1 = n, which does not exist
-        assert same_bits(W[r, :n], before_w) and same_bits(V[r, :n], before_v)
+        assert equal_bits(W[r, :n], before_w) and equal_bits(V[r, :n], before_v)
         p, q = R.round_pairs(n, r)
         assert p.size == m // 2 - 1
         Wn = W[:n, :n].cpu().numpy()
@@ -192,7 +176,7 @@ def test_three_rounds_of_a_wide_matrix(gpu, K, n):
         print('n = %d round %d: pair orthogonality err / bound = %.4f' % (n, r, float((dot / lim).max())))
         assert (dot <= lim).all()
         rotated += p.size
-    assert frame_ok(W, n, n) and frame_ok(V, n, n) and is_sent64(stat[m:]) and is_sent64(scale[1:])
+    assert frame_ok(W, n, n) and frame_ok(V, n, n) and is_sent(stat[m:]) and is_sent(scale[1:])
     st = stat[:m].cpu().numpy().reshape(-1, 2)
     assert st[0].tolist() == [0.0, 0.0]                        # slot 0 held the bye in every round
     assert st[:, 1].sum() == rotated and (st[1:, 1] == 3).all()                  # round_lo > 0 does not clear
@@ -202,10 +186,10 @@ def test_three_rounds_of_a_wide_matrix(gpu, K, n):
     prod = float(np.abs(Wn - Vn @ A).max()) / (K['resid'] * EPS * n * norm2)
     print('n = %d: |V V^T - I| err / bound = %.4f, |W - V A| err / bound = %.4f' % (n, orth, prod))
     assert orth <= 1 and prod <= 1
-    lam = sent64((n + 3,), gpu)
+    lam = sent((n + 3,), gpu, F64)
     _lib.check(lib().dv_spectrum_values_f64(W.data_ptr(), W.shape[1], V.data_ptr(), V.shape[1], n, lam.data_ptr(), s), 'dv_spectrum_values_f64')
     torch.cuda.synchronize()
-    assert is_sent64(lam[n:])
+    assert is_sent(lam[n:])
     want = (Vn * Wn).sum(1) / (Vn * Vn).sum(1)
     assert (np.abs(lam[:n].cpu().numpy() - want) <= (n // 256 + 24) * EPS * (np.abs(Vn) * np.abs(Wn)).sum(1)).all()
 
@@ -219,13 +203,13 @@ def test_rounds_clear_stat_only_from_round_zero(gpu):
     for split in (False, True):
         Ad = torch.from_numpy(A).to(gpu)
         W, V = torch.empty_like(Ad), torch.empty_like(Ad)
-        scale, stat = torch.empty(1, dtype=torch.float64, device=gpu), sent64((8,), gpu)
+        scale, stat = torch.empty(1, dtype=torch.float64, device=gpu), sent((8,), gpu, F64)
         _lib.check(lib().dv_spectrum_init_f64(Ad.data_ptr(), 8, 8, W.data_ptr(), 8, V.data_ptr(), 8, scale.data_ptr(), s), 'dv_spectrum_init_f64')
         for lo, hi in ([(r, r + 1) for r in range(7)] if split else [(0, 7)]):
             _lib.check(lib().dv_spectrum_rounds_f64(W.data_ptr(), 8, V.data_ptr(), 8, 8, lo, hi, scale.data_ptr(), stat.data_ptr(), s),
                        'dv_spectrum_rounds_f64')
         out.append((W.clone(), V.clone(), stat.clone()))
-    assert all(same_bits(a, b) for a, b in zip(*out))
+    assert all(equal_bits(a, b) for a, b in zip(*out))
     assert float(out[0][2][1::2].sum()) == 28                  # every pair of a full 8 x 8 matrix rotates in the first sweep
 
 
@@ -340,4 +324,4 @@ def test_classifier_spectrum_branch_writes_its_three_files(gpu, planted, tmp_pat
     assert train['video_share'][0] >= 0.9 and len(train['video_share']) == 40
     saved = torch.load(str(tmp_path / 'ucf101_spectrum.pth.tar'), weights_only=True)
     assert saved['components'].shape == (40, 40) and saved['components'].dtype == torch.float64
-    assert same_bits(saved['eigenvalues'], want['eigenvalues'].cpu()) and same_bits(saved['mean'], want['mean'].cpu())
+    assert equal_bits(saved['eigenvalues'], want['eigenvalues'].cpu()) and equal_bits(saved['mean'], want['mean'].cpu())

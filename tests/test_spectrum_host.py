@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from tests import spectrum_reference as R
+from tests.checks import lib
 from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,11 +35,6 @@ def __getattr__(name):
     if name in ('MODEL_RATIOS', 'MODEL_INFO'):
         return R.model_ratios()[name == 'MODEL_INFO']
     raise AttributeError(name)
-
-
-def lib():
-    from dualvar_amd import _lib
-    return _lib.load()
 
 
 def test_spectrum_header_table_and_library_agree():

@@ -3,7 +3,7 @@ against the float64 reference of tests/tsne_reference.py, which is written from 
 
 Conventions (those of tests/test_variance_gpu.py): outputs sit in buffers filled with a NaN bit pattern no kernel produces and
 larger than needed; after every call everything beyond what the header says is written must still hold it.  Lists come with
-ldk = k1 and ldk = k1 + 3.  u = 2^-24; E_EXPF, E_LOG, E_LOG1P are the device-function figures of tests/test_loss_gemm_optim_gpu.py.
+ldk = k1 and ldk = k1 + 3.  u = 2^-24; E_EXPF, E_LOG, E_LOG1P are the device-function figures of tests/chains.py.
 
 Bounds, each from the header's expressions (first order, times 1.01 for the higher orders):
   perplexity  e_j is formed by the reference in fp32 with the header's own operations: the same bits.  At the returned beta, in
@@ -46,43 +46,23 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from dualvar_amd import _lib, ops  # noqa: E402
+from dualvar_amd import ops  # noqa: E402
 from tests import tsne_reference as R  # noqa: E402
-from tests.test_loss_gemm_optim_gpu import E_EXPF, E_LOG, E_LOG1P, TINY, U, is_sent, sent  # noqa: E402
+from tests.chains import E_EXPF, E_LOG, E_LOG1P, TINY  # noqa: E402
+from tests.checks import U, Ratios, is_sent, lib, report_fixture, sent  # noqa: E402
+from tests.dataset_support import write_dataset  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U64 = 2.0 ** -53
 SLACK = 1.01
 TILE = 256                           # DV_TSNE_ROWS = DV_TSNE_TILE
-WORST = {}
-
-
-def lib():
-    return _lib.load()
-
-
-def ratio(err, bound, what):
-    """largest err / bound over the elements; where the bound is 0 the error must be 0"""
-    err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
-    assert np.isfinite(err).all(), what + ': non-finite output'
-    zero = bound == 0
-    assert (err[zero] == 0).all(), what + ': error where the bound is exactly 0'
-    r = float((err[~zero] / bound[~zero]).max()) if (~zero).any() else 0.0
-    key = what.split(' ')[0]
-    WORST[key] = max(WORST.get(key, 0.0), r)
-    assert r <= 1.0, '%s: err / bound = %.3f' % (what, r)
-    return r
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _report_worst():
-    yield
-    print('\nlargest err / bound per quantity:')
-    for k in sorted(WORST):
-        print('  %-28s %.3f' % (k, WORST[k]))
+WORST = Ratios()
+ratio = WORST.ratio
+_report_worst = report_fixture(WORST, 28)
 
 
 def sent64(count, dev):
+    """float64 words that hold the int32 sentinel twice: their frames are checked through int32 views"""
     return sent((count, 2), dev, torch.int32).view(torch.float64).reshape(count)
 
 
@@ -457,7 +437,6 @@ def test_end_to_end_clusters(gpu):
 
 # ------------------------------------------------------------------------------------------------------- the driver, one child
 def test_cli_retrieval_with_tsne(gpu, tmp_path_factory):
-    from tests.test_frame_dataset_host import write_dataset
     d = tmp_path_factory.mktemp('tsne_cli')
     split, frame = write_dataset(str(d / 'data'), videos=((0, 40), (0, 9), (1, 70)), rows=830, sizes=[(90, 120), (120, 90), (80, 100)])
     os.makedirs(str(d / 'run' / 'model'))

@@ -16,6 +16,7 @@ import torch
 
 from tests import abi_coverage as A
 from tests import tsne_reference as R
+from tests.checks import lib
 from tests.util import check_header_binding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,11 +46,6 @@ def test_tsne_header_table_and_library_agree():
         assert kind in A.KINDS, (name, kind)
         assert re.search(r"ops\.call\('%s'|lib\.%s\(|lib\(\)\.%s\(" % (name, name, name), open(os.path.join(ROOT, 'tests', fname)).read()), \
             '%s is not called by tests/%s' % (name, fname)
-
-
-def lib():
-    from dualvar_amd import _lib
-    return _lib.load()
 
 
 PERP_OK = dict(top_val=X, top_idx=X, ldk=8, n=5, k1=8, row0=0, perplexity=2.0, p=X, beta=X)

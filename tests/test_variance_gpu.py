@@ -1,7 +1,7 @@
 """The streaming pair statistics (dv_pairstat_accum_f32), their host module (dualvar_amd/utils/variance.py) and
 `classifier.py --retrieval --variance` against float64 references written here from include/dualvar_pairstat.h.
 
-Conventions (those of tests/test_loss_gemm_optim_gpu.py, whose helpers are imported): the state sits in buffers filled with a NaN
+Conventions (those of tests/test_loss_gemm_optim_gpu.py; the helpers are tests/checks.py's): the state sits in buffers filled with a NaN
 bit pattern no kernel produces and larger than needed (a fourth row behind hist / sums / ext, ldh = bins + 3, 64 bytes behind the
 workspace): after every call everything beyond hist[c][0..bins], sums [3][4] and ext [3][2] must still hold it.  The similarity
 carries NaN in sim[:, n_cols:ld).  Three layouts: ld = n_cols on an aligned base (16-byte loads iff n_cols % 4 == 0),
@@ -24,11 +24,10 @@ add exactly in double), sum s^2 0.296, sum w 0.407 (R = 1, n = 63; 0.06 on the 1
 std 0.001, min 0.057, max 0.046, sum w 0.004; 10 of 16 770 pairs undecidable at a bin edge with centring, 0 without, 1 of 3 900
 in the cross case.  The whole file takes 17 s, 11 s of it the two classifier.py children; every other test is below 0.5 s.
 """
+import functools
 import json
 import math
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -36,14 +35,20 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from dualvar_amd import _lib, ops  # noqa: E402
-from tests.test_loss_gemm_optim_gpu import E_EXPF, U, f32, gemm_bound, gemm_chain, is_sent, same_bits, sent, within  # noqa: E402
+from tests import checks  # noqa: E402
+from tests.chains import E_EXPF, gemm_bound, gemm_chain  # noqa: E402
+from tests.checks import U, Ratios, child as _child, f32, is_sent, sent  # noqa: E402
+from tests.dataset_support import write_dataset  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = math.inf
 U64 = 2.0 ** -53
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
 NO_SELF = -(1 << 40)
-RATIO = {}
+RATIO = Ratios()                   # cleared per test: each prints its own figures
+within = RATIO.within
+# bit for bit against float64: the reference must be an fp32 number; + 0.0 on both sides only folds -0 into +0
+same_bits = functools.partial(checks.same_bits, ref_exact_in=torch.float32, signed_zeros=False)
 
 
 # --------------------------------------------------------------------------------------------------------------- reference
@@ -115,7 +120,10 @@ class State:
         assert self.hist.shape == (4, self.ldh) and self.sums.shape == (4, 4)
 
     def frame_ok(self):
-        return is_sent(self.hist[3:]) and is_sent(self.hist[:3, self.bins + 1:]) and is_sent(self.sums[3:]) and is_sent(self.ext[3:])
+        """(the 8-byte words hold the int32 sentinel twice: they are checked through int32 views)"""
+        w32 = lambda t: t.contiguous().view(torch.int32)      # noqa: E731
+        return (is_sent(w32(self.hist[3:])) and is_sent(w32(self.hist[:3, self.bins + 1:])) and is_sent(w32(self.sums[3:]))
+                and is_sent(self.ext[3:]))
 
     def bits(self):
         """the whole state as integers, for bit comparisons"""
@@ -132,8 +140,7 @@ class State:
         self.check_exact(ref, what)
         got = self.sums[:3, :3].cpu()
         for k, name in enumerate(('sum_s', 'sum_s2', 'sum_w')):
-            r = within(got[:, k], ref['sums'][:, k], ref['bound'][:, k], 'accum.%s %s' % (name, what), quiet=True)
-            RATIO['accum.' + name] = max(RATIO.get('accum.' + name, 0.0), r)
+            within(got[:, k], ref['sums'][:, k], ref['bound'][:, k], 'accum.%s %s' % (name, what), key='accum.' + name, quiet=True)
 
 
 def layout(s, kind, dev):
@@ -506,22 +513,7 @@ def test_variance_eval_known_by_construction(gpu):
 
 
 # --------------------------------------------------------------------------------------------------- 5. the driver, two children
-STATE = {}
-
-
-def _child(argv, cwd, timeout):
-    """one GPU child process under its own timeout; a failure marks the chain as broken"""
-    assert not STATE.get('broken'), 'an earlier child failed or died: no further GPU child is started'
-    STATE['broken'] = True
-    r = subprocess.run([sys.executable] + argv, capture_output=True, text=True, timeout=timeout, cwd=cwd)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    STATE['broken'] = False
-    return out
-
-
 def test_cli_retrieval_with_variance(gpu, tmp_path_factory):
-    from tests.test_frame_dataset_host import write_dataset
     d = tmp_path_factory.mktemp('variance_cli')
     split, frame = write_dataset(str(d / 'data'), videos=((0, 40), (0, 9), (1, 70)), rows=830, sizes=[(90, 120), (120, 90), (80, 100)])
     os.makedirs(str(d / 'run' / 'model'))

@@ -64,6 +64,13 @@ def rel_err(got, ref):
     return float(np.max(np.abs(got - ref)) / (np.max(np.abs(ref)) + 1e-12))
 
 
+def _hue_matches(q, want_u8):
+    """floor(255 * x) == the reference's uint8 result; a float within rounding of an integer may truncate either way"""
+    diff = np.abs(np.floor(q) - want_u8.astype(np.float64))
+    near = np.abs(q - np.round(q)) < 2e-3
+    return int(((diff > 0) & ~((diff <= 1) & near)).sum()), int(((diff > 0) & near).sum())
+
+
 def grad_summary(model, P):
     sd = model.state_dict(keep_vars=True)
     out = {}
