@@ -394,15 +394,56 @@ __device__ __forceinline__ void ordered_fold(float* __restrict__ ws, uint32_t bi
   clear_ticket(tick + ngrp);
 }
 
-template <typename T, bool GATE = false>
-__device__ __forceinline__ void bn_bwd_reduce_body(const T* __restrict__ dy, int lddy, const T* __restrict__ y, int ldy,
+// Where a BatchNorm-backward pass takes dL/dy from.  load() issues the source's loads for the V channels at (row r, c0): g
+// itself, or what finish() forms it from in registers once the body has issued its own loads of y / x.  kRows: the rows
+// column_reduce keeps in flight (0: its default).  kPooled: see PooledDy.
+template <typename T>
+struct PlainDy {
+  static constexpr int V = DT<T>::VEC, kRows = 0;
+  static constexpr bool kPooled = false;
+  struct Pend {};
+  const T* dy; int lddy;
+  __device__ __forceinline__ void load(int64_t r, int c0, float (&g)[V], Pend&) const { Pack16<T>::load(dy + r * lddy + c0, g); }
+  __device__ __forceinline__ void finish(int64_t, int, float (&)[V], Pend&) const {}
+};
+
+// dL/dy behind a self-gating scale, as gate_bwd_apply would have left it in dy (ga.g == nullptr: the plain dy).
+// (half the rows in flight -- two more vectors per row -- which keeps the registers at the plain kernel's occupancy; measured,
+// 2 / 3 / 4 rows in flight run the step's gated reduces in 601 / 611 / 611 us)
+// ROW_FIRST (the reduce): the gate's row is issued before dy -- these loads hit in L1 / L2 and come back at once; issued behind
+// dy and x they cost 15 us more per step.  The apply issues them last, where they are not held across its other loads.
+template <typename T, bool ROW_FIRST>
+struct GatedDy {
+  static constexpr int V = DT<T>::VEC, kRows = V == 4 ? 2 : 1;
+  static constexpr bool kPooled = false;
+  struct Pend { float gv[V], dv[V]; };
+  const T* dy; int lddy; GateOnLoad ga;
+  __device__ __forceinline__ void gate_row(int64_t r, int c0, Pend& p) const {
+    const size_t go = (size_t)fd_div((uint32_t)r, ga.fS) * ga.ldg;
+    load_params<V>(ga.g + go, c0, p.gv);
+    load_params<V>(ga.dm + go, c0, p.dv);
+  }
+  __device__ __forceinline__ void load(int64_t r, int c0, float (&g)[V], Pend& p) const {
+    if (ROW_FIRST && ga.g) gate_row(r, c0, p);
+    Pack16<T>::load(dy + r * lddy + c0, g);
+  }
+  __device__ __forceinline__ void finish(int64_t r, int c0, float (&g)[V], Pend& p) const {
+    if (!ga.g) return;
+    if (!ROW_FIRST) gate_row(r, c0, p);
+#pragma unroll
+    for (int e = 0; e < V; ++e) g[e] = as_stored<T>(gate_grad(g[e], p.gv[e], p.dv[e], ga.invS));
+  }
+};
+
+template <typename T, typename Src>
+__device__ __forceinline__ void bn_bwd_reduce_body(const Src& src, const T* __restrict__ y, int ldy,
                                                    const T* __restrict__ x, int ldx, const float* __restrict__ mean,
                                                    const float* __restrict__ invstd, int64_t M, int C, int CP, int flags,
                                                    int64_t rows_per_block, float* __restrict__ sums_all, int n_rep,
-                                                   uint32_t bid, const float* __restrict__ scale = nullptr,
-                                                   const float* __restrict__ shift = nullptr, float* __restrict__ ws = nullptr,
-                                                   uint32_t nblk = 0, const GateOnLoad& ga = GateOnLoad()) {
+                                                   uint32_t bid, const float* __restrict__ scale,
+                                                   const float* __restrict__ shift, float* __restrict__ ws, uint32_t nblk) {
   constexpr int V = DT<T>::VEC;
+  if (Src::kPooled) { flags = DV_MASK_FROM_X; ws = nullptr; }
   // Ordered mode (ws != nullptr): the block stores its partial sums to ws[bid][2][CP] (sc1 stores); the block that takes the
   // last ticket (ordered_fold: drained stores -> ticket -> sc1 loads) adds the partials in block order into sums_all[0] -- no
   // float atomics, so the sums do not depend on the order blocks finish in.  Legacy mode: atomics, spread over n_rep replicas because atomics on one
@@ -415,24 +456,15 @@ __device__ __forceinline__ void bn_bwd_reduce_body(const T* __restrict__ dy, int
   // (same expression, same rounding), so the output tensor is not read at all: 2 tensor reads instead of 3
   const bool fromx = mask && (flags & DV_MASK_FROM_X);
   float mu[V], is[V], sc[V], sh[V];
-  // (gated: half the rows in flight -- two more vectors per row -- which keeps the registers at the plain kernel's occupancy;
-  // measured, 2 / 3 / 4 rows in flight run the step's gated reduces in 601 / 611 / 611 us)
-  column_reduce<V, 2, GATE ? (V == 4 ? 2 : 1) : 0>(
+  column_reduce<V, 2, Src::kRows>(
       r0, r1, CP,
       [&](int64_t r, int c0, float(&acc)[2][V]) {
-        float g[V], yy[V], xx[V], gv[V], dv[V];
-        if (GATE && ga.g) {                        // the gate's row first: these loads hit in L1 / L2 and come back at once; issued
-          const size_t go = (size_t)fd_div((uint32_t)r, ga.fS) * ga.ldg;      // behind dy and x they cost 15 us more per step
-          load_params<V>(ga.g + go, c0, gv);
-          load_params<V>(ga.dm + go, c0, dv);
-        }
-        Pack16<T>::load(dy + r * lddy + c0, g);
+        float g[V], yy[V], xx[V];
+        typename Src::Pend pend;
+        src.load(r, c0, g, pend);
         if (mask && !fromx) Pack16<T>::load(y + r * ldy + c0, yy);
         Pack16<T>::load(x + r * ldx + c0, xx);
-        if (GATE && ga.g) {                        // dL/dy behind the gate, as gate_bwd_apply would have left it in dy
-#pragma unroll
-          for (int e = 0; e < V; ++e) g[e] = as_stored<T>(gate_grad(g[e], gv[e], dv[e], ga.invS));
-        }
+        src.finish(r, c0, g, pend);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           const float act = fromx ? bn_affine(xx[e], sc[e], sh[e]) : yy[e];
@@ -462,8 +494,8 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
                                      const T* __restrict__ x, int ldx, const float* __restrict__ mean,
                                      const float* __restrict__ invstd, int64_t M, int C, int CP, int flags,
                                      int64_t rows_per_block, float* __restrict__ sums_all, int n_rep, float* __restrict__ ws) {
-  bn_bwd_reduce_body<T>(dy, lddy, y, ldy, x, ldx, mean, invstd, M, C, CP, flags, rows_per_block, sums_all, n_rep, blockIdx.x,
-                        nullptr, nullptr, ws, gridDim.x);
+  bn_bwd_reduce_body<T>(PlainDy<T>{dy, lddy}, y, ldy, x, ldx, mean, invstd, M, C, CP, flags, rows_per_block, sums_all, n_rep,
+                        blockIdx.x, nullptr, nullptr, ws, gridDim.x);
 }
 
 template <typename T>
@@ -473,8 +505,8 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_multi_kernel(const dv_
   const dv_bn_item& it = items[i];
   const int CP = (it.C + 7) & ~7;
   const int64_t rpb = (it.M + nblk - 1) / nblk;
-  bn_bwd_reduce_body<T>((const T*)it.dy, it.lddy, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean, it.invstd, it.M,
-                        it.C, CP, it.bwd_flags, rpb, it.sums, it.n_rep, bid, it.scale, it.shift, it.red_ws, nblk);
+  bn_bwd_reduce_body<T>(PlainDy<T>{(const T*)it.dy, it.lddy}, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean,
+                        it.invstd, it.M, it.C, CP, it.bwd_flags, rpb, it.sums, it.n_rep, bid, it.scale, it.shift, it.red_ws, nblk);
 }
 
 __device__ __forceinline__ GateOnLoad gate_of_item(const int32_t* __restrict__ gate_off, int i, const float* g, const float* dm,
@@ -499,9 +531,9 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_multi_gated_kernel(con
   const dv_bn_item& it = items[i];
   const int CP = (it.C + 7) & ~7;
   const int64_t rpb = (it.M + nblk - 1) / nblk;
-  bn_bwd_reduce_body<T, true>((const T*)it.dy, it.lddy, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean, it.invstd, it.M,
-                              it.C, CP, it.bwd_flags, rpb, it.sums, it.n_rep, bid, it.scale, it.shift, it.red_ws, nblk,
-                              gate_of_item(gate_off, i, g, dm, fS, ldg));
+  bn_bwd_reduce_body<T>(GatedDy<T, true>{(const T*)it.dy, it.lddy, gate_of_item(gate_off, i, g, dm, fS, ldg)}, (const T*)it.y, it.ldy,
+                        (const T*)it.x, it.ldx, it.mean, it.invstd, it.M, it.C, CP, it.bwd_flags, rpb, it.sums, it.n_rep, bid,
+                        it.scale, it.shift, it.red_ws, nblk);
 }
 
 // partials [n_blocks][W] -> out[W] (+=): 32 columns x 8 row lanes per block
@@ -533,18 +565,17 @@ __global__ void reduce_rows_kernel(const float* __restrict__ part, int64_t ld, i
 
 // dx = k1[c]*g + k2[c]*x + k3[c] with  k1 = gamma*invstd, k2 = -k1*invstd*sgx/M, k3 = -k1*sg/M - k2*mean
 // (sg, sgx = global sums of g and g*xhat).  The table is built once per block in LDS.
-template <typename T, bool GATE = false>
-__device__ __forceinline__ void bn_bwd_apply_body(const T* __restrict__ dy, int lddy, const T* __restrict__ y, int ldy,
+template <typename T, typename Src>
+__device__ __forceinline__ void bn_bwd_apply_body(const Src& src, const T* __restrict__ y, int ldy,
                                                   const T* __restrict__ x, int ldx, const float* __restrict__ mean,
                                                   const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                   const float* __restrict__ sums_g, int rep_g, float inv_count,
                                                   float dscale, float* dgamma, float* dbeta, T* __restrict__ dx,
                                                   int lddx, T* __restrict__ dres, int lddres, uint32_t total, int C,
                                                   int CP, const FastDiv& fcv, int flags, uint32_t bid, uint32_t nblk,
-                                                  const float* __restrict__ scale = nullptr,
-                                                  const float* __restrict__ shift = nullptr,
-                                                  const GateOnLoad& ga = GateOnLoad()) {
+                                                  const float* __restrict__ scale, const float* __restrict__ shift) {
   constexpr int V = DT<T>::VEC;
+  if (Src::kPooled) { flags = DV_MASK_FROM_X; dres = nullptr; }
   extern __shared__ __attribute__((aligned(16))) float coef[];      // [3][CP] (+ [2][CP] scale, shift with DV_MASK_FROM_X)
   const bool fromx = !(flags & DV_NO_RELU_MASK) && (flags & DV_MASK_FROM_X);
   if (bid == 0 && dgamma) {
@@ -574,18 +605,12 @@ __device__ __forceinline__ void bn_bwd_apply_body(const T* __restrict__ dy, int 
     const uint32_t row = fd_div(i, fcv);
     const int c0 = (int)(i - row * CV) * V;
     float g[V], yy[V], xx[V], o[V], ro[V], k1[V], k2[V], k3[V], sc[V], sh[V];
-    Pack16<T>::load(dy + (size_t)row * lddy + c0, g);
+    typename Src::Pend pend;
+    src.load(row, c0, g, pend);
     if (mask && !fromx) Pack16<T>::load(y + (size_t)row * ldy + c0, yy);
     Pack16<T>::load(x + (size_t)row * ldx + c0, xx);
     if (dres && (flags & DV_ACCUM)) Pack16<T>::load(dres + (size_t)row * lddres + c0, ro);
-    if (GATE && ga.g) {                            // (as in bn_bwd_reduce_body: the same dL/dy in both passes)
-      const size_t go = (size_t)fd_div(row, ga.fS) * ga.ldg;
-      float gv[V], dv[V];
-      load_params<V>(ga.g + go, c0, gv);
-      load_params<V>(ga.dm + go, c0, dv);
-#pragma unroll
-      for (int e = 0; e < V; ++e) g[e] = as_stored<T>(gate_grad(g[e], gv[e], dv[e], ga.invS));
-    }
+    src.finish(row, c0, g, pend);                         // (as in bn_bwd_reduce_body: the same dL/dy in both passes)
     load_params<V>(coef, c0, k1);
     load_params<V>(coef + CP, c0, k2);
     load_params<V>(coef + 2 * CP, c0, k3);
@@ -611,8 +636,8 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, int lddy, const T*
                                     float* dgamma, float* dbeta, T* __restrict__ dx, int lddx,
                                     T* __restrict__ dres, int lddres, uint32_t total, int C, int CP, FastDiv fcv,
                                     int flags) {
-  bn_bwd_apply_body<T>(dy, lddy, y, ldy, x, ldx, mean, invstd, gamma, sums_g, rep_g, inv_count, dscale, dgamma, dbeta, dx,
-                       lddx, dres, lddres, total, C, CP, fcv, flags, blockIdx.x, gridDim.x);
+  bn_bwd_apply_body<T>(PlainDy<T>{dy, lddy}, y, ldy, x, ldx, mean, invstd, gamma, sums_g, rep_g, inv_count, dscale, dgamma,
+                       dbeta, dx, lddx, dres, lddres, total, C, CP, fcv, flags, blockIdx.x, gridDim.x, nullptr, nullptr);
 }
 
 template <typename T>
@@ -622,7 +647,7 @@ __global__ void bn_bwd_apply_multi_kernel(const dv_bn_item* __restrict__ items, 
   const dv_bn_item& it = items[i];
   constexpr int V = DT<T>::VEC;
   const int CP = (it.C + 7) & ~7;
-  bn_bwd_apply_body<T>((const T*)it.dy, it.lddy, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean, it.invstd,
+  bn_bwd_apply_body<T>(PlainDy<T>{(const T*)it.dy, it.lddy}, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean, it.invstd,
                        it.gamma, it.sums, it.n_rep, it.inv_count, it.dparam_scale, it.dgamma, it.dbeta, (T*)it.dx, it.lddx,
                        (T*)it.dres, it.lddres, (uint32_t)(it.M * (CP / V)), it.C, CP, fastdiv_dev((uint32_t)(CP / V)),
                        it.bwd_flags, bid, nblk, it.scale, it.shift);
@@ -636,11 +661,10 @@ __global__ void bn_bwd_apply_multi_gated_kernel(const dv_bn_item* __restrict__ i
   const dv_bn_item& it = items[i];
   constexpr int V = DT<T>::VEC;
   const int CP = (it.C + 7) & ~7;
-  bn_bwd_apply_body<T, true>((const T*)it.dy, it.lddy, (const T*)it.y, it.ldy, (const T*)it.x, it.ldx, it.mean, it.invstd,
-                             it.gamma, it.sums, it.n_rep, it.inv_count, it.dparam_scale, it.dgamma, it.dbeta, (T*)it.dx,
-                             it.lddx, (T*)it.dres, it.lddres, (uint32_t)(it.M * (CP / V)), it.C, CP,
-                             fastdiv_dev((uint32_t)(CP / V)), it.bwd_flags, bid, nblk, it.scale, it.shift,
-                             gate_of_item(gate_off, i, g, dm, fS, ldg));
+  bn_bwd_apply_body<T>(GatedDy<T, false>{(const T*)it.dy, it.lddy, gate_of_item(gate_off, i, g, dm, fS, ldg)}, (const T*)it.y, it.ldy,
+                       (const T*)it.x, it.ldx, it.mean, it.invstd, it.gamma, it.sums, it.n_rep, it.inv_count, it.dparam_scale,
+                       it.dgamma, it.dbeta, (T*)it.dx, it.lddx, (T*)it.dres, it.lddres, (uint32_t)(it.M * (CP / V)), it.C, CP,
+                       fastdiv_dev((uint32_t)(CP / V)), it.bwd_flags, bid, nblk, it.scale, it.shift);
 }
 
 // ------------------------------------------------------------------ MaxPool3d
@@ -905,44 +929,31 @@ __device__ __forceinline__ void pool_gather(const PoolArgs& a, const T* __restri
   }
 }
 
+// dL/dy gathered from the pooled gradient: the third source of bn_bwd_reduce_body / bn_bwd_apply_body.  kPooled fixes, at
+// compile time, what the one consumer of such a BatchNorm never varies -- the mask rebuilt from x (DV_MASK_FROM_X), sums by
+// atomics (no ordered-fold workspace, hence no ticket word in LDS), no residual gradient -- so those branches fold away.
+template <typename T>
+struct PooledDy {
+  static constexpr int V = DT<T>::VEC, kRows = 0;
+  static constexpr bool kPooled = true;
+  struct Pend {};
+  const PoolArgs& a; const T* dyp; const uint8_t* idx;
+  __device__ __forceinline__ void load(int64_t r, int c0, float (&g)[V], Pend&) const {
+#pragma unroll
+    for (int e = 0; e < V; ++e) g[e] = 0.f;
+    pool_gather<T>(a, dyp, idx, (uint32_t)r, c0, g);
+  }
+  __device__ __forceinline__ void finish(int64_t, int, float (&)[V], Pend&) const {}
+};
+
 template <typename T>
 __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_maxpool_kernel(PoolArgs a, const T* __restrict__ dyp, const uint8_t* __restrict__ idx,
                                              const T* __restrict__ x, const float* __restrict__ mean,
                                              const float* __restrict__ invstd, const float* __restrict__ scale,
                                              const float* __restrict__ shift, int64_t M, int C, int CP, int64_t rows_per_block,
                                              float* __restrict__ sums_all, int n_rep) {
-  constexpr int V = DT<T>::VEC;
-  float* sums = sums_all + (size_t)(blockIdx.x % n_rep) * 2 * CP;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = min(M, r0 + rows_per_block);
-  float mu[V], is[V], sc[V], sh[V];
-  column_reduce<V, 2>(
-      r0, r1, CP,
-      [&](int64_t r, int c0, float(&acc)[2][V]) {
-        float g[V], xx[V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) g[e] = 0.f;
-        pool_gather<T>(a, dyp, idx, (uint32_t)r, c0, g);
-        Pack16<T>::load(x + r * a.ldx + c0, xx);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-          const float act = bn_affine(xx[e], sc[e], sh[e]);
-          const float gg = !(act > 0.f) ? 0.f : g[e];
-          acc[0][e] += gg;
-          acc[1][e] += gg * (xx[e] - mu[e]) * is[e];
-        }
-      },
-      [&](int c0, float(&acc)[2][V]) {
-#pragma unroll
-        for (int e = 0; e < V; ++e)
-          if (c0 + e < C) { atomicAdd(sums + c0 + e, acc[0][e]); atomicAdd(sums + CP + c0 + e, acc[1][e]); }
-      },
-      [&](int c0) {
-        load_params<V>(mean, c0, mu);
-        load_params<V>(invstd, c0, is);
-        load_params<V>(scale, c0, sc);
-        load_params<V>(shift, c0, sh);
-      });
+  bn_bwd_reduce_body<T>(PooledDy<T>{a, dyp, idx}, nullptr, 0, x, a.ldx, mean, invstd, M, C, CP, 0, rows_per_block, sums_all,
+                        n_rep, blockIdx.x, scale, shift, nullptr, gridDim.x);
 }
 
 template <typename T>
@@ -953,53 +964,8 @@ __global__ void bn_bwd_apply_maxpool_kernel(PoolArgs a, const T* __restrict__ dy
                                             const float* __restrict__ sums_g, int rep_g, float inv_count, float dscale,
                                             float* dgamma, float* dbeta, T* __restrict__ dx, int lddx, uint32_t total, int C,
                                             int CP) {
-  constexpr int V = DT<T>::VEC;
-  extern __shared__ __attribute__((aligned(16))) float coef[];      // [5][CP]: k1, k2, k3, scale, shift
-  if (blockIdx.x == 0 && dgamma) {
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-      float sb = 0.f, sg = 0.f;
-      for (int r = 0; r < rep_g; ++r) { sb += sums_g[(size_t)r * 2 * CP + c]; sg += sums_g[(size_t)r * 2 * CP + CP + c]; }
-      dbeta[c] += dscale * sb;
-      dgamma[c] += dscale * sg;
-    }
-  }
-  for (int c = threadIdx.x; c < CP; c += blockDim.x) {
-    float k1 = 0.f, k2 = 0.f, k3 = 0.f;
-    if (c < C) {
-      float sg = 0.f, sgx = 0.f;
-      for (int r = 0; r < rep_g; ++r) { sg += sums_g[(size_t)r * 2 * CP + c]; sgx += sums_g[(size_t)r * 2 * CP + CP + c]; }
-      k1 = gamma[c] * invstd[c];
-      k2 = -k1 * invstd[c] * sgx * inv_count;
-      k3 = -k1 * sg * inv_count - k2 * mean[c];
-    }
-    coef[c] = k1; coef[CP + c] = k2; coef[2 * CP + c] = k3;
-    coef[3 * CP + c] = c < C ? scale[c] : 0.f; coef[4 * CP + c] = c < C ? shift[c] : 0.f;
-  }
-  __syncthreads();
-  const uint32_t CV = a.fcv.d;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    uint32_t row, cvi;
-    fd_divmod(i, a.fcv, row, cvi);
-    const int c0 = (int)cvi * V;
-    float g[V], xx[V], o[V], k1[V], k2[V], k3[V], sc[V], sh[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) g[e] = 0.f;
-    pool_gather<T>(a, dyp, idx, row, c0, g);
-    Pack16<T>::load(x + (size_t)row * a.ldx + c0, xx);
-    load_params<V>(coef, c0, k1);
-    load_params<V>(coef + CP, c0, k2);
-    load_params<V>(coef + 2 * CP, c0, k3);
-    load_params<V>(coef + 3 * CP, c0, sc);
-    load_params<V>(coef + 4 * CP, c0, sh);
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const float act = bn_affine(xx[e], sc[e], sh[e]);
-      const float gg = !(act > 0.f) ? 0.f : g[e];
-      o[e] = k1[e] * gg + k2[e] * xx[e] + k3[e];
-    }
-    Pack16<T>::store(dx + (size_t)row * lddx + c0, o);
-  }
-  (void)CV;
+  bn_bwd_apply_body<T>(PooledDy<T>{a, dyp, idx}, nullptr, 0, x, a.ldx, mean, invstd, gamma, sums_g, rep_g, inv_count, dscale,
+                       dgamma, dbeta, dx, lddx, nullptr, 0, total, C, CP, a.fcv, 0, blockIdx.x, gridDim.x, scale, shift);
 }
 
 // ------------------------------------------------------------------ MaxPool3d 3x3x3 / stride 1 / padding 1, LDS-staged
@@ -1330,12 +1296,10 @@ static bool pool_tile_args(const PoolArgs& p, int V, int TH, int TW, int CV, int
   a.accumulate = accumulate;
   return true;
 }
-static int pool_tile_cv(int dflt) { return dflt; }
 // Tile width / channel vectors per workgroup.  Measured on the 14x14 and 7x7 pools of S3D-G (tools/pool_sweep.sh): the
 // backward is occupancy-bound (three-plane ring of dy + idx), so it takes the 7-wide tile and 64 bytes of dy per pixel; the
 // forward (two single-plane slots) is flat between the shapes.
 static int pool_tile_tw(int W, bool narrow) { return (W <= 7 || narrow) ? 7 : 14; }
-static bool pool_tile_off() { return false; }
 
 // ------------------------------------------------------------------ spatial mean / gating
 // One workgroup per (sample, slice of the S positions): with one workgroup per sample (N = 128) half the CUs had no
@@ -1890,11 +1854,11 @@ enum { kPoolGather = 0, kPoolQuad = 1, kPoolTile = 2 };
 static int pool_route(const dv_pool_desc* d, const PoolArgs& a, bool bwd, bool idx_aligned, int accumulate, PoolTileArgs& ta,
                       int& tw, int& cv) {
   tw = cv = 0;
-  if (pool333_shape(d) && !pool_tile_off() && idx_aligned) {
+  if (pool333_shape(d) && idx_aligned) {
     const int V = d->dtype == DV_F32 ? 4 : 8;
-    const int cv_ = pool_tile_cv(bwd ? (d->dtype == DV_BF16 ? 2 : 4) : 4);
+    const int cv_ = bwd && d->dtype == DV_BF16 ? 2 : 4;
     const int tw_ = pool_tile_tw(a.Wi, bwd || d->dtype == DV_BF16);
-    if ((cv_ == 2 || cv_ == 4 || cv_ == 8) && pool_tile_args(a, V, 7, tw_, cv_, accumulate, ta)) {
+    if (pool_tile_args(a, V, 7, tw_, cv_, accumulate, ta)) {
       tw = tw_; cv = cv_;
       return kPoolTile;
     }

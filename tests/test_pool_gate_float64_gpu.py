@@ -23,6 +23,8 @@ written views are 0.
                       channels); also on Gaussian data, where the values are in addition bounded against pure float64.
                       backward: sums (replicas added on the host, n_rep 1 and 4), dgamma, dbeta exact; dx exact where M is a
                       power of two.  The ReLU mask is the sign of the fp32 restatement: the forward's definition.
+                      fp32, one block: sums, dx, dgamma, dbeta == the two-pass form's (dv_maxpool3d_bwd, then the multi-tensor
+                      reduce and apply with DV_MASK_FROM_X), which the fused passes share their arithmetic with.
     means and gates   integer data, S a power of two, dyadic g: exact on every chunk layout and on both rowscale paths (the
                       scalar one forced by C % V != 0 and by a g / dmean table at a 4-byte offset); S = 127 is bounded (1 / S).
     helpers, ingest   dv_relu_bwd_f32, dv_l2norm_fwd on rows of power-of-two norm, the ingest copies: exact.
@@ -75,11 +77,11 @@ pytestmark = pytest.mark.gpu
 from dualvar_amd import _lib as L, ops  # noqa: E402
 from dualvar_amd._lib import DV_ACCUM, DV_BF16, DV_F32  # noqa: E402
 from tests import pool_cases as T  # noqa: E402
-from tests.bn_support import DTYPES  # noqa: E402
+from tests.bn_support import DTYPES, Member, make_table  # noqa: E402
 from tests.chains import column_chain  # noqa: E402
 from tests import checks  # noqa: E402
-from tests.checks import (BF16_U, U, Ratios, View, bits, ceil_div, chan, cp8, is_sent, launch, report_fixture,  # noqa: E402
-                          sent, vec)
+from tests.checks import (BF16_U, U, Ratios, View, bits, ceil_div, chan, cp8, equal_bits, is_sent, launch,  # noqa: E402
+                          report_fixture, sent, vec)
 from tests.pool_reference import ref_pool_bwd, ref_pool_fwd  # noqa: E402
 
 IDX_SENT = 0xEE                    # idx bytes before a launch: no tap is that large (kt*kh*kw <= 27 here)
@@ -494,6 +496,59 @@ def test_bn_relu_pool_backward_bounds(gpu, dtype, ill, c):
     b = BnPool(c, dtype, gpu, False, 41, ill=ill)
     for n_rep in (1, 4):
         run_bn_pool_backward(b, n_rep, 1.0, '%s%s n_rep %d' % (c.name, ' ill' if ill else '', n_rep))
+
+
+# M = 32 rows: dv_bn_bwd_blocks gives one block, so the atomics of both forms add onto zero once and no order is left open
+_ONE_BLOCK = [T._pc('bnp_133_one_block', 1, 2, 4, 4, 5, (1, 3, 3), (1, 2, 2), (0, 1, 1)),
+              T._pc('bnp_333s2_one_block', 1, 2, 4, 4, 5, T.K333, (2, 2, 2), T.P1)]
+
+
+@pytest.mark.parametrize('c', _ONE_BLOCK, ids=lambda c: c.name)
+def test_pooled_bn_backward_equals_two_pass_bits(gpu, c):
+    """dv_bn_bwd_reduce_maxpool + dv_bn_bwd_apply_maxpool against the two passes they replace, bit for bit: dv_maxpool3d_bwd into
+    a dy buffer, then dv_bn_bwd_reduce_multi + dv_bn_bwd_apply_multi over one DV_MASK_FROM_X member with red_ws = NULL.  fp32
+    only: there the pool's gradient is stored unrounded, summed in the same ascending tap order (bf16 would round dy between)."""
+    dtype, lib = DV_F32, L.load()
+    C_, CP = c.C, cp8(c.C)
+    M, Mo = c.N * c.T * c.H * c.W, c.N * math.prod(T.out_dims(c))
+    assert M <= 32 and int(lib.dv_bn_bwd_blocks(M, C_)) == 1 and C_ % 8
+    m = Member(gpu, dtype, M, C_, 51, exact=False, from_x=True)
+    m.red_ws = torch.empty(0, dtype=torch.float32, device=gpu)               # the item's red_ws = NULL: sums by atomics
+    assert m.red_ws.data_ptr() == 0
+    m.sums[0].zero_()
+    dyp = View.sliced(dtype, Mo, C_, gpu, False, torch.randn((Mo, C_), generator=gen(52), dtype=torch.float64))
+    # taps of the fused forward on the member's own x
+    y, idx = View.sliced(dtype, Mo, C_, gpu), IdxBuf(Mo, CP, gpu)
+    par = {k: m.p[k].data_ptr() for k in m.p}
+    launch('dv_bn_apply_maxpool', C.byref(T.desc(c, dtype, m.x.ld, y.ld)), m.x.ptr, par['scale'], par['shift'], y.ptr, idx.ptr)
+    # fused (first: the two-pass form below adds onto the same dgamma / dbeta values)
+    sums = torch.zeros(2 * CP, dtype=torch.float32, device=gpu)
+    dgamma, dbeta = m.dgamma.clone(), m.dbeta.clone()
+    dx = View.sliced(dtype, M, C_, gpu)
+    d = T.desc(c, dtype, m.x.ld, dyp.ld)
+    launch('dv_bn_bwd_reduce_maxpool', C.byref(d), dyp.ptr, idx.ptr, m.x.ptr, par['mean'], par['invstd'], par['scale'], par['shift'],
+           sums.data_ptr(), 1)
+    launch('dv_bn_bwd_apply_maxpool', C.byref(d), dyp.ptr, idx.ptr, m.x.ptr, par['mean'], par['invstd'], par['gamma'], par['scale'],
+           par['shift'], sums.data_ptr(), 1, 1.0 / M, m.dscale, dgamma.data_ptr(), dbeta.data_ptr(), dx.ptr, dx.ld)
+    # two passes
+    launch('dv_maxpool3d_bwd', C.byref(T.desc(c, dtype, m.dy.ld, dyp.ld)), dyp.ptr, idx.ptr, m.dy.ptr, 0)
+    tab, ends = make_table([m], lib, gpu, dtype)
+    assert ends['red'] == 1 and ends['bapply'] == 1
+    launch('dv_bn_bwd_reduce_multi', dtype, tab.data_ptr(), 1, 1)
+    launch('dv_bn_bwd_apply_multi', dtype, tab.data_ptr(), 1, 1, C_)
+    torch.cuda.synchronize()
+    idx.check_frame(c.name)
+    for v, what in ((m.dy, 'two-pass dy'), (m.dx, 'two-pass dx'), (dx, 'fused dx')):
+        v.check_frame('%s %s' % (c.name, what))                               # zeros in the pad lanes
+    # the data can tell: gathered gradient passes the mask in every channel (a pool picks a masked element only from a window
+    # of zeros, so little is dropped), and both sums of every channel are nonzero
+    s2, act = m.sums[0], m.x.val() * m.scale + m.shift
+    assert bool(((m.dy.val() != 0) & (act > 0)).any(0).all()) and bool((s2[:C_] != 0).all()) and bool((s2[CP:CP + C_] != 0).all())
+    for got, want, what in ((sums, s2, 'sums'), (dx.cols(), m.dx.cols(), 'dx'), (dgamma, m.dgamma, 'dgamma'), (dbeta, m.dbeta, 'dbeta')):
+        assert equal_bits(got, want), '%s: %s of the fused and the two-pass form differ' % (c.name, what)
+    assert bool((sums.view(2, CP)[:, C_:] == 0).all()), c.name + ': pad lanes of the sums'
+    assert bool((dgamma[C_:] == 0.625).all()) and bool((dbeta[C_:] == 0.625).all()), c.name + ': pad lanes of dgamma / dbeta'
+    assert not torch.equal(dgamma[:C_], chan(m.dg0, CP, gpu)[:C_])
 
 
 # ------------------------------------------------------------------------------------------------------------ means and gates
