@@ -106,6 +106,21 @@ class _IngestStep:
     def __call__(self, stream):
         self.op._launch(stream)
 
+    @property
+    def reads(self):
+        """what the bound source holds (engine.Launch.reads): the clips, or the decoded frames and their augmentation tables"""
+        op = self.op
+        fb = op.src if isinstance(op.src, FrameBatch) else None
+        ts = [op.mean, op.istd, op.perm] + ([fb.frames, fb.table, fb.blur, fb.patches] if fb is not None else [op.src])
+        return tuple((t, 0, t.numel()) for t in ts if t is not None)
+
+    @property
+    def writes(self):
+        op = self.op
+        fb = isinstance(op.src, FrameBatch)
+        ts = [op.cmean, getattr(op, 'blur_tmp', None)] if fb else []
+        return (op.y,) + tuple((t, 0, t.numel()) for t in ts if t is not None)
+
 
 class _Token:
     pass

@@ -427,6 +427,28 @@ class ParamStore:
             return self.wd3.data_ptr() + s.wd3_off, L.DV_W3
         return self.wd.data_ptr() + s.wd_off * ops.ESIZE[self.dtype], 0
 
+    # what those pointers cover, as accesses (tensor, first element, end element): Launch.reads / Launch.writes
+    @staticmethod
+    def _span(s):
+        return s.size if s.kind != 'vec' else s.tensor.numel()
+
+    def fwd_range(self, s):
+        if getattr(s, 'w3_off', -1) is not None and getattr(s, 'w3_off', -1) >= 0 and self.w3 is not None:
+            return self.w3, s.w3_off, s.w3_off + int(L.load().dv_w3_bytes(s.Cout, s.size // s.Cout))
+        return self.cc, s.off, s.off + s.size
+
+    def master_range(self, s):
+        return self.master, s.off, s.off + self._span(s)
+
+    def grad_range(self, s):
+        return self.grad, s.off, s.off + self._span(s)
+
+    def dgrad_range(self, s, w3):
+        """w3: the pre-split form (the DV_W3 flag w_dgrad answered with)"""
+        if w3:
+            return self.wd3, s.wd3_off, s.wd3_off + int(L.load().dv_w3_bytes(s.Cin, s.taps * s.cout_pitch))
+        return self.wd, s.wd_off, s.wd_off + s.Cin * s.taps * s.cout_pitch
+
     def bump_bn_counters(self):
         if self.nbt:
             self._nbt_arena += 1
@@ -457,12 +479,24 @@ class Comm:
         return self._xstream
 
 
-class Launch:
-    """One kernel launch of a plan: a bound C-ABI call plus its algorithmic cost (for the roofline report)."""
-    __slots__ = ('name', 'kname', 'fn', 'args', 'bytes', 'flops', 'shape', 'gend', 'pair', 'members')
+def _all(t):
+    """a whole flat buffer as an access"""
+    return None if t is None else (t, 0, t.numel())
 
-    def __init__(self, name, kname, fn, args, nbytes=0, flops=0, shape=''):
+
+def _accesses(seq):
+    return tuple(a for a in seq if a is not None)
+
+
+class Launch:
+    """One kernel launch of a plan: a bound C-ABI call plus its algorithmic cost (for the roofline report), and what it
+    touches: `reads` / `writes` are accesses -- an ops.Act (its allocation, the channel columns [off, off + cpitch) of every
+    row) or a flat range (tensor, first element, end element).  A target that is added to stands in both."""
+    __slots__ = ('name', 'kname', 'fn', 'args', 'bytes', 'flops', 'shape', 'gend', 'pair', 'members', 'reads', 'writes')
+
+    def __init__(self, name, kname, fn, args, nbytes=0, flops=0, shape='', reads=(), writes=()):
         self.name, self.kname, self.fn, self.args, self.bytes, self.flops, self.shape = name, kname, fn, args, nbytes, flops, shape
+        self.reads, self.writes = _accesses(reads), _accesses(writes)
         self.gend = 0                # end (element offset) of the highest gradient-arena range this launch writes
         self.pair = None             # PairMember: this conv launch as one member of a shared grid (pair_convs), if it can be one
         self.members = ()            # the two launches a paired launch replaces
@@ -475,10 +509,11 @@ class Launch:
 
 class StreamStep:
     """A host-side step that needs the stream it is issued on (event hops around a direct RCCL call)."""
-    __slots__ = ('name', 'kname', 'call', 'bytes', 'flops')
+    __slots__ = ('name', 'kname', 'call', 'bytes', 'flops', 'reads', 'writes')
 
-    def __init__(self, name, call):
+    def __init__(self, name, call, reads=(), writes=()):
         self.name, self.kname, self.call, self.bytes, self.flops = name, 'host:' + name, call, 0, 0
+        self.reads, self.writes = _accesses(reads), _accesses(writes)
 
     def __call__(self, stream):
         self.call(stream)
@@ -486,10 +521,11 @@ class StreamStep:
 
 class HostStep:
     """A host-side step inside a plan (a torch.distributed collective on the current stream)."""
-    __slots__ = ('name', 'kname', 'call', 'bytes', 'flops')
+    __slots__ = ('name', 'kname', 'call', 'bytes', 'flops', 'reads', 'writes')
 
-    def __init__(self, name, call):
+    def __init__(self, name, call, reads=(), writes=()):
         self.name, self.kname, self.call, self.bytes, self.flops = name, 'host:' + name, call, 0, 0
+        self.reads, self.writes = _accesses(reads), _accesses(writes)
 
     def __call__(self, stream):
         self.call()
@@ -568,11 +604,12 @@ class PlanGraph:
 
 class PairMember:
     """A conv forward / data-gradient launch as one member of a two-member grid: its arguments as the pair entry takes them, and
-    what it reads and writes (activations: ops.Act; flat buffers: tensors) for the independence check."""
+    what it reads and writes (its launch's own sets: activations, flat buffers or ranges of them) for the independence check."""
     __slots__ = ('role', 'desc', 'args', 'reads', 'writes')
 
     def __init__(self, role, desc, args, reads, writes):
-        self.role, self.desc, self.args, self.reads, self.writes = role, desc, args, reads, [w for w in writes if w is not None]
+        self.role, self.desc, self.args, self.reads = role, desc, args, reads
+        self.writes = [w for w in writes if w is not None] if any(w is None for w in writes) else writes
 
 
 PAIR_ENTRIES = {'fwd': ('dv_conv3d_fwd_pair', 0), 'fwd_bn_in': ('dv_conv3d_fwd_bn_in_pair', L.DV_PAIR_BN_IN0 | L.DV_PAIR_BN_IN1),
@@ -580,6 +617,8 @@ PAIR_ENTRIES = {'fwd': ('dv_conv3d_fwd_pair', 0), 'fwd_bn_in': ('dv_conv3d_fwd_b
 
 
 def _storage(t):
+    if isinstance(t, tuple):
+        t = t[0]
     return _bufkey(t) if isinstance(t, ops.Act) else t.untyped_storage().data_ptr()
 
 
@@ -587,6 +626,8 @@ def _written(t):
     """(allocation, first, end): the channel columns of an activation's rows a conv writes / the elements of a flat buffer"""
     if isinstance(t, ops.Act):
         return _bufkey(t), t.off, t.off + t.cpitch
+    if isinstance(t, tuple):
+        return t[0].untyped_storage().data_ptr(), t[0].storage_offset() + t[1], t[0].storage_offset() + t[2]
     return t.untyped_storage().data_ptr(), t.storage_offset(), t.storage_offset() + t.numel()
 
 
@@ -624,6 +665,7 @@ def pair_convs(lst, lib, side=()):
             p = Launch(l0.name, l0.kname + '+pair', getattr(lib, PAIR_ENTRIES[m0.role][0]), m0.args + m1.args + extra,
                        l0.bytes + l1.bytes, l0.flops + l1.flops, l0.shape + ' | ' + l1.shape)
             p.gend, p.members = max(l0.gend, l1.gend), (l0, l1)
+            p.reads, p.writes = l0.reads + l1.reads, l0.writes + l1.writes
             out.append(p)
             out += lst[i + 1:j]
             i = j + 1
@@ -842,7 +884,7 @@ class Plan:
         if self.with_grad and self._zero_words:
             self.zero_arena = self.f32(self._zero_words)
             arena = self.zero_arena
-            self.b_list.append(HostStep('zero_bwd_sums', arena.zero_))
+            self.b_list.append(HostStep('zero_bwd_sums', arena.zero_, writes=[_all(arena)]))
         for op in self.ops:
             f, b = op.launches()
             self.f_list += f
@@ -1120,28 +1162,33 @@ class ConvOp(Op):
         p.bytes += q.numel()
         return q, sc, Launch('quantize_fp8', 'quantize_fp8<%s>' % ('e5m2' if fmt else 'e4m3'), p.lib.dv_quantize_fp8,
                              (DV_BF16, a.ptr, a.rows, a.cpitch, a.ld, fmt, q.data_ptr(), a.cpitch, sc.data_ptr(), p._fp8_ws.data_ptr()),
-                             2 * _abytes(a) + q.numel(), 0, shp)
+                             2 * _abytes(a) + q.numel(), 0, shp, reads=[a, _all(p._fp8_ws)], writes=[_all(q), _all(sc), _all(p._fp8_ws)])
 
     def fwd_launches(self):
         """plain / with the BatchNorm of the input applied on load / fp8 behind the quantisation of x"""
         lib, x, y, d = self.plan.lib, self.x, self.y, self.d_in
         _, flops, wbytes, gv, shp = self._cost()
         stats = self.stats.data_ptr() if self.stats is not None else 0
+        wr = [y, _all(self.stats)]
         if self.fp8:
             w8, sw, _, _ = self.plan.store.fp8_weights(self.slot)
             self.x8, self.sx, ql = self._quantize(x, 0, shp)
             return [ql, Launch('conv_fwd', 'conv_gemm<fp8,FWD,16,%d,%d>' % _tile_shape(lib, d, 0), lib.dv_conv3d_fwd_fp8,
                                (C.byref(d), self.x8.data_ptr(), w8.data_ptr(), self.sx.data_ptr(), sw.data_ptr(), y.ptr, stats),
-                               self.x8.numel() + wbytes // 2 + _abytes(y), flops, shp)]
+                               self.x8.numel() + wbytes // 2 + _abytes(y), flops, shp,
+                               reads=[_all(self.x8), _all(w8), _all(self.sx), _all(sw)], writes=wr)]
         kf, nbytes = _conv_kname(lib, d, 0, _dt(self.dtype), gv), _abytes(x) + wbytes + _abytes(y)
+        w = self.plan.store.fwd_range(self.slot)
         if self.bn_in is not None:
             m = self.bn_in
             args = (C.byref(d), m.x.ptr, C.byref(ops.bn_in_desc(m.scale, m.shift, m.relu)), self._wf, y.ptr, stats)
-            l = Launch('conv_fwd', kf + '+bn_in', lib.dv_conv3d_fwd_bn_in, args, nbytes, flops, shp + ' +bn_in')
-            l.pair = PairMember('fwd_bn_in', d, args, [m.x, m.scale, m.shift], [y, self.stats])
+            l = Launch('conv_fwd', kf + '+bn_in', lib.dv_conv3d_fwd_bn_in, args, nbytes, flops, shp + ' +bn_in',
+                       reads=[m.x, _all(m.scale), _all(m.shift), w], writes=wr)
+            l.pair = PairMember('fwd_bn_in', d, args, l.reads, l.writes)
         else:
-            l = Launch('conv_fwd', kf, lib.dv_conv3d_fwd, (C.byref(d), x.ptr, self._wf, 0, y.ptr, stats), nbytes, flops, shp)
-            l.pair = PairMember('fwd', d, (C.byref(d), x.ptr, self._wf, y.ptr, stats), [x], [y, self.stats])
+            l = Launch('conv_fwd', kf, lib.dv_conv3d_fwd, (C.byref(d), x.ptr, self._wf, 0, y.ptr, stats), nbytes, flops, shp,
+                       reads=[x, w], writes=wr)
+            l.pair = PairMember('fwd', d, (C.byref(d), x.ptr, self._wf, y.ptr, stats), l.reads, l.writes)
         return [l]
 
     def wgrad_launches(self):
@@ -1153,6 +1200,8 @@ class ConvOp(Op):
         kw = 'conv_wgrad<%s,%d,%d,%d>' % (_dt(self.dtype), gv, tr.value, tc.value)
         ws = (p.wgrad_ws.data_ptr(), p.wgrad_ws.numel()) if p.wgrad_ws is not None else (0, 0)
         dw, nbytes, gend = st.w_grad(sl), _abytes(x) + _abytes(y) + sl.Cout * kdim * 4, sl.off + sl.size
+        # dw += x^T dy through the shared partial-tile scratch: the target is read and written
+        tgt, wsa = (st.grad, sl.off, sl.off + sl.size), _all(p.wgrad_ws)
         if self.bn_apply is not None:
             m = self.bn_apply
             gs, bs = st.slot(m.bn.weight), st.slot(m.bn.bias)
@@ -1162,19 +1211,23 @@ class ConvOp(Op):
             r.gamma, r.dgamma, r.dbeta = st.w_master(gs), st.w_grad(gs), st.w_grad(bs)
             r.sums, r.n_rep, r.flags = p.zero_ptr(m.sums_off), BN_REPLICAS, (0 if m.relu else DV_NO_RELU_MASK)
             r.inv_count, r.dparam_scale = 1.0 / (m.M * p.comm.world), 1.0 / p.comm.world
+            dpar = [st.grad_range(gs), st.grad_range(bs)]
             b = [Launch('conv_wgrad', kw + '+bn_bwd_apply', lib.dv_conv3d_wgrad_bn, (C.byref(d), x.ptr, m.y.grad.ptr, dw) + ws + (C.byref(r),),
-                        nbytes + _abytes(y), flops, shp + ' +bn_bwd_apply')]
+                        nbytes + _abytes(y), flops, shp + ' +bn_bwd_apply',
+                        reads=[x, m.y.grad, y, _all(m.mean), _all(m.invstd), _all(m.scale), _all(m.shift), st.master_range(gs),
+                               (p.zero_arena, m.sums_off, m.sums_off + m.sums_len), tgt, wsa] + dpar, writes=[tgt, wsa] + dpar)]
             b[0].gend = _gend(gs, bs)    # (it writes the BatchNorm's parameter gradients too)
         elif self.bn_in is not None:
             m = self.bn_in
             b = [Launch('conv_wgrad', kw + '+bn_in', lib.dv_conv3d_wgrad_bn_in,
                         (C.byref(d), m.x.ptr, C.byref(ops.bn_in_desc(m.scale, m.shift, m.relu)), y.grad.ptr, dw) + ws,
-                        nbytes, flops, shp + ' +bn_in')]
+                        nbytes, flops, shp + ' +bn_in', reads=[m.x, _all(m.scale), _all(m.shift), y.grad, tgt, wsa], writes=[tgt, wsa])]
         else:
-            b = [Launch('conv_wgrad', kw, lib.dv_conv3d_wgrad, (C.byref(d), x.ptr, y.grad.ptr, dw) + ws, nbytes, flops, shp)]
+            b = [Launch('conv_wgrad', kw, lib.dv_conv3d_wgrad, (C.byref(d), x.ptr, y.grad.ptr, dw) + ws, nbytes, flops, shp,
+                        reads=[x, y.grad, tgt, wsa], writes=[tgt, wsa])]
         if self.zero_pad_taps is not None:
             rows, pitch, c0, nc = self.zero_pad_taps
-            b.append(Launch('stem_pad_taps', 'fill_cols', lib.dv_fill_cols_f32, (dw, rows, pitch, c0, nc, 0.0)))
+            b.append(Launch('stem_pad_taps', 'fill_cols', lib.dv_fill_cols_f32, (dw, rows, pitch, c0, nc, 0.0), reads=[tgt], writes=[tgt]))
         for l in b:
             l.gend = max(l.gend, gend)
         return b
@@ -1186,26 +1239,32 @@ class ConvOp(Op):
         p, lib, x, y, d = self.plan, self.plan.lib, self.x, self.y, self.dgrad_desc()
         _, flops, wbytes, _, shp = self._cost()
         dxbytes = _abytes(x) * (2 if d.flags & DV_ACCUM or self.bn_fuse is not None else 1)      # (the reduce re-reads its tile)
+        acc = [x.grad] if d.flags & DV_ACCUM else []
         if self.fp8:
             _, _, wd8, swd = p.store.fp8_weights(self.slot)
             self.dy8, self.sdy, ql = self._quantize(y.grad, 1, shp)
             return [ql, Launch('conv_dgrad', 'conv_gemm<fp8,DGRAD,16,%d,%d>' % _tile_shape(lib, d, 1), lib.dv_conv3d_dgrad_fp8,
                                (C.byref(d), self.dy8.data_ptr(), wd8.data_ptr(), self.sdy.data_ptr(), swd.data_ptr(), x.grad.ptr),
-                               self.dy8.numel() + wbytes // 2 + dxbytes, flops, shp)]
+                               self.dy8.numel() + wbytes // 2 + dxbytes, flops, shp,
+                               reads=[_all(self.dy8), _all(wd8), _all(self.sdy), _all(swd)] + acc, writes=[x.grad])]
         kd, args = _conv_kname(lib, d, 1, _dt(self.dtype)), (C.byref(d), y.grad.ptr, self._wd, x.grad.ptr)
         nbytes = _abytes(y) + wbytes + dxbytes
+        rd = [y.grad, p.store.dgrad_range(self.slot, d.flags & L.DV_W3)] + acc
         if self.bn_fuse is None:
-            l = Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad, args, nbytes, flops, shp)
-            l.pair = PairMember('dgrad', d, args + (0,), [y.grad] + ([x.grad] if d.flags & DV_ACCUM else []), [x.grad])
+            l = Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad, args, nbytes, flops, shp, reads=rd, writes=[x.grad])
+            l.pair = PairMember('dgrad', d, args + (0,), l.reads, l.writes)
             return [l]
         m = self.bn_fuse
         r = ops.bn_reduce_desc(m.x, m.mean, m.invstd, m.scale, m.shift, p.zero_ptr(m.sums_off), BN_REPLICAS,
                                0 if m.relu else DV_NO_RELU_MASK)
+        sums = (p.zero_arena, m.sums_off, m.sums_off + m.sums_len)       # (added to: read and written)
+        rd += [m.x, _all(m.mean), _all(m.invstd), _all(m.scale), _all(m.shift), sums]
         if self.bn_fuse_tap:
             ws = p.bn_fuse_ws
             return [Launch('conv_dgrad', kd + '+bn_reduce', lib.dv_conv3d_dgrad_bn_ws, args + (C.byref(r), ws.data_ptr(), ws.numel() * 4),
-                           nbytes, flops, shp + ' +bn_reduce')]
-        return [Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad_bn, args + (C.byref(r),), nbytes, flops, shp + ' +bn_reduce')]
+                           nbytes, flops, shp + ' +bn_reduce', reads=rd + [_all(ws)], writes=[x.grad, sums, _all(ws)])]
+        return [Launch('conv_dgrad', kd, lib.dv_conv3d_dgrad_bn, args + (C.byref(r),), nbytes, flops, shp + ' +bn_reduce',
+                       reads=rd, writes=[x.grad, sums])]
 
 
 BN_PHASES = ('stats', 'apply', 'red', 'bapply')     # forward statistics and apply, backward reduce and apply: dv_bn_item's blk_*
@@ -1276,6 +1335,30 @@ class BNMember:
                             | (DV_ACCUM if (dres is not None and self.group.acc.get('res%d' % self.index)) else 0))
         return it
 
+    def touched(self):
+        """{field of dv_bn_item: the access behind that pointer}, for the pointers item() sets.  A launch that takes a table of
+        items declares every one of them a read (the table points there) and, of these, the ones its phase writes (written())."""
+        p, st, x, y, res = self.plan, self.plan.store, self.x, self.y, self.res
+        gs, bs = st.slot(self.bn.weight), st.slot(self.bn.bias)
+        t = dict(gamma=st.master_range(gs), beta=st.master_range(bs), running_mean=_all(self.bn.running_mean),
+                 running_var=_all(self.bn.running_var), mean=_all(self.mean), invstd=_all(self.invstd), scale=_all(self.scale),
+                 shift=_all(self.shift), x=x, residual=res, y=y if y.buf.numel() else None)
+        if p.training:
+            t.update(partials=_all(self.conv.stats), local_stats=(self.group.local, self.loff, self.loff + self.width))
+        if p.training and p.with_grad:
+            t.update(dy=y.grad, dx=x.grad, dres=res.grad if res is not None else None, red_ws=_all(self.red_ws),
+                     sums=(p.zero_arena, self.sums_off, self.sums_off + self.sums_len),
+                     dgamma=st.grad_range(gs), dbeta=st.grad_range(bs))
+        return {k: v for k, v in t.items() if v is not None}
+
+    PHASE_WRITES = {'stats': ('local_stats',), 'finalize': ('running_mean', 'running_var', 'mean', 'invstd', 'scale', 'shift'),
+                    'apply': ('y',), 'red': ('sums', 'red_ws'), 'bapply': ('dgamma', 'dbeta', 'dx', 'dres')}
+
+    def written(self, *phases):
+        """the accesses of touched() that the launches of `phases` write for this member (none where a fusion runs the phase)"""
+        t = self.touched()
+        return [t[f] for ph in phases if not (ph in BN_PHASES and self.fused(ph)) for f in self.PHASE_WRITES[ph] if f in t]
+
     def fused(self, phase):
         """a fusion of Plan.finalize runs `phase` of this member in place of the group's own launch (the apply: on load in the
         consuming conv, in the gate or in the max-pool)"""
@@ -1313,7 +1396,7 @@ def _bn_apply_launch(m):
     p, it = m.plan, m.item()
     return Launch('bn_apply', 'bn_apply<%s>' % _dt(p.dtype), p.lib.dv_bn_apply,
                   (p.dtype, it.x, it.ldx, it.scale, it.shift, it.residual, it.ldr, it.y, it.ldy, it.M, it.C, it.fwd_flags),
-                  m.nbytes('apply'), 0, 'M%d C%d' % (m.M, m.C))
+                  m.nbytes('apply'), 0, 'M%d C%d' % (m.M, m.C), reads=[m.x, _all(m.scale), _all(m.shift), m.res], writes=[m.y])
 
 
 class BNGroupOp(Op):
@@ -1365,11 +1448,14 @@ class BNGroupOp(Op):
             it = m.item()
             if m.bn.running_mean is None:
                 raise NotImplementedError('eval-mode BatchNorm without running statistics')
+            t = m.touched()
             f.append(Launch('bn_eval_coeffs', 'bn_eval_coeffs', lib.dv_bn_eval_coeffs,
-                            (it.gamma, it.beta, it.running_mean, it.running_var, it.eps, it.C, it.scale, it.shift)))
+                            (it.gamma, it.beta, it.running_mean, it.running_var, it.eps, it.C, it.scale, it.shift),
+                            reads=[t[k] for k in ('gamma', 'beta', 'running_mean', 'running_var')], writes=[t['scale'], t['shift']]))
             if m.conv_bias is not None:          # y = scale*(conv + b) + shift
                 f.append(Launch('bn_bias_shift', 'addcmul', lib.dv_addcmul_f32,
-                                (it.shift, it.scale, st.w_master(st.slot(m.conv_bias)), 1.0, it.C)))
+                                (it.shift, it.scale, st.w_master(st.slot(m.conv_bias)), 1.0, it.C),
+                                reads=[t['shift'], t['scale'], st.master_range(st.slot(m.conv_bias))], writes=[t['shift']]))
             if not m.fused('apply'):             # (else: the pool op applies it while it reads its windows)
                 f.append(_bn_apply_launch(m))
         return f, []
@@ -1384,15 +1470,19 @@ class BNGroupOp(Op):
         rc = p.comm.rccl
         if rc is not None:       # in-stream: ordered with the reduce kernels before and the finalize after, no hop
             f.append(Launch('syncbn_allgather', 'rccl:all_gather', rc.all_gather,
-                            (local.data_ptr(), gathered.data_ptr(), self.width), 4 * self.width * (R + 1)))
+                            (local.data_ptr(), gathered.data_ptr(), self.width), 4 * self.width * (R + 1),
+                            reads=[_all(local)], writes=[_all(gathered)]))
         elif p.comm.flat_gather:
-            f.append(HostStep('syncbn_allgather', lambda: dist.all_gather_into_tensor(gathered, local, group=group)))
+            f.append(HostStep('syncbn_allgather', lambda: dist.all_gather_into_tensor(gathered, local, group=group),
+                              reads=[_all(local)], writes=[_all(gathered)]))
         else:
-            f.append(HostStep('syncbn_allgather', lambda: dist.all_gather(list(gathered.unbind(0)), local, group=group)))
+            f.append(HostStep('syncbn_allgather', lambda: dist.all_gather(list(gathered.unbind(0)), local, group=group),
+                              reads=[_all(local)], writes=[_all(gathered)]))
         if p.with_grad:
             first, last = self.members[0], self.members[-1]
             lo, n = first.sums_off, last.sums_off + last.sums_len - first.sums_off
             pending = []
+            inplace = dict(reads=[(p.zero_arena, lo, lo + n)], writes=[(p.zero_arena, lo, lo + n)])      # the all-reduce's, on its start step
 
             # In place on the (contiguous) replica accumulators of the group, asynchronously: Plan.finalize moves
             # the weight-gradient kernels of the layers above between `start` and `wait`, so the exchange latency
@@ -1407,7 +1497,7 @@ class BNGroupOp(Op):
                 # the two event hops of the overlapped form cost ~24 us per exchange, more than a small RCCL
                 # all-reduce inside a node takes -- step 11.71 ms overlapped vs 10.95 ms in-stream (10.74 without exchange)
                 b.append(Launch('syncbn_allreduce', 'rccl:all_reduce', lambda stream: rc.all_reduce(p.zero_ptr(lo), n, stream), (),
-                                8 * n))
+                                8 * n, **inplace))
             elif rc is not None:
                 # same overlap with RCCL called directly: main --event--> exchange stream: all-reduce --event--> main
                 ev_a, ev_b = torch.cuda.Event(), torch.cuda.Event()
@@ -1422,10 +1512,10 @@ class BNGroupOp(Op):
 
                 def _wait_direct(stream):
                     torch.cuda.current_stream(dev).wait_event(ev_b)
-                b.append(StreamStep('syncbn_allreduce_start', _start_direct))
+                b.append(StreamStep('syncbn_allreduce_start', _start_direct, **inplace))
                 b.append(StreamStep('syncbn_allreduce_wait', _wait_direct))
             else:
-                b.append(HostStep('syncbn_allreduce_start', _start))
+                b.append(HostStep('syncbn_allreduce_start', _start, **inplace))
                 b.append(HostStep('syncbn_allreduce_wait', _wait))
         return f, b
 
@@ -1447,30 +1537,38 @@ class BNGroupOp(Op):
         bwd_in = (p.dtype, it.dy, it.lddy, it.y, it.ldy, it.x, it.ldx, it.mean, it.invstd)
         xf, xb = self._exchange() if exchange else ([], [])
         nb = {ph: sum(m.nbytes(ph) for m in ms) for ph in (BN_PHASES if p.with_grad else BN_PHASES[:2])}      # bytes per phase
+        # every launch of the group reads what the members' items point at (and the table of them); it writes its phases' part
+        rd = [a for m_ in ms for a in m_.touched().values()] + ([_all(self._items)] if tab else [])
+
+        def wr(*phases):
+            return [a for m_ in ms for a in m_.written(*phases)]
 
         # forward: statistics -> exchange -> finalize -> conv bias -> apply
         if fwd_multi:
             f = [Launch('bn_stats_multi', 'bn_stats_multi', lib.dv_bn_stats_multi, (tab, n, 0 if exchange else 1, ends['stats']),
-                        nb['stats'])]
+                        nb['stats'], reads=rd, writes=wr('stats') if exchange else wr('stats', 'finalize'))]
         elif exchange:
-            f = [Launch('bn_reduce_stats', 'bn_reduce_stats', lib.dv_bn_reduce_stats, stats_in, nb['stats'])]
+            f = [Launch('bn_reduce_stats', 'bn_reduce_stats', lib.dv_bn_reduce_stats, stats_in, nb['stats'], reads=rd, writes=wr('stats'))]
         else:
-            f = [Launch('bn_stats_finalize', 'bn_reduce_stats', lib.dv_bn_stats_finalize, stats_in + finalize, nb['stats'])]
+            f = [Launch('bn_stats_finalize', 'bn_reduce_stats', lib.dv_bn_stats_finalize, stats_in + finalize, nb['stats'],
+                        reads=rd, writes=wr('stats', 'finalize'))]
         f += xf
         if exchange and fwd_multi:       # ONE finalize launch for the group after the all-gather (instead of one per member)
             f.append(Launch('bn_finalize_multi', 'bn_finalize_multi', lib.dv_bn_finalize_multi,
                             (tab, n, sum((m.C + 127) // 128 for m in ms), self.local.data_ptr(), self.gathered.data_ptr(), R,
-                             self.width)))
+                             self.width), reads=rd + [_all(self.local), _all(self.gathered)], writes=wr('finalize')))
         elif exchange:
             f.append(Launch('bn_finalize', 'bn_finalize', lib.dv_bn_finalize,
-                            (self.gathered.data_ptr() + 4 * m.loff, R, self.width, it.C) + finalize))
+                            (self.gathered.data_ptr() + 4 * m.loff, R, self.width, it.C) + finalize,
+                            reads=rd + [_all(self.gathered)], writes=wr('finalize')))
         if any(m.conv_bias is not None and m.bn.running_mean is not None for m in ms):
             assert n == 1                # conv bias in front of the BN: only the running mean sees it
             f.append(Launch('bn_bias_running_mean', 'addcmul', lib.dv_addcmul_f32,
-                            (it.running_mean, st.w_master(st.slot(m.conv_bias)), 0, it.momentum, it.C)))
+                            (it.running_mean, st.w_master(st.slot(m.conv_bias)), 0, it.momentum, it.C),
+                            reads=[_all(m.bn.running_mean), st.master_range(st.slot(m.conv_bias))], writes=[_all(m.bn.running_mean)]))
         if fwd_multi and ends['apply']:
             f.append(Launch('bn_apply_multi', 'bn_apply_multi<%s>' % dt, lib.dv_bn_apply_multi, (p.dtype, tab, n, ends['apply']),
-                            nb['apply']))
+                            nb['apply'], reads=rd, writes=wr('apply')))
         elif not fwd_multi and not m.fused('apply'):
             f.append(_bn_apply_launch(m))
         if not p.with_grad:
@@ -1491,21 +1589,25 @@ class BNGroupOp(Op):
                 red_fn, app_fn, suffix = lib.dv_bn_bwd_reduce_multi_gated, lib.dv_bn_bwd_apply_multi_gated, '+gate'
                 gargs = (gop.g.data_ptr(), gop.dmean.data_ptr(), gop.cat.S, gop.cat.C, self._gate_off.data_ptr())
                 gbytes = sum(8 * gop.cat.N * m.C for m in gated)
+                rd = rd + [_all(gop.g), _all(gop.dmean), _all(self._gate_off)]
             if ends['red'] or gated:
                 b_red.append(Launch('bn_bwd_reduce_multi', 'bn_bwd_reduce_multi<%s>%s' % (dt, suffix), red_fn,
-                                    (p.dtype, tab, n, ends['red']) + gargs, nb['red'] + gbytes))
+                                    (p.dtype, tab, n, ends['red']) + gargs, nb['red'] + gbytes,
+                                    reads=rd, writes=wr('red')))
             if ends['bapply'] or gated:
                 b_app.append(Launch('bn_bwd_apply_multi', 'bn_bwd_apply_multi<%s>%s' % (dt, suffix), app_fn,
-                                    (p.dtype, tab, n, ends['bapply'], max(m.C for m in ms)) + gargs, nb['bapply'] + gbytes))
+                                    (p.dtype, tab, n, ends['bapply'], max(m.C for m in ms)) + gargs, nb['bapply'] + gbytes,
+                                    reads=rd, writes=wr('bapply')))
         else:
             if not m.fused('red'):       # (the reduce writes no dres: without DV_ACCUM)
                 b_red.append(Launch('bn_bwd_reduce', 'bn_bwd_reduce<%s>' % dt, lib.dv_bn_bwd_reduce,
                                     bwd_in + (it.M, it.C, it.bwd_flags & ~DV_ACCUM, it.sums, it.n_rep, it.red_ws),
-                                    nb['red'], 0, shape))
+                                    nb['red'], 0, shape, reads=rd, writes=wr('red')))
             if not m.fused('bapply'):
                 b_app.append(Launch('bn_bwd_apply', 'bn_bwd_apply<%s>' % dt, lib.dv_bn_bwd_apply,
                                     bwd_in + (it.gamma, it.sums, it.n_rep, it.inv_count, it.dparam_scale, it.dgamma, it.dbeta, it.dx,
-                                              it.lddx, it.dres, it.lddres, it.M, it.C, it.bwd_flags), nb['bapply'], 0, shape))
+                                              it.lddx, it.dres, it.lddres, it.M, it.C, it.bwd_flags), nb['bapply'], 0, shape,
+                                    reads=rd, writes=wr('bapply')))
         for l in b_app:
             l.gend = _gend(*[st.slot(t) for m in ms for t in (m.bn.weight, m.bn.bias)])
         return f, b_red + xb + b_app
@@ -1542,16 +1644,18 @@ class PoolOp(Op):
             m = self.bn_member
             f = [Launch('bn_apply_maxpool', 'bn_apply_maxpool<%s>' % dt, lib.dv_bn_apply_maxpool,
                         (C.byref(self.d_fused), m.x.ptr, m.scale.data_ptr(), m.shift.data_ptr(), y.ptr, self.idx.data_ptr()),
-                        _abytes(x) + _abytes(y) + y.rows * x.C)]
+                        _abytes(x) + _abytes(y) + y.rows * x.C, reads=[m.x, _all(m.scale), _all(m.shift)], writes=[y, _all(self.idx)])]
         else:
             f = [Launch('maxpool_fwd', 'maxpool_fwd<%s>' % dt, lib.dv_maxpool3d_fwd,
-                        (C.byref(self.d), x.ptr, y.ptr, self.idx.data_ptr()), _abytes(x) + _abytes(y) + y.rows * x.C)]
+                        (C.byref(self.d), x.ptr, y.ptr, self.idx.data_ptr()), _abytes(x) + _abytes(y) + y.rows * x.C,
+                        reads=[x], writes=[y, _all(self.idx)])]
         b = []
         if self.need_dx:
             acc = bool(self.acc.get('x'))
             b.append(Launch('maxpool_bwd', 'maxpool_bwd<%s>' % dt, lib.dv_maxpool3d_bwd,
                             (C.byref(self.d), y.grad.ptr, self.idx.data_ptr(), x.grad.ptr, DV_ACCUM if acc else 0),
-                            _abytes(y) + y.rows * x.C + _abytes(x) * (2 if acc else 1)))
+                            _abytes(y) + y.rows * x.C + _abytes(x) * (2 if acc else 1),
+                            reads=[y.grad, _all(self.idx)] + ([x.grad] if acc else []), writes=[x.grad]))
         return f, b
 
 
@@ -1615,6 +1719,8 @@ class GateGroupOp(Op):
         N, Ct, S, dt = cat.N, cat.C, cat.S, _dt(p.dtype)
         mean, g = self.mean.data_ptr(), self.g.data_ptr()
         fwd_d, bwd_d = [], []
+        wm = [st.master_range(st.slot(fc.weight)) for fc, _, _ in self.fcs]
+        wg = [st.grad_range(st.slot(fc.weight)) for fc, _, _ in self.fcs]
         bias0 = None
         for fc, off, w in self.fcs:
             ws, bs = st.slot(fc.weight), st.slot(fc.bias)
@@ -1633,11 +1739,12 @@ class GateGroupOp(Op):
                                   M=w, N=w, K=N, flags=DV_ACCUM, alpha=1.0))               # dW += dpre^T @ mean
         self._ft, ftiles = self._table(fwd_d)
         f = [Launch('gate_mean', 'spatial_mean<%s>' % dt, lib.dv_spatial_mean,
-                    (p.dtype, cat.ptr, cat.ld, N, S, Ct, mean), _abytes(cat)),
+                    (p.dtype, cat.ptr, cat.ld, N, S, Ct, mean), _abytes(cat), reads=[cat], writes=[_all(self.mean)]),
              Launch('gate_fc', 'gemm_f32_grouped', lib.dv_gemm_f32_grouped, (self._ft.data_ptr(), len(fwd_d), ftiles),
-                    sum(w * w * 4 for _, _, w in self.fcs), sum(2 * N * w * w for _, _, w in self.fcs)),
+                    sum(w * w * 4 for _, _, w in self.fcs), sum(2 * N * w * w for _, _, w in self.fcs),
+                    reads=[_all(self._ft), _all(self.mean), (st.master, bias0.off, bias0.off + Ct)] + wm, writes=[_all(self.g)]),
              Launch('gate_scale', 'rowscale<%s,0>' % dt, lib.dv_gate_scale,
-                    (p.dtype, cat.ptr, cat.ld, g, N, S, Ct, cat.ptr, cat.ld), 2 * _abytes(cat))]
+                    (p.dtype, cat.ptr, cat.ld, g, N, S, Ct, cat.ptr, cat.ld), 2 * _abytes(cat), reads=[cat, _all(self.g)], writes=[cat])]
         if self.fused:
             # the members' own table (the two kernels read x, y, scale, shift and C of it) and their first columns in mean / g
             arr = (L.BnItem * len(self.fused))(*[m.item() for m in self.fused])
@@ -1646,21 +1753,27 @@ class GateGroupOp(Op):
             p.bytes += self._items.numel() + 4 * self._gate_off.numel()
             tab, goff, nm = self._items.data_ptr(), self._gate_off.data_ptr(), len(self.fused)
             xbytes = sum(_abytes(m.x) for m in self.fused)
+            rd = [a for m in self.fused for a in m.touched().values()] + [_all(self._items), _all(self._gate_off)]
             f[0] = Launch('gate_mean_bn', 'gate_mean_bn<%s>' % dt, lib.dv_gate_mean_bn,
-                          (p.dtype, tab, nm, goff, N, S, Ct, mean), xbytes)
+                          (p.dtype, tab, nm, goff, N, S, Ct, mean), xbytes, reads=rd, writes=[_all(self.mean)])
             f[2] = Launch('gate_scale_bn', 'gate_scale_bn<%s>' % dt, lib.dv_gate_scale_bn,
-                          (p.dtype, tab, nm, goff, g, N, S, Ct), xbytes + _abytes(cat) + 4 * N * Ct)
+                          (p.dtype, tab, nm, goff, g, N, S, Ct), xbytes + _abytes(cat) + 4 * N * Ct,
+                          reads=rd + [_all(self.g)], writes=[m.y for m in self.fused])
         b = []
         if p.with_grad:
             dy = cat.grad
             self._bt, btiles = self._table(bwd_d)
             b = [Launch('gate_bwd_reduce', 'gate_bwd_reduce<%s>' % dt, lib.dv_gate_bwd_reduce,
-                        (p.dtype, dy.ptr, dy.ld, cat.ptr, cat.ld, g, N, S, Ct, self.dpre.data_ptr(), 1), 2 * _abytes(cat)),
+                        (p.dtype, dy.ptr, dy.ld, cat.ptr, cat.ld, g, N, S, Ct, self.dpre.data_ptr(), 1), 2 * _abytes(cat),
+                        reads=[dy, cat, _all(self.g)], writes=[_all(self.dpre)]),
                  Launch('gate_fc_bwd', 'gemm_f32_grouped', lib.dv_gemm_f32_grouped, (self._bt.data_ptr(), len(bwd_d), btiles),
-                        sum(w * w * 12 for _, _, w in self.fcs), sum(4 * N * w * w for _, _, w in self.fcs)),
-                 Launch('gate_db', 'reduce_rows', lib.dv_colsum_f32, (self.dpre.data_ptr(), Ct, N, Ct, st.w_grad(bias0))),
+                        sum(w * w * 12 for _, _, w in self.fcs), sum(4 * N * w * w for _, _, w in self.fcs),
+                        reads=[_all(self._bt), _all(self.dpre), _all(self.mean)] + wm + wg, writes=[_all(self.dmean)] + wg),
+                 Launch('gate_db', 'reduce_rows', lib.dv_colsum_f32, (self.dpre.data_ptr(), Ct, N, Ct, st.w_grad(bias0)),
+                        reads=[_all(self.dpre), (st.grad, bias0.off, bias0.off + Ct)], writes=[(st.grad, bias0.off, bias0.off + Ct)]),
                  Launch('gate_bwd_apply', 'rowscale<%s,1>' % dt, lib.dv_gate_bwd_apply,
-                        (p.dtype, dy.ptr, dy.ld, g, self.dmean.data_ptr(), N, S, Ct, dy.ptr, dy.ld, 0), 2 * _abytes(cat))]
+                        (p.dtype, dy.ptr, dy.ld, g, self.dmean.data_ptr(), N, S, Ct, dy.ptr, dy.ld, 0), 2 * _abytes(cat),
+                        reads=[dy, _all(self.g), _all(self.dmean)], writes=[dy])]
             b[1].gend = _gend(*[st.slot(fc.weight) for fc, _, _ in self.fcs])
             b[2].gend = _gend(*[st.slot(fc.bias) for fc, _, _ in self.fcs])
             if self.fused:
@@ -1686,11 +1799,11 @@ class MeanOp(Op):
     def launches(self):
         p, x, dt = self.plan, self.x, _dt(self.plan.dtype)
         f = [Launch('avgpool', 'spatial_mean<%s>' % dt, p.lib.dv_spatial_mean,
-                    (p.dtype, x.ptr, x.ld, x.N, x.S, x.C, self.out.data_ptr()), _abytes(x))]
+                    (p.dtype, x.ptr, x.ld, x.N, x.S, x.C, self.out.data_ptr()), _abytes(x), reads=[x], writes=[_all(self.out)])]
         b = []
         if p.with_grad and x.grad is not None:
             acc = bool(self.acc.get('x'))
             b = [Launch('avgpool_bwd', 'rowscale<%s,2>' % dt, p.lib.dv_spatial_mean_bwd,
                         (p.dtype, self.dout.data_ptr(), x.N, x.S, x.C, x.grad.ptr, x.grad.ld, DV_ACCUM if acc else 0),
-                        _abytes(x) * (2 if acc else 1))]
+                        _abytes(x) * (2 if acc else 1), reads=[_all(self.dout)] + ([x.grad] if acc else []), writes=[x.grad])]
         return f, b

@@ -1,7 +1,12 @@
 """The coverage ledger of the C ABI: every entry of dualvar_amd._lib.SIGNATURES -> (the test file that holds its strongest
 reference test, the kind of that reference).  tests/test_abi_and_host.py::test_every_abi_entry_names_its_strongest_test keeps
 the keys equal to SIGNATURES and checks that each file mentions its entry, so a new entry has to say here how it is tested and
-whatever is still 'torch fp32 only' stays visible as the next gap."""
+whatever is still 'torch fp32 only' stays visible as the next gap.
+
+The ledger is per entry.  Above it: tests/test_plan_audit_gpu.py checks every op of a backbone plan against float64, and
+tests/test_plan_streams_host.py / tests/test_plan_streams_gpu.py (support: tests/plan_hazards.py) check WHEN the launches of a
+plan run relative to each other -- what each launch reads and writes, and that the backward's side stream orders every pair
+that conflicts."""
 
 FLOAT64 = 'float64'
 BIT_EXACT = 'bit-exact against PIL / torch cast'
