@@ -22,15 +22,16 @@ struct fp8e5_t { unsigned char v; };
 #define DV_WAVE 64
 
 // ------------------------------------------------------------------ fast unsigned division
-// q = n / d for 0 <= n < 2^31, d >= 1:  q = (umulhi(n, mul) + n) >> shr
+// q = n / d for 0 <= n < 2^31, 1 <= d <= 2^31:  q = (umulhi(n, mul) + n) >> shr
 struct FastDiv {
   uint32_t mul, shr, d, _pad;
 };
-static inline FastDiv make_fastdiv(uint32_t d) {
+// (host: launch arguments; device: the multi-tensor kernels, whose divisor comes from the item table)
+__host__ __device__ static inline FastDiv make_fastdiv(uint32_t d) {
   FastDiv f;
   f.d = d;
   uint32_t s = 0;
-  while ((1ull << s) < d) ++s;
+  while ((1u << s) < d) ++s;
   f.shr = s;
   f.mul = (uint32_t)((((1ull << s) - d) << 32) / d + 1);
   f._pad = 0;

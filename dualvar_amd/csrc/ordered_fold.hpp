@@ -1,6 +1,6 @@
 // The ticketed hand-off of the ordered reductions: workgroups pass rows of partial sums to the one that arrives last, which adds
 // them in a fixed order -- no float atomics, so the sums do not depend on the order workgroups finish in.  Users: the
-// BatchNorm-backward reduces (elementwise.hip: ordered_fold), the same reduce inside the LDS-staged data gradient's epilogue
+// BatchNorm-backward reduces (streaming.hpp: ordered_fold), the same reduce inside the LDS-staged data gradient's epilogue
 // (conv_tap.hip: dv_conv3d_dgrad_bn_ws) and the ordered K-split of dv_infonce_fwd (loss.hip: gemm_f32_splitk_kernel).
 // Device side only, apart from the ticket / row layout arithmetic below, which the host wrappers size their workspaces with.
 #pragma once

@@ -1,11 +1,11 @@
 """The case tables of tests/test_batchnorm_single_gpu.py: the single-tensor BatchNorm entries (dv_bn_reduce_stats,
 dv_bn_stats_finalize, dv_bn_finalize, dv_bn_apply, dv_bn_bwd_reduce, dv_bn_bwd_apply) at the shapes where their wrappers in
-csrc/elementwise.hip decide something on their own.  Every row writes out as literals what it was written to hit; the reduce
+csrc/batchnorm.hip decide something on their own.  Every row writes out as literals what it was written to hit; the reduce
 literals are read back through dv_bn_bwd_blocks / dv_bn_bwd_reduce_workspace and the others recomputed from the launch rules
 quoted below by tests/test_abi_and_host.py::test_bn_case_table_blocks_and_coverage, without a GPU, so a retune that moves a
 row off its edge is named there.  The shapes are the smallest that reach each edge; C stays small wherever M is large.
 
-The launch rules, as csrc/elementwise.hip has them:
+The launch rules, as csrc/batchnorm.hip has them (column_reduce and ordered_fold: csrc/streaming.hpp):
   dv_bn_reduce_stats / dv_bn_stats_finalize   grid C, block n_tiles >= 2048 ? 1024 : 256; the last tile holds M - (n_tiles-1) tile_rows rows
   dv_bn_finalize                              grid ceil(C / 128), block 128
   dv_bn_apply                                 total = M * (CP / V) vectors, grid min(4096, ceil(total / 256)), block 256, grid-stride
@@ -25,21 +25,21 @@ FOLD_GROUP = 32
 BAPPLY_MAX_C = 5120
 
 
-# the rules above as csrc/elementwise.hip spells them: (text, occurrences), and for a rule that lives in another file of csrc
-# that file's name.  The case-table test finds each in its source, so a block size, cap or limit that is retuned there has to
+# the rules above as csrc spells them: (text, {file it lives in: occurrences there}).  The case-table test finds each in its
+# home as often as quoted and in none of the other files it lists, so a block size, cap or limit that is retuned there has to
 # be retuned in this file's rules (and rows) too.
 QUOTED_RULES = [
-    ('constexpr int kThreads = 256;', 1),
-    ('static inline int grid_for(int64_t work_items, int max_blocks = 4096) {', 1, 'common.hpp'),   # shared with optim.hip
-    ('int64_t b = (work_items + 255) / 256;', 1, 'common.hpp'),                    # ... in blocks of kThreads
-    ('dim3(C), dim3(n_tiles >= 2048 ? 1024 : kThreads)', 2),                       # dv_bn_reduce_stats, dv_bn_stats_finalize
-    ('hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 127) / 128), dim3(128)', 1),
-    ('hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(grid_for(total)), dim3(kThreads)', 1),
-    ('int grid = grid_for(total, 2048);', 1),                                      # dv_bn_bwd_apply
-    ('if (3 * CP * 4 > 60 * 1024) return DV_EUNSUPPORTED;', 1),
-    ('const int64_t rpb = (M + blocks - 1) / blocks;', 2),                         # dv_bn_bwd_reduce (and its max-pool twin)
-    ('constexpr int kFoldGroup = 32;', 1, 'ordered_fold.hpp'),                      # shared with the other ordered folds
-    ('for (int cvb = 0; cvb < CV; cvb += kThreads) {', 1),                         # column_reduce
+    ('constexpr int kThreads = 256;', {'streaming.hpp': 1}),
+    ('static inline int grid_for(int64_t work_items, int max_blocks = 4096) {', {'common.hpp': 1}),   # shared with optim.hip
+    ('int64_t b = (work_items + 255) / 256;', {'common.hpp': 1}),                  # ... in blocks of kThreads
+    ('dim3(C), dim3(n_tiles >= 2048 ? 1024 : kThreads)', {'batchnorm.hip': 2}),    # dv_bn_reduce_stats, dv_bn_stats_finalize
+    ('hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 127) / 128), dim3(128)', {'batchnorm.hip': 1}),
+    ('hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(grid_for(total)), dim3(kThreads)', {'batchnorm.hip': 1}),
+    ('int grid = grid_for(total, 2048);', {'batchnorm.hip': 1}),                   # dv_bn_bwd_apply
+    ('if (3 * CP * 4 > 60 * 1024) return DV_EUNSUPPORTED;', {'batchnorm.hip': 1}),
+    ('const int64_t rpb = (M + blocks - 1) / blocks;', {'batchnorm.hip': 1, 'pool.hip': 1}),   # dv_bn_bwd_reduce; its max-pool twin
+    ('constexpr int kFoldGroup = 32;', {'ordered_fold.hpp': 1}),                    # shared with the other ordered folds
+    ('for (int cvb = 0; cvb < CV; cvb += kThreads) {', {'streaming.hpp': 1}),      # column_reduce
 ]
 
 # ------------------------------------------------------------------------------------------------------------ statistics

@@ -22,9 +22,9 @@ def gamma(n):
     return n * U / (1 - n * U)
 
 
-# ---------------------------------------------------------------------------------------------------- csrc/elementwise.hip
+# ------------------------------------------------------------------------------- csrc/streaming.hpp, csrc/batchnorm.hip
 def column_chain(rows, CP, dtype, NS, extra=0):
-    """longest chain of sequential fp32 additions column_reduce (elementwise.hip) forms over `rows` rows of CP columns with NS
+    """longest chain of sequential fp32 additions column_reduce (streaming.hpp) forms over `rows` rows of CP columns with NS
     sums per column: rows per thread, then ceil(log2 rg) for the pairwise fold of the rg row groups; `extra` is what the caller
     adds behind it (block folds, or the blocks that add to one replica with float atomics; 0: every output has one owner)"""
     V, CV = vec(dtype), CP // vec(dtype)
@@ -39,7 +39,7 @@ def column_chain(rows, CP, dtype, NS, extra=0):
 
 
 def bwd_reduce_chain(M, C_, dtype, nblk):
-    """longest chain of sequential fp32 additions of bn_bwd_reduce_body + ordered_fold (elementwise.hip): column_chain over
+    """longest chain of sequential fp32 additions of bn_bwd_reduce_body + ordered_fold (streaming.hpp): column_chain over
     the rows of one block, the fold of a group of <= 32 block rows, the fold of the groups"""
     return column_chain(ceil_div(M, nblk), cp8(C_), dtype, 2, min(32, nblk) + ceil_div(nblk, 32))
 

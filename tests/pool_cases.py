@@ -1,5 +1,5 @@
 """The case tables of tests/test_pool_gate_float64_gpu.py: MaxPool3d problems, per-sample column reductions and the capped
-grid-stride launches of csrc/elementwise.hip.  Every row names the launch route it was written for; the host-side queries
+grid-stride launches of csrc/pool.hip, csrc/gate.hip and csrc/elementwise.hip.  Every row names the launch route it was written for; the host-side queries
 (dv_maxpool3d_route, dv_spatial_chunks) are compared with those literals by
 tests/test_abi_and_host.py::test_pool_case_table_routes_and_coverage, without a GPU, so a threshold that moves a case away
 from its route is named there.  The shapes are the smallest that still reach each behaviour."""

@@ -784,16 +784,17 @@ BN_TABLE_ROWS = [
 def test_bn_case_table_blocks_and_coverage():
     """tests/bn_cases.py, the tables tests/test_batchnorm_single_gpu.py runs: every literal of every row against the host
     queries (dv_bn_bwd_blocks, dv_bn_bwd_reduce_workspace) and against the launch rules the table quotes from
-    csrc/elementwise.hip (the fold's group size: csrc/ordered_fold.hpp; grid_for: csrc/common.hpp) -- each of which is found in its source as quoted --
+    csrc/batchnorm.hip (the max-pool twin of the reduce: csrc/pool.hip; kThreads, column_reduce: csrc/streaming.hpp; the fold's group size:
+    csrc/ordered_fold.hpp; grid_for: csrc/common.hpp) -- each of which is found in its home as often as quoted, and in no other file listed here --
     and the tables as a whole reach every member of bn_cases.REQUIRED and every row listed above.  A retune of dv_bn_bwd_blocks, of the 2048-tile threshold or of a grid cap
     that moves a row off its edge is named here."""
     from tests import bn_cases as T
-    homes = ('elementwise.hip', 'ordered_fold.hpp', 'common.hpp')
+    homes = ('batchnorm.hip', 'pool.hip', 'gate.hip', 'elementwise.hip', 'streaming.hpp', 'ordered_fold.hpp', 'common.hpp')
     src = {f: open(os.path.join(ROOT, 'dualvar_amd', 'csrc', f)).read() for f in homes}
-    for text, count, *home in T.QUOTED_RULES:
-        home = home[0] if home else 'elementwise.hip'
-        for f in homes:                 # as often as quoted in the file the rule lives in, and not in the other
-            want = count if f == home else 0
+    for text, where in T.QUOTED_RULES:
+        assert where and set(where) <= set(homes), (text, where)
+        for f in homes:                 # as often as quoted in the file(s) the rule lives in, and not in the others
+            want = where.get(f, 0)
             assert src[f].count(text) == want, 'csrc/%s no longer reads %r %d time(s): tests/bn_cases.py quotes it' % (f, text, want)
     assert (T.BLOCK, T.APPLY_CAP, T.BAPPLY_CAP, T.FOLD_GROUP, T.STATS_WIDE_FROM, T.BAPPLY_MAX_C) == (256, 4096, 2048, 32, 2048, 5120)
     moved, seen = [], set()
@@ -991,8 +992,8 @@ def test_every_abi_entry_names_its_strongest_test():
 
 def test_ordered_fold_protocol_has_one_home():
     """The ticketed hand-off of the ordered reductions (sc1 stores, drained counter, agent-scope ticket, sc1 loads) lies outside
-    the HIP memory model and is guarded for gfx950 in csrc/ordered_fold.hpp; its three users (elementwise.hip, conv_tap.hip,
-    loss.hip) call that header.  So no other source spells an agent-scope atomic of its own, and loss.hip no longer carries
+    the HIP memory model and is guarded for gfx950 in csrc/ordered_fold.hpp; its three users (streaming.hpp, for the BatchNorm
+    backward of batchnorm.hip; conv_tap.hip; loss.hip) call that header.  So no other source spells an agent-scope atomic of its own, and loss.hip no longer carries
     a bare drain: a fourth copy of the protocol would fail here."""
     csrc = os.path.join(ROOT, 'dualvar_amd', 'csrc')
     files = sorted(f for f in os.listdir(csrc) if f.endswith(('.hip', '.hpp')))

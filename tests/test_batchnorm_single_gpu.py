@@ -37,9 +37,9 @@ chain against the float64 layer 0.31 (fp32) / 0.99 (bf16: the store's half ulp);
 sums 0.0006.  In units of u * sum|terms|, as the sibling file prints them: ordered sums 1.9 / 2.2 (chain 15 - 45), SyncBN 0.5 /
 0.7, dx 3.6 of the 12 u allowed through the ordered sums and 14.4 behind four atomic replicas (M = 220 000: the 12 u plus the
 three additions of the fold, which weigh on k3 where sum g cancels).  Every (A) quantity is bit-equal.  The file takes 13 s
-(168 tests, the longest 0.3 s).
+(174 tests, the longest 0.3 s).
 
-Four launch rules changed one at a time in a scratch build of csrc/elementwise.hip, and what noticed:
+Four launch rules changed one at a time in a scratch build of what is now csrc/batchnorm.hip, and what noticed:
   an empty reduce block stores no row      test_backward_against_float64[m20481_c8_r2-*] and [m300033_c8-*] (NaN in the sums)
   bid % n_rep -> 0 in the atomic form      test_backward_against_float64[m33_c83_accum-*] and [m2048_c3-*] (a replica is not
                                            the sum of its blocks; the total alone would not tell)
@@ -267,6 +267,73 @@ def test_finalize_against_float64(gpu, case):
     assert all(is_sent(t[C_:]) for t in out.values()), f'{w}: outputs past C'
     if c.running:
         assert bool((rm[C_:] == 0.625).all()) and bool((rv[C_:] == 0.625).all()), f'{w}: running statistics past C'
+
+
+# per-rank row counts of the three rank tables below: unequal, one of them a single row (its M2 is 0)
+FORM_COUNTS = {1: (37,), 2: (120, 1), 3: (64, 1, 300)}
+
+
+@pytest.mark.parametrize('running', [True, False], ids=['running', 'norunning'])
+@pytest.mark.parametrize('C_', [3, 83, 130])
+def test_finalize_forms_agree_bit_for_bit(gpu, C_, running):
+    """the finalize is one expression: on one seeded [R][stride] table dv_bn_finalize and dv_bn_finalize_multi (the table as a
+    one-item group) leave the same bytes in mean / invstd / scale / shift / running_mean / running_var, for R = 1, 2, 3;
+    and dv_bn_stats_finalize leaves the bytes of dv_bn_reduce_stats + dv_bn_finalize(R = 1) on the same partials (several
+    tiles with a one-row tail, and the single row whose count is 1).  C = 130 crosses the 128-channel block."""
+    gen = torch.Generator(device=gpu).manual_seed(1000 + C_)
+    CP, keys = cp8(C_), ('mean', 'invstd', 'scale', 'shift')
+    m = SimpleNamespace(C=C_, p={'gamma': chan(1 + 0.2 * torch.randn(C_, generator=gen, device=gpu), CP, gpu),
+                                 'beta': chan(0.1 * torch.randn(C_, generator=gen, device=gpu), CP, gpu)})
+    rm0 = torch.randint(-8, 9, (C_,), generator=gen, device=gpu).float() / 8
+    rv0 = 0.5 + torch.randint(0, 9, (C_,), generator=gen, device=gpu).float() / 8
+
+    def outputs():
+        return {k: sent((CP,), gpu) for k in keys}, (chan(rm0, CP, gpu) if running else None), (chan(rv0, CP, gpu) if running else None)
+
+    def same(a, b, what):
+        (oa, rma, rva), (ob, rmb, rvb) = a, b
+        assert not is_sent(oa['mean'][:C_]) and all(is_sent(t[C_:]) for t in list(oa.values()) + list(ob.values())), what
+        for k in keys:
+            assert equal_bits(oa[k], ob[k]), f'{what}: {k}: the two forms differ'
+        if running:
+            assert not torch.equal(rma[:C_], rm0) and equal_bits(rma, rmb) and equal_bits(rva, rvb), f'{what}: running statistics'
+
+    for R, counts in FORM_COUNTS.items():
+        stride = 2 * C_ + 1 + 5
+        n_r = torch.tensor(counts, dtype=torch.float64, device=gpu)
+        table = torch.full((R, stride), NAN, dtype=torch.float32, device=gpu)
+        table[:, :C_] = (n_r[:, None] * (0.5 + 0.3 * torch.randn((R, C_), generator=gen, device=gpu, dtype=torch.float64))).float()
+        table[:, C_:2 * C_] = ((n_r[:, None] - 1) * (0.25 + torch.rand((R, C_), generator=gen, device=gpu, dtype=torch.float64))).float()
+        table[:, 2 * C_] = n_r.float()
+        single, multi = outputs(), outputs()
+        finalize(table.data_ptr(), R, stride, m, *single)
+        arr = (L.BnItem * 1)()
+        it = arr[0]
+        it.C, it.local_stats, it.eps, it.momentum = C_, table.data_ptr(), EPS, MOM
+        it.gamma, it.beta = m.p['gamma'].data_ptr(), m.p['beta'].data_ptr()
+        it.running_mean, it.running_var = (multi[1].data_ptr(), multi[2].data_ptr()) if running else (0, 0)
+        it.mean, it.invstd, it.scale, it.shift = (multi[0][k].data_ptr() for k in keys)
+        tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(gpu)
+        launch('dv_bn_finalize_multi', tab.data_ptr(), 1, ceil_div(C_, 128), table.data_ptr(), table.data_ptr(), R, stride)
+        torch.cuda.synchronize()
+        same(single, multi, f'finalize vs finalize_multi, C={C_} R={R}')
+
+    for n_tiles, tile_rows, M in [(5, 8, 33), (1, 4, 1)]:
+        rows = torch.full((n_tiles,), float(tile_rows), dtype=torch.float64, device=gpu)
+        rows[-1] = M - (n_tiles - 1) * tile_rows
+        part = torch.empty((2, C_, n_tiles), dtype=torch.float32, device=gpu)
+        part[0] = (rows * (0.5 + 0.3 * torch.randn((C_, n_tiles), generator=gen, device=gpu, dtype=torch.float64))).float()
+        part[1] = ((rows - 1) * (0.25 + torch.rand((C_, n_tiles), generator=gen, device=gpu, dtype=torch.float64))).float()
+        fused, split = outputs(), outputs()
+        loc_f, loc_s = sent((2 * C_ + 1,), gpu), sent((2 * C_ + 1,), gpu)
+        launch('dv_bn_stats_finalize', part.data_ptr(), n_tiles, tile_rows, C_, M, C_, loc_f.data_ptr(), m.p['gamma'].data_ptr(),
+               m.p['beta'].data_ptr(), EPS, MOM, *(t.data_ptr() if t is not None else 0 for t in fused[1:]),
+               *(fused[0][k].data_ptr() for k in keys))
+        launch('dv_bn_reduce_stats', part.data_ptr(), n_tiles, tile_rows, C_, M, C_, loc_s.data_ptr())
+        finalize(loc_s.data_ptr(), 1, 2 * C_ + 1, m, *split)
+        torch.cuda.synchronize()
+        assert equal_bits(loc_f, loc_s) and float(loc_f[2 * C_]) == M, f'local row, C={C_} M={M}'
+        same(fused, split, f'stats_finalize vs reduce_stats + finalize, C={C_} M={M}')
 
 
 # ----------------------------------------------------------------------------------------------------------- apply

@@ -1,4 +1,4 @@
-"""The pooling, self-gating, spatial-mean, small fp32 helper and ingest kernels of csrc/elementwise.hip against plain float64
+"""The pooling (csrc/pool.hip), self-gating and spatial-mean (csrc/gate.hip), small fp32 helper and ingest kernels (csrc/elementwise.hip) against plain float64
 restatements of include/dualvar_hip.h, through the C ABI on explicit tensors, on every launch route of tests/pool_cases.py
 (tests/test_abi_and_host.py::test_pool_case_table_routes_and_coverage pins each row to its route without a GPU).
 
