@@ -250,7 +250,7 @@ RANKEVAL_SIGNATURES = {
     'dv_rankeval_finish': [P, I32, P, I32, I32, P, I32, P, P, P, P, P, P, P],
 }
 
-# name -> argtypes of include/dualvar_conv_pair.h (two independent convs in one grid: csrc/conv.hip, csrc/conv_tap.hip)
+# name -> argtypes of include/dualvar_conv_pair.h (two independent convs in one grid: csrc/conv.hip; kernels csrc/conv_gemm.hpp, csrc/conv_tap.hip)
 PAIR_SIGNATURES = {
     'dv_conv3d_pair_ok': [CD, CD, I32],
     'dv_conv3d_fwd_pair': [CD, P, P, P, P, CD, P, P, P, P, P],
@@ -329,7 +329,7 @@ def require_device():
 
 
 def f32_exact():
-    """DUALVAR_F32_EXACT as the LIBRARY reads it (csrc/conv.hip f32_exact(): atoi(value) != 0), so that the host's choice of
+    """DUALVAR_F32_EXACT as the LIBRARY reads it (csrc/conv_common.hpp f32_exact(): atoi(value) != 0), so that the host's choice of
     pre-split weights and the kernels' choice of MFMA never disagree ('2', '01', ' 1' all mean on; 'yes' means off)."""
     import re
     m = re.match(r'\s*([+-]?\d+)', os.environ.get('DUALVAR_F32_EXACT', ''))

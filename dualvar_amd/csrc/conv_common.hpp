@@ -1,7 +1,8 @@
-// Device-side pieces and argument blocks shared by the convolution translation units: conv.hip (the GEMM and DMA kernels and
-// all host code: one plan per call, route_conv for a forward / data gradient, plan_wgrad for a weight gradient), conv_tap.hip /
-// conv_tap_wgrad.hip (the LDS-staged kernels those plans can pick), conv_experiments.hip (the opt-in, not-selected form).
-// Everything sits in an anonymous namespace: each translation unit gets its own copy (argument blocks cross by address).
+// Device-side pieces and argument blocks shared by the convolution translation units: conv.hip (the forward / data gradient's host
+// layer: one route per call, route_conv), conv_gemm.hpp (the implicit-GEMM kernels it launches, built as conv_gemm_fwd.hip /
+// conv_gemm_dgrad.hip), conv_wgrad.hip (the weight gradient: kernels, plan_wgrad, entries), conv_tap.hip / conv_tap_wgrad.hip (the
+// LDS-staged kernels those plans can pick), conv_experiments.hip (the opt-in, not-selected form).  Functions sit in an anonymous
+// namespace; the argument blocks do not: they cross translation units by reference (the interface is this header's last section).
 #pragma once
 #include "common.hpp"
 #include <algorithm>
@@ -32,9 +33,9 @@ static int conv_tap_bm128() { static const int v = env_int("DUALVAR_CONV_TAP_BM1
 static int conv_tap_bm128_grid() { static const int v = env_int("DUALVAR_CONV_TAP_BM128_GRID", 768); return v; }
 // DUALVAR_CONV_PP_FWD=0: no pixel-pair stem form (conv_tap.hip: conv_pp_fwd_kernel)
 static int conv_pp_fwd() { static const int v = env_int("DUALVAR_CONV_PP_FWD", 1); return v; }
-// DUALVAR_CONV_KS=0: no K split over the waves (conv.hip: conv_gemm_ks_kernel)
+// DUALVAR_CONV_KS=0: no K split over the waves (conv_gemm.hpp: conv_gemm_ks_kernel)
 static int conv_ks() { static const int v = env_int("DUALVAR_CONV_KS", 1); return v; }
-
+}  // namespace
 struct ConvGeom {
   // "row space" (what m enumerates) and "source space" (the tensor the gather reads)
   int rT, rH, rW;        // row-space dims
@@ -58,6 +59,7 @@ struct RowPerm {
   int on, pT, pS, nfull, full_span;
   FastDiv fB, f32T, fwt;
 };
+namespace {
 static RowPerm make_row_perm(bool on, int T, int S) {
   RowPerm p;
   p.on = on ? 1 : 0; p.pT = T; p.pS = S; p.nfull = S / 32; p.full_span = p.nfull * 32 * T;
@@ -79,7 +81,7 @@ __device__ __forceinline__ uint32_t perm_row(const RowPerm& a, uint32_t q) {
   }
   return (n * (uint32_t)a.pT + t) * (uint32_t)a.pS + pix;
 }
-
+}  // namespace
 struct ConvArgs {
   const void* src;       // gathered tensor (x for fwd, dy for dgrad)
   const void* w;         // [N rows][Ktot] K-contiguous, pitch ldw
@@ -125,6 +127,7 @@ struct ConvArgs {
   const float* in_shift = nullptr;
   int in_C = 0, in_relu = 0;
 };
+namespace {
 
 template <int BYTES> struct VecB;
 template <> struct VecB<16> { typedef uint4 type; static __device__ __forceinline__ uint4 zero() { return make_uint4(0, 0, 0, 0); } };
@@ -182,19 +185,9 @@ __device__ __forceinline__ RowPos decode_row(uint32_t m, int M, const ConvGeom& 
   return r;
 }
 
-// source position (in elements/ld units) of (row, tap) or -1
-template <int MODE>
+// source position (in elements/ld units) of (forward row, tap) or -1 (its one user gathers x: conv_wgrad_kernel)
 __device__ __forceinline__ int src_pos(const RowPos& r, const KCursor& k, const ConvGeom& g) {
-  int t, h, w;
-  if (MODE == MODE_FWD) {
-    t = r.t0 + k.dt; h = r.h0 + k.dh; w = r.w0 + k.dw;
-  } else {
-    t = r.t0 - k.dt; h = r.h0 - k.dh; w = r.w0 - k.dw;
-    // strides are 1 or 2 (checked on the host)
-    if (((t & (g.st - 1)) | (h & (g.sh - 1)) | (w & (g.sw - 1))) != 0) return -1;
-    if ((t | h | w) < 0) return -1;
-    t >>= (g.st - 1); h >>= (g.sh - 1); w >>= (g.sw - 1);
-  }
+  const int t = r.t0 + k.dt, h = r.h0 + k.dh, w = r.w0 + k.dw;
   bool ok = r.valid && (k.dt < g.kt) && (unsigned)t < (unsigned)g.sT && (unsigned)h < (unsigned)g.sH &&
             (unsigned)w < (unsigned)g.sW;
   return ok ? r.base + (t * g.sH + h) * g.sW + w : -1;
@@ -392,7 +385,8 @@ __device__ __forceinline__ float act_apply(float v, int flags) {
   return v;
 }
 
-// ---- weight-gradient argument blocks (conv.hip, conv_experiments.hip) ----------------------------------------------------
+}  // namespace
+// ---- weight-gradient argument blocks (conv_wgrad.hip, conv_experiments.hip) ----------------------------------------------------
 struct WgradArgs {
   const void* x;
   const void* dy;
@@ -406,20 +400,6 @@ struct WgradArgs {
   ConvGeom g;
   RowPerm perm;           // row order of the DMA kernel (see RowPerm)
 };
-
-// one 32x32 accumulator block -> slab / dW.  Per register a half wave stores 32 consecutive floats (128 B).
-__device__ __forceinline__ void wgrad_store_block(const WgradArgs& a, int split, int row0, int col, int h, const f32x16& acc) {
-  if (col >= a.J) return;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (row < a.Cout) {
-      const size_t e = (size_t)row * a.ldw + col;
-      if (a.slab) a.slab[(size_t)split * a.slab_stride + e] = acc[r];
-      else a.dw[e] += acc[r];
-    }
-  }
-}
 
 // dv_conv3d_wgrad_bn: the dY operand is dv_bn_bwd_apply's output formed on the fly from g = dy and the BatchNorm's input x (same
 // rows / pitch as dy), the fields of dv_bn_bwd.  x == nullptr: plain weight gradient (nothing else is read).
@@ -436,6 +416,21 @@ struct WgradDmaArgs {
   int x_bytes, dy_bytes;
   BnBwdFuse bn;           // BNA
 };
+namespace {
+
+// one 32x32 accumulator block -> slab / dW.  Per register a half wave stores 32 consecutive floats (128 B).
+__device__ __forceinline__ void wgrad_store_block(const WgradArgs& a, int split, int row0, int col, int h, const f32x16& acc) {
+  if (col >= a.J) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    if (row < a.Cout) {
+      const size_t e = (size_t)row * a.ldw + col;
+      if (a.slab) a.slab[(size_t)split * a.slab_stride + e] = acc[r];
+      else a.dw[e] += acc[r];
+    }
+  }
+}
 
 // rows of RB bytes: four consecutive rows must fall on four different 64-byte bank groups of the 256-byte LDS line
 // (RB a multiple of 256: XOR the 64-byte chunk index with row&3; RB = 128 mod 256, i.e. 128 or 384: rows 0/1 already
@@ -455,6 +450,7 @@ __device__ __forceinline__ bf16x8 wg_frag(const unsigned char* tile, int col0, i
   return __builtin_bit_cast(bf16x8, v);
 }
 
+}  // namespace
 // ---- weight gradient of the stride-1 3x1x1 convs with LDS-staged, once-split operand tiles (conv_tap_wgrad.hip) -------------
 struct TmWgradArgs {
   const void* x;          // [N][T][S][ldx] fp32
@@ -484,4 +480,83 @@ struct TmWgradArgs {
   int in_C = 0, in_relu = 0;
 };
 
+// ==== the conv translation units' interface: everything one conv .hip defines and another calls ==================================
+// One conv_gemm_kernel launch as the route decided it: the tile, the gather (gm: 1 uniform tap, 0 generic), the LDS stages, and
+// for fp32 the bf16 split (split), pre-split weights (wf) and BatchNorm on load (bnl).  launch_gemm maps it to a template.
+struct GemmForm {
+  int bm, bn, gvb, gm, ns;
+  bool split, wf, bnl;
+};
+
+// the host helpers more than one of conv.hip / conv_gemm.hpp / conv_wgrad.hip needs
+namespace {
+static void fill_geom(const dv_conv_desc* d, int mode, ConvGeom& g) {
+  const bool fwd = mode == MODE_FWD;
+  g.kt = d->kt; g.kh = d->kh; g.kw = d->kw;
+  g.st = d->st; g.sh = d->sh; g.sw = d->sw;
+  g.pt = d->pt; g.ph = d->ph; g.pw = d->pw;
+  g.rT = fwd ? d->To : d->Ti; g.rH = fwd ? d->Ho : d->Hi; g.rW = fwd ? d->Wo : d->Wi;
+  g.sT = fwd ? d->Ti : d->To; g.sH = fwd ? d->Hi : d->Ho; g.sW = fwd ? d->Wi : d->Wo;
+  g.CP = fwd ? d->cin_pitch : d->cout_pitch;
+  g.Ktot = d->kt * d->kh * d->kw * g.CP;
+  g.dW = make_fastdiv((uint32_t)g.rW); g.dH = make_fastdiv((uint32_t)g.rH); g.dT = make_fastdiv((uint32_t)g.rT);
+}
+static int check_desc(const dv_conv_desc* d) {
+  if (!d) return DV_EINVAL;
+  if (d->dtype != DV_F32 && d->dtype != DV_BF16) return DV_EUNSUPPORTED;
+  if (d->N <= 0 || d->Ti <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Cin <= 0 || d->Cout <= 0) return DV_EINVAL;
+  if (d->kt <= 0 || d->kh <= 0 || d->kw <= 0 || d->st <= 0 || d->sh <= 0 || d->sw <= 0) return DV_EINVAL;
+  if (d->pt < 0 || d->ph < 0 || d->pw < 0) return DV_EINVAL;
+  if ((d->Ti + 2 * d->pt - d->kt) / d->st + 1 != d->To) return DV_EINVAL;
+  if ((d->Hi + 2 * d->ph - d->kh) / d->sh + 1 != d->Ho) return DV_EINVAL;
+  if ((d->Wi + 2 * d->pw - d->kw) / d->sw + 1 != d->Wo) return DV_EINVAL;
+  if (d->To <= 0 || d->Ho <= 0 || d->Wo <= 0) return DV_EINVAL;
+  const int gv_min = 4;
+  if (d->cin_pitch < d->Cin || d->cin_pitch % gv_min) return DV_EINVAL;
+  if (d->cout_pitch < d->Cout || d->cout_pitch % 8) return DV_EINVAL;
+  if (d->ldx < d->cin_pitch || d->ldy < d->cout_pitch) return DV_EINVAL;
+  const int esz = d->dtype == DV_F32 ? 4 : 2;
+  if ((d->ldx * esz) % 8 || (d->ldy * esz) % 16) return DV_EALIGN;
+  const int64_t mi = (int64_t)d->N * d->Ti * d->Hi * d->Wi, mo = (int64_t)d->N * d->To * d->Ho * d->Wo;
+  if (mi >= (1ll << 31) || mo >= (1ll << 31)) return DV_EINVAL;
+  return DV_OK;
+}
+// gather vector bytes for a channel pitch
+static int gather_bytes(int dtype, int cp) {
+  if (dtype == DV_F32) return 16;                   // 4 floats; cp % 4 == 0 checked
+  return (cp % 8 == 0) ? 16 : 8;                    // bf16: 8 elements, or 4 for the padded RGB input
+}
+// bytes from the first element of a [rows][ld] tensor of es-byte elements to the end of its last row's `cp` live channels:
+// what a buffer descriptor over the operand must span, and must be < 2 GiB for the kernels that address through one
+static int64_t extent_bytes(int64_t rows, int ld, int cp, int es) { return ((rows - 1) * ld + cp) * es; }
+static bool fits_descriptor(int64_t bytes) { return bytes < (1ll << 31); }
 }  // namespace
+
+// Plain C++ symbols of the shared object's own translation units, each declared HERE and nowhere else: every conv .hip includes this
+// header, so a definition is checked against the declaration its callers compile against.  Argument blocks cross by reference.
+// conv_tap.hip, the LDS-staged input-tile kernels: three predicates answer route_conv's questions, the launches run what it decided
+int dvt_conv_tap_kind(const ConvArgs& a, int mode);
+int dvt_conv_tap_bm(const ConvArgs& a, int kind);
+int dvt_conv_pp_lines(const ConvArgs& a, int mode);
+void dvt_conv_tap_launch(const ConvArgs& a, int mode, int kind, int bm, hipStream_t s);
+int dvt_conv_tap_pair_inst(const ConvArgs& a0, int kind0, int bm0, const ConvArgs& a1, int kind1, int bm1, int mode);
+void dvt_conv_tap_launch_pair(const ConvArgs& a0, const ConvArgs& a1, int mode, int kind, int bm, hipStream_t s);
+void dvt_conv_pp_launch(const ConvArgs& a, int G, hipStream_t s);
+int64_t dvt_bn_ws_floats(int64_t rows, int np);
+// conv_gemm_fwd.hip / conv_gemm_dgrad.hip (conv_gemm.hpp for one mode each): conv_gemm_kernel in the form `f` for bf16 / fp32 (dtype)
+// and for the fp8 pointwise GEMMs; conv_gemm_ks_kernel with column tile bn for one problem or two in one grid.  They set a.ntn.
+void dvg_fwd_gemm(int dtype, const GemmForm& f, ConvArgs& a, hipStream_t s);
+void dvg_fwd_gemm_fp8(const GemmForm& f, ConvArgs& a, hipStream_t s);
+void dvg_fwd_ks(int bn, ConvArgs& a, hipStream_t s);
+void dvg_fwd_ks_pair(int bn, ConvArgs& a0, ConvArgs& a1, hipStream_t s);
+void dvg_dgrad_gemm(int dtype, const GemmForm& f, ConvArgs& a, hipStream_t s);
+void dvg_dgrad_gemm_fp8(const GemmForm& f, ConvArgs& a, hipStream_t s);
+void dvg_dgrad_ks(int bn, ConvArgs& a, hipStream_t s);
+void dvg_dgrad_ks_pair(int bn, ConvArgs& a0, ConvArgs& a1, hipStream_t s);
+// conv_wgrad.hip: the weight gradient's plan has a form that applies the BatchNorm in front of the conv on load
+bool dvwg_bn_in_ok(const dv_conv_desc* d);
+// conv_experiments.hip: conv_wgrad_f32s_kernel, the fp32 split mode's second weight-gradient form (opt-in only)
+int dvx_wgrad_f32s_shape(int cfg, int* bi, int* bj);          // tile; returns the LDS bytes of a workgroup
+void dvx_launch_wgrad_f32s(int cfg, const WgradDmaArgs& aa, int grid, hipStream_t s);
+// conv_tap_wgrad.hip: the LDS-staged weight gradients
+void dvw_wgrad_tm_launch(const TmWgradArgs& a, int grid, hipStream_t s);

@@ -376,18 +376,15 @@ __attribute__((amdgpu_waves_per_eu(wgrad_f32s_waves_per_simd(BI, BJ, ROWS, NS)))
 
 }  // namespace
 
-// ---- entry points for conv.hip (plain C++ symbols of the shared object's own translation units; the argument block is
-// conv_common.hpp's WgradDmaArgs, passed by address because each translation unit has its own anonymous-namespace copy of
-// the type).  Configurations: 0 = 64 x 256 tile, 16 rows per step; 2 = 128 x 128, 16 rows (the two the sweep kept: the other
+// ---- entry points for conv_wgrad.hip (plain C++ symbols of the shared object's own translation units, declared in
+// conv_common.hpp's interface section).  Configurations: 0 = 64 x 256 tile, 16 rows per step; 2 = 128 x 128, 16 rows (the two the sweep kept: the other
 // four shapes of round 3 -- 32-row steps, 128 x 256, 64 x 128 -- were never faster anywhere and are gone).
 int dvx_wgrad_f32s_shape(int cfg, int* bi, int* bj) {          // the tile; returns the LDS bytes of a workgroup
   *bi = cfg == 0 ? 64 : 128;
   *bj = cfg == 0 ? 256 : 128;
   return wgrad_f32s_lds(*bi, *bj, 16, 3);
 }
-void dvx_launch_wgrad_f32s(int cfg, const void* args, int grid, void* stream) {
-  const WgradDmaArgs& aa = *static_cast<const WgradDmaArgs*>(args);
-  hipStream_t s = (hipStream_t)stream;
+void dvx_launch_wgrad_f32s(int cfg, const WgradDmaArgs& aa, int grid, hipStream_t s) {
   if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_f32s_kernel<64, 256, 16, 3>), dim3(grid), dim3(256), 0, s, aa);
   else hipLaunchKernelGGL((conv_wgrad_f32s_kernel<128, 128, 16, 3>), dim3(grid), dim3(256), 0, s, aa);
 }

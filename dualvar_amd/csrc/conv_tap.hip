@@ -1,7 +1,7 @@
 // LDS-staged input tiles for the separable convolutions (fp32 split mode): the stride-1 "same" 1x3x3 and 3x1x1 convs of
 // backbone/s3dg.py:30-65 (STConv3d: 1xkxk -> BN -> ReLU -> kx1x1) and backbone/r21d.py:11-70 -- forward and data gradient.
 //
-// conv_gemm_kernel (conv.hip) is a per-tap implicit GEMM: every (tap, 16-channel) K tile costs one global -> LDS DMA round of the
+// conv_gemm_kernel (conv_gemm.hpp) is a per-tap implicit GEMM: every (tap, 16-channel) K tile costs one global -> LDS DMA round of the
 // activation tile and, in the fp32 mode, one split of its fragments into bf16 triples; the round-3 ablation priced those two at
 // 172 of the 523 us of Conv_2c's 1x3x3 forward, and nothing overlapped the matrix pipe.  Here a workgroup stages the 16-channel
 // slab of its 256 output positions ONCE per channel chunk -- with the halo its taps reach --, splits it ONCE into bf16 planes in
@@ -52,7 +52,7 @@ struct TapArgs {
   FastDiv fW, fH;
   int T, S, P, lgP, NQ;   // temporal: frames, pixels per frame, pixels per tile (256 / T), log2 P, N * S
   FastDiv fS;
-  // temporal, general form (the parity classes of a t-strided data gradient, conv.hip ConvArgs::cls_on == 1: every class is a
+  // temporal, general form (the parity classes of a t-strided data gradient, conv_common.hpp ConvArgs::cls_on == 1: every class is a
   // dense stride-1 problem over T frames of dY): tap j reads frame f + sgn * (j - pt); its weights sit at the ORIGINAL tap
   // wt0 + wts * j; row frame f is frame f * ofs + ofo of an output tensor with oT frames
   int pt, wt0, wts, oT, ofs, ofo;
@@ -847,15 +847,14 @@ int64_t dvt_bn_ws_floats(int64_t rows, int np) {
   return kBnTickWords + (int64_t)ntn * bn_ws_floats_per_coltile(n_mt);
 }
 
-// entry points for conv.hip (the argument block is conv_common.hpp's ConvArgs, passed by address).  The route (conv.hip:
-// route_conv) asks the three predicates and launches what they answered; the launches decide nothing themselves.
-int dvt_conv_pp_lines(const void* conv_args, int mode) { return pp_lines(*static_cast<const ConvArgs*>(conv_args), mode); }
-int dvt_conv_tap_kind(const void* conv_args, int mode) { return tap_kind(*static_cast<const ConvArgs*>(conv_args), mode); }
-int dvt_conv_tap_bm(const void* conv_args, int kind) { return tap_bm(*static_cast<const ConvArgs*>(conv_args), kind); }
+// entry points for conv.hip (declared in conv_common.hpp's interface section).  The route (conv.hip: route_conv) asks the three
+// predicates and launches what they answered; the launches decide nothing themselves.
+int dvt_conv_pp_lines(const ConvArgs& a, int mode) { return pp_lines(a, mode); }
+int dvt_conv_tap_kind(const ConvArgs& a, int mode) { return tap_kind(a, mode); }
+int dvt_conv_tap_bm(const ConvArgs& a, int kind) { return tap_bm(a, kind); }
 
 // the pixel-pair stem form with tiles of G output lines (G = dvt_conv_pp_lines)
-void dvt_conv_pp_launch(const void* conv_args, int G, void* stream) {
-  const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);
+void dvt_conv_pp_launch(const ConvArgs& a, int G, hipStream_t s) {
   const ConvGeom& g = a.g;
   PpArgs t;
   t.src = a.src; t.w = a.w; t.out = a.out; t.stats = a.stats;
@@ -867,7 +866,7 @@ void dvt_conv_pp_launch(const void* conv_args, int G, void* stream) {
   t.fWo = make_fastdiv((uint32_t)g.rW); t.fWp = make_fastdiv((uint32_t)g.sW); t.fHg = make_fastdiv((uint32_t)t.Hg);
   const int grid = t.ntn * (a.M / t.rows);
   const size_t lds = 2 * 64 * 96 + (size_t)t.npos * 48;
-  hipLaunchKernelGGL((conv_pp_fwd_kernel<2>), dim3(grid), dim3(256), lds, (hipStream_t)stream, t);
+  hipLaunchKernelGGL((conv_pp_fwd_kernel<2>), dim3(grid), dim3(256), lds, s, t);
 }
 
 // the launch of the LDS-staged kernel in form `kind` (dvt_conv_tap_kind) with tiles of bm rows (dvt_conv_tap_bm)
@@ -931,24 +930,21 @@ static void launch_tap_inst(const TapLaunch& l, const TapLaunch* l1, hipStream_t
   }
 }
 
-void dvt_conv_tap_launch(const void* conv_args, int mode, int kind, int bm, void* stream) {
-  launch_tap_inst(tap_launch_of(*static_cast<const ConvArgs*>(conv_args), mode, kind, bm), nullptr, (hipStream_t)stream);
+void dvt_conv_tap_launch(const ConvArgs& a, int mode, int kind, int bm, hipStream_t s) {
+  launch_tap_inst(tap_launch_of(a, mode, kind, bm), nullptr, s);
 }
 
 // Two launches in one grid (conv_tap_pair_kernel).  dvt_conv_tap_pair_inst: the instantiation both would run alone, or 0 where
 // they differ or a member may not share a grid: one that carries the fused BatchNorm-backward reduce (the members would share the
 // ticket workspace) or is a parity class of a strided data gradient.  The launch runs what the query said; conv.hip asks first.
-int dvt_conv_tap_pair_inst(const void* args0, int kind0, int bm0, const void* args1, int kind1, int bm1, int mode) {
-  const ConvArgs& a0 = *static_cast<const ConvArgs*>(args0);
-  const ConvArgs& a1 = *static_cast<const ConvArgs*>(args1);
+int dvt_conv_tap_pair_inst(const ConvArgs& a0, int kind0, int bm0, const ConvArgs& a1, int kind1, int bm1, int mode) {
   if (!kind0 || kind0 != kind1 || bm0 != bm1) return 0;
   if (a0.bn_x != nullptr || a1.bn_x != nullptr || a0.cls_on || a1.cls_on) return 0;
   const int i0 = tap_launch_of(a0, mode, kind0, bm0).inst, i1 = tap_launch_of(a1, mode, kind1, bm1).inst;
   return i0 == i1 ? i0 : 0;
 }
 
-void dvt_conv_tap_launch_pair(const void* args0, const void* args1, int mode, int kind, int bm, void* stream) {
-  const TapLaunch l0 = tap_launch_of(*static_cast<const ConvArgs*>(args0), mode, kind, bm);
-  const TapLaunch l1 = tap_launch_of(*static_cast<const ConvArgs*>(args1), mode, kind, bm);
-  launch_tap_inst(l0, &l1, (hipStream_t)stream);
+void dvt_conv_tap_launch_pair(const ConvArgs& a0, const ConvArgs& a1, int mode, int kind, int bm, hipStream_t s) {
+  const TapLaunch l0 = tap_launch_of(a0, mode, kind, bm), l1 = tap_launch_of(a1, mode, kind, bm);
+  launch_tap_inst(l0, &l1, s);
 }

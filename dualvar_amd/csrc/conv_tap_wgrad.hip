@@ -4,7 +4,7 @@
 //
 //   dW[n][dt][c] = sum over clips, pixels p, frames f:  dY[f][p][n] * X[f + dt - 1][p][c]
 //
-// conv_wgrad_dma_kernel (conv.hip) treats this as a GEMM over rows with J = (tap, channel) columns: every tap's column tile
+// conv_wgrad_dma_kernel (conv_wgrad.hip) treats this as a GEMM over rows with J = (tap, channel) columns: every tap's column tile
 // fetches and splits its own copy of the x rows (the same rows one frame apart) and of dY.  Here a workgroup owns 64 output
 // channels x 64 input channels x ALL THREE taps and a range of pixels; a step stages 64 / T pixels of ALL T frames of both
 // operands once (global -> registers -> bf16 triples -> row-major planes in LDS), and each (frame, tap) pair whose source frame
@@ -608,10 +608,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 }  // namespace
 
-// entry point for conv.hip (the argument block is conv_common.hpp's TmWgradArgs, passed by address)
-void dvw_wgrad_tm_launch(const void* args, int grid, void* stream) {
-  const TmWgradArgs& a = *static_cast<const TmWgradArgs*>(args);
-  hipStream_t s = (hipStream_t)stream;
+// entry point for conv_wgrad.hip (declared in conv_common.hpp's interface section)
+void dvw_wgrad_tm_launch(const TmWgradArgs& a, int grid, hipStream_t s) {
   if (a.kind == 4) {
     if (a.bn.x) hipLaunchKernelGGL((conv_wgrad_pp_kernel<true>), dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_wgrad_pp_kernel<false>), dim3(grid), dim3(256), 0, s, a);

@@ -1,5 +1,5 @@
 /* Two independent convs in one grid, beside dualvar_hip.h: the pair entries of dv_conv3d_fwd / dv_conv3d_fwd_bn_in /
- * dv_conv3d_dgrad (csrc/conv.hip, csrc/conv_tap.hip).  Same conventions: plain C, device pointers, the stream last, 0 on success,
+ * dv_conv3d_dgrad (csrc/conv.hip; kernels csrc/conv_gemm.hpp, csrc/conv_tap.hip).  Same conventions: plain C, device pointers, the stream last, 0 on success,
  * DV_E* (< 0) for refused arguments before anything is launched, a hipError_t (> 0) for a failed launch.
  * ctypes mirror: dualvar_amd/_lib.py PAIR_SIGNATURES (tests/test_conv_pair_host.py compares the two). */
 #ifndef DUALVAR_CONV_PAIR_H

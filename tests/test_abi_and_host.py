@@ -1003,3 +1003,61 @@ def test_ordered_fold_protocol_has_one_home():
     loss = open(os.path.join(csrc, 'loss.hip')).read()
     assert not re.search(r's_waitcnt\s+vmcnt\(0\)"\s*:\s*:\s*:\s*"memory"', loss)
     assert '#include "ordered_fold.hpp"' in loss
+
+
+def test_conv_interface_has_one_home():
+    """The conv sources talk across translation units through plain C++ functions (dvt_ conv_tap.hip, dvg_ conv_gemm_fwd.hip / conv_gemm_dgrad.hip, dvwg_
+    conv_wgrad.hip, dvw_ conv_tap_wgrad.hip, dvx_ conv_experiments.hip).  Each is declared exactly once, in the interface section
+    that ends csrc/conv_common.hpp, and nowhere else; every conv source includes that header, so the compiler checks each
+    definition against the declaration its callers see; and no definition takes an argument block (or anything else) as void*.
+    A prototype copied back into a .hip, a crossing function without a declaration in the header, or a type-erased argument
+    fails here."""
+    csrc = os.path.join(ROOT, 'dualvar_amd', 'csrc')
+    convs = sorted(f for f in os.listdir(csrc) if f.startswith('conv') and f.endswith('.hip'))
+    assert convs == ['conv.hip', 'conv_experiments.hip', 'conv_gemm_dgrad.hip', 'conv_gemm_fwd.hip', 'conv_tap.hip', 'conv_tap_wgrad.hip',
+                     'conv_wgrad.hip']
+    from dualvar_amd.build import SOURCES
+    assert set(convs) <= set(SOURCES)
+    text = {f: open(os.path.join(csrc, f)).read() for f in convs}
+    hdr = open(os.path.join(csrc, 'conv_common.hpp')).read()
+    cut = hdr.index("// ==== the conv translation units' interface")
+    before, iface = hdr[:cut], hdr[cut:]
+
+    def proto(name):      # a declaration: return type, name, parameter list, semicolon
+        return re.compile(r'^[ \t]*(?!return\b|else\b)[\w<>]+[\w<>\s*&]*?[\s*&]' + name + r'\s*\([^;{]*\)\s*;', re.M)
+
+    def definition(name):
+        return re.compile(r'^[\w<>]+[\w<>\s*&]*?[\s*&]' + name + r'\s*\(([^;{]*)\)\s*\{', re.M)
+
+    # what crosses: every function with C++ linkage that a conv source defines outside its anonymous namespaces ...
+    external = {}
+    for f in convs:
+        anon = 0
+        for line in text[f].split('\n'):
+            if line.startswith('namespace {'):
+                anon += 1
+            elif line.startswith('}  // namespace'):
+                anon -= 1
+            elif not anon:
+                m = re.match(r'(?!static\b|extern\b|template\b|struct\b|enum\b|typedef\b|constexpr\b|using\b)[\w<>]+[\w<>\s*&]*?[\s*&]'
+                             r'(\w+)\s*\((?:[^;{]*\)\s*\{|[^;{)]*$)', line)
+                if m:
+                    assert m.group(1) not in external, m.group(1)
+                    external[m.group(1)] = f
+        assert anon == 0, f
+    # ... which is every dvt_ / dvg_ / ... name that any of them mentions
+    called = set(n for t in text.values() for n in re.findall(r'\bdv[a-z]+_\w+', t))
+    assert set(external) == called and len(called) >= 20, (sorted(set(external) ^ called), len(called))
+    for name, home in sorted(external.items()):
+        assert len(proto(name).findall(iface)) == 1, name
+        assert not proto(name).search(before), name
+        for f in convs:
+            assert not proto(name).search(text[f]), (name, f)
+        users = [f for f in convs if f != home and re.search(r'\b' + name + r'\b', text[f])]
+        assert users, name
+        defs = definition(name).findall(text[home])
+        assert len(defs) == 1 and not re.search(r'\bvoid\s*\*', defs[0]), (name, defs)
+    gemm_hpp = open(os.path.join(csrc, 'conv_gemm.hpp')).read()      # (the two conv_gemm_*.hip include the header through it)
+    assert '#include "conv_common.hpp"' in gemm_hpp and not any(proto(n).search(gemm_hpp) for n in external)
+    for f in convs:
+        assert '#include "conv_common.hpp"' in text[f] or (f.startswith('conv_gemm_') and '#include "conv_gemm.hpp"' in text[f]), f

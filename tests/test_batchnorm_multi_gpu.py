@@ -287,7 +287,7 @@ def test_stats_from_conv_epilogue_partials(gpu, dtype):
     """a pointwise conv with DV_STATS whose Cout is split into three members, as the engine slices a merged conv (partials
     pointer at the member's first channel, pitch = Cout): the statistics against float64 of the STORED conv output.
     The epilogue's tile sum and M2 add at most tile_rows terms in a row.  fp32 takes M2 about the tile mean (two passes);
-    bf16 about a provisional centre c, one of the tile's values (conv.hip), merged with Chan's formula: its terms are
+    bf16 about a provisional centre c, one of the tile's values (conv_gemm.hpp), merged with Chan's formula: its terms are
     bounded by (x - c)^2 <= 4 max_tile (x - m)^2 and its sum by |x| + |c| <= |x| + max_tile |x|."""
     f32 = dtype == DV_F32
     if f32 and L.f32_exact():

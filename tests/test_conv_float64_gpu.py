@@ -1,4 +1,4 @@
-"""The convolution kernels (csrc/conv.hip, conv_tap.hip, conv_tap_wgrad.hip) against a float64 reference, on the route
+"""The convolution kernels (csrc/conv_gemm.hpp, conv_wgrad.hip, conv_tap.hip, conv_tap_wgrad.hip; host layer csrc/conv.hip) against a float64 reference, on the route
 each row of tests/conv_cases.py names.  Every entry is called through the C ABI / dualvar_amd.ops on explicit tensors.
 
 Reference: a plain float64 convolution (`ref_fwd`, `ref_dgrad`, `ref_wgrad` of tests/conv_reference.py): a loop over the kernel taps, each

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel register / LDS / occupancy table of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
 
-    python tools/kernel_resources.py dualvar_amd/csrc/conv.hip [name filter]
+    python tools/kernel_resources.py dualvar_amd/csrc/conv_gemm_fwd.hip [name filter]
 
 Reads the report the library build keeps next to the object (csrc/<name>.res) when it is newer than the source, otherwise
 compiles the file.
